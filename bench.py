@@ -11,8 +11,12 @@ A "step" is one full-batch optimisation iteration over the synthetic 72-view cap
     loss.backward()  -> grad[V,3]; all-reduce over ranks (views are sharded round-robin)
     limit_hook + SGD(nesterov) step                  (optim.py:155-171, 215)
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mode dropin|fused] [--res R] [--views V]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mode dropin|fused] [--res R] [--views V] [--full] [--dump-outputs DIR]
 For N > 1 launch under torch.distributed.run (one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, takes W untimed steps (at least 3), times exactly K steps, writes the last step's outputs if --dump-outputs is
+given and prints the line.  --full adds everything else the line can carry: a sustained measurement, the roofline and per-stage tables,
+the fused / establish / tight-framing / route-B extras, the drop-in vs fused loss check and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -246,6 +250,16 @@ def roofline(prof, args, P, n_local_views, V, F, elapsed, world, prof_alone=None
     return top
 
 
+def usable_cpus():
+    """CPUs this process may run on: its affinity mask, capped by OMP_NUM_THREADS when that is set (os.cpu_count() counts the
+    whole host, and a pool sized by it on a share of the host only oversubscribes that share)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def cpu_baseline(mesh, center, extent):
     """the oracle (port of the reference's CPU path: brute-force float32 tracer + float64 PyTorch
     autograd, `BASELINE.json:configs[0]`) on the GPU box's host cores, forward + backward, median of 3:
@@ -254,7 +268,7 @@ def cpu_baseline(mesh, center, extent):
     `value` is (ii).  For context also a 768x768 slice and the same path with a BVH tracer instead of the brute force."""
     import statistics
     from oracle import diffrender_oracle as orc
-    cores = os.cpu_count() or 1
+    cores = usable_cpus()
     orc.TRACER_THREADS = cores                       # the C tracers use every core ...
     orc.TORCH_THREADS = min(32, cores)               # ... PyTorch's float64 ops do not scale past a few dozen threads (they collapse at 256)
     torch.set_num_threads(orc.TORCH_THREADS)
@@ -400,6 +414,22 @@ def regime_roofline(scene, step_fn, kk, n_rays_per_step, verify_every_ray, pmc_m
             "stages_alone_ms_per_step": {k: round(v, 4) for k, v in alone.items()}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write every array as `dirname/<name>.npy` in float64.  If the set would take more than `limit` bytes, every array of more
+    than one row is cut to the same fraction of its rows, chosen by a fixed seed: the same rows in every run with the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit and a.ndim > 0 and len(a) > 1:
+            keep = max(1, int(len(a) * (limit - (1 << 16)) / total))       # (64 KiB left for the .npy headers and the one-row arrays)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -421,27 +451,40 @@ def main():
                          "-1 (default): graph when N > 1 AND the rank's share is below 24 views x 1024^2 camera rays (a chain of small launches: "
                          "9 views 0.655 vs 0.691 ms eager, 18 views 0.792 vs 0.819; above, the eager step is the faster one: 36 views 1.177 vs 1.204) "
                          "-- eager otherwise; falls back to eager if the capture fails")
-    ap.add_argument("--repeats", type=int, default=int(os.environ.get("DRT_BENCH_REPEATS", "0")),
-                    help="the timed region (exactly --steps steps between two barrier + synchronize pairs) is run this many times back to back. "
-                         "0 (default): SUSTAINED mode -- at least 5 repeats and as many as it takes for --min-seconds of timed steps; `value` / "
+    ap.add_argument("--repeats", type=int, default=int(os.environ.get("DRT_BENCH_REPEATS", "1")),
+                    help="the timed region (exactly --steps steps between two barrier + synchronize pairs) is run this many times back to back, "
+                         "and `value` / `ms_per_step` are those of the median repeat.  1 (default): one region, exactly --steps timed steps.  "
+                         "0: SUSTAINED mode -- at least 5 repeats and as many as it takes for --min-seconds of timed steps; `value` / "
                          "`ms_per_step` are then those of the median repeat among the ones that STARTED after the first --settle-seconds of timed "
                          "steps (the chip's clocks settle over the first few hundred milliseconds of sustained load), the first repeat's figure "
-                         "is reported beside it.  R > 0: exactly R repeats, the median of all of them")
+                         "is reported beside it.  (--full with R > 0 runs a sustained measurement after the headline and reports it as `sustained`)")
     ap.add_argument("--min-seconds", type=float, default=float(os.environ.get("DRT_BENCH_MIN_SECONDS", "3.0")),
                     help="sustained mode: total length of the timed regions (s)")
     ap.add_argument("--settle-seconds", type=float, default=1.0, help="sustained mode: repeats that start before this much timed time has passed do not count for `value`")
-    ap.add_argument("--reset-every", type=int, default=200,
-                    help="between two repeats (outside the timed regions) the parameter and the momentum buffer are put back to their initial state once this many "
-                         "steps were taken since the last reset, so that a long sustained run stays within the first iterations of a pass "
-                         "(BASELINE.json: 200 iterations per pass) instead of timing whatever mesh 2 000 steps of descent on synthetic targets produce; 0 = never")
+    ap.add_argument("--reset-every", type=int, default=50,
+                    help="the parameter and the momentum buffer are put back to their initial state once this many steps (untimed ones included) were "
+                         "taken since the last reset -- between two repeats, or inside a longer timed region as two in-place fills enqueued in front of "
+                         "the next step (timed with it, no drain) -- so that a long "
+                         "run stays within the first iterations of a pass (BASELINE.json: 200 iterations per pass) instead of timing whatever mesh 2 000 "
+                         "steps of descent on synthetic targets produce.  50: the float64 atomics of the gradient sums differ in the last bits from run to "
+                         "run, and this descent amplifies that (two runs 8e-13 apart after 70 steps from the same state, 3e-3 after 130), so a shorter "
+                         "horizon keeps the last step's outputs (--dump-outputs) equal to rounding from run to run; 0 = never")
     ap.add_argument("--bind", type=int, default=1,
                     help="1 (default): the views' rays and targets are handed to the scene ONCE (scene.bind_rays -> diffrender.RayBinding) and every step "
                          "renders through the handle: trusted grids and recycled outputs by contract; 0: the drop-in signature render_transparent(origin, "
                          "ray_dir) on the same tensors every step, which reaches the same kernels through tensor-identity heuristics and torch's storage use counts")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: the sustained measurement, the roofline and per-stage tables, "
+                         "the fused / establish / tight-framing / route-B extras, the drop-in vs fused loss check, the CPU baseline.  "
+                         "Off by default: a plain run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned -- the loss of all views, the parameter after the "
+                         "optimiser step and the gradient it applied -- as DIR/<name>.npy (float64; a fixed, seeded sample of the rows above "
+                         f"{DUMP_LIMIT_BYTES >> 20} MB in all).  The inputs are identical from run to run with the same arguments")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed extras after the timed region (fused-mode comparison, traversal statistics); "
-                         "used under rocprofv3 so that the trace ends with the timed steps")
+                    help="with --full: skip the extras after the timed region (sustained measurement, fused-mode comparison, traversal "
+                         "statistics); the roofline and stage tables are still taken")
     ap.add_argument("--displaced-targets", action="store_true", help="targets from a noise-displaced hull even when data/<mesh>_scan.ply exists")
     ap.add_argument("--random-targets", action="store_true",
                     help="skip the ground-truth render of the setup (targets = random points); used for PMC passes so that every "
@@ -524,6 +567,7 @@ def main():
         small = len(my_views) * P < (3 << 23)
         args.graph = 1 if world > 1 and small and os.environ.get("DRT_BENCH_GRAPH", "1") != "0" and os.environ.get("DRT_DIST_BACKEND") != "gloo" else 0
     graph = None
+    untimed = 0                                      # steps taken before the timed region, each of them an optimiser step (--reset-every counts them)
     if args.graph:
         # The step has no host-side data dependence (every list size lives on the device), so it can be
         # captured once and replayed: one graph launch per step instead of ~60 kernel launches.
@@ -532,6 +576,7 @@ def main():
         with torch.cuda.stream(side):
             for _ in range(max(3, args.warmup)):
                 step(False)
+                untimed += 1
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         try:
@@ -539,6 +584,7 @@ def main():
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):      # (the process group's watchdog thread may query events meanwhile)
                 static_loss = step(False)
             graph.replay()
+            untimed += 1                             # (the capture itself runs nothing; its first replay is a step)
             torch.cuda.synchronize()
             ok = torch.tensor([1.0], device=dev)
         except Exception as e:                      # (a capture that fails must fail on every rank alike: the ranks agree below)
@@ -556,12 +602,13 @@ def main():
     # at least three untimed steps whatever --warmup says: the first call on a capture's ray tensors ESTABLISHES the grid verdict, the second
     # reads it back (one host sync per ray tensor, ever), and the caching allocator has its steady set of blocks from the third on
     for _ in range(max(args.warmup, 3)):
+        untimed += 1
         loss = run()     # (held like in the timed loop: the previous step's loss keeps its autograd nodes -- and the face-id / path-list arrays they
                          #  reference -- alive while the next step allocates, so the caching allocator must see THAT pattern before the timed region:
                          #  a first hipMalloc of a 1.8 GB block inside it costs 30 ms on a box whose driver clears the memory first)
-    # N = 1: the per-kernel hipEvent pairs are recorded live inside the timed region (the roofline contract).  N > 1: they
+    # N = 1, --full: the per-kernel hipEvent pairs are recorded live inside the timed region (the roofline contract).  N > 1: they
     # are recorded in an eager repeat right after it, so that ~120 event records per step do not sit in a 1.7 ms step.
-    live_profile = not args.graph and world == 1 and not os.environ.get('DRT_BENCH_NOPROF')
+    live_profile = args.full and not args.graph and world == 1 and not os.environ.get('DRT_BENCH_NOPROF')
     # the launches of the kernel the roofline is about (k_trace<closest> on the refracted rays: the closest-hit launch on rays outside the grid
     # is not even issued when every ray is a verified grid ray).  Every event pair is a stream marker that keeps the next kernel from
     # starting under the previous one's tail (~8 us each): with the occlusion launches and the empty first-traversal stage timed live too,
@@ -571,48 +618,78 @@ def main():
         scene.optix_mesh.profile_select(LIVE)   # hipEvent pairs around the traversal kernels only (the other stages are
         scene.optix_mesh.profile_enable(True)   # timed in the repeat below: ~50 more event records per step cost 0.15 ms of 3.3)
         scene.optix_mesh.profile_read()
-    # The timed region -- exactly K steps between two (barrier, synchronize) pairs, max over ranks -- run R times back to back; the line
-    # reports the MEDIAN repeat (a 35 ms region on its own is one scheduling hiccup away from a wrong number, and too short for an outside
-    # observer's utilisation samples to see the GPU busy), every repeat is listed.
-    repeats = []
-    ms0 = torch.cuda.memory_stats(dev)
-    sustained = args.repeats <= 0
-    timed_total, since_reset, n_resets = 0.0, max(args.warmup, 3), 0
-    starts = []                                      # timed seconds in front of each repeat
-    while True:
-        rep = len(repeats)
-        if (not sustained and rep >= args.repeats) or (sustained and rep >= 5 and timed_total >= args.min_seconds) or rep >= 2000:
-            break
-        if args.reset_every > 0 and since_reset + args.steps > args.reset_every and rep > 0:
-            # (untimed, between two regions; in place, so that a captured graph sees it too: momentum buffer 0 = a first step)
+
+    def timed_region(n_repeats, since_reset):
+        """The timed region -- exactly K steps between two (barrier, synchronize) pairs, max over ranks -- run `n_repeats` times back to
+        back (0: sustained mode, see --repeats); `elapsed` is the MEDIAN repeat's, every repeat is listed.  `loss` is rebound every step like
+        in the warm-up: the previous step's loss (and what its autograd nodes reference) lives while the next step allocates.
+        Every --reset-every steps (untimed ones included) parameter and momentum go back to their initial state -- between two repeats
+        (untimed), or inside a region longer than that: there two in-place fills on the compute stream, ordered like the optimiser's own
+        in-place update and timed with the step (no drain) -- so that a run of any length times the first iterations of a pass, and its
+        last step starts at most --reset-every steps after a state that is the same in every run."""
+        nonlocal loss
+        repeats, starts = [], []                     # (seconds, host enqueue ms per step) of each repeat; timed seconds in front of it
+        sustained = n_repeats <= 0
+        timed_total, n_resets = 0.0, 0
+
+        def reset():
+            # (in place, so that a captured graph sees it too: momentum buffer 0 = a first step)
+            nonlocal since_reset, n_resets
             with torch.no_grad():
                 parameter.zero_()
                 if getattr(opt, "buf", None) is not None:
                     opt.buf.zero_()
             since_reset, n_resets = 0, n_resets + 1
-        since_reset += args.steps
-        if live_profile:
-            scene.optix_mesh.profile_read()          # (drops the event pairs of the previous repeat: the stage rows are the last repeat's)
-        ddist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        host_marks = []
-        for _ in range(args.steps):
-            loss = run()
-            host_marks.append(time.perf_counter())
-            if os.environ.get("DRT_BENCH_ALLOC_TRACE"):
-                m = torch.cuda.memory_stats(dev)
-                print("step", len(host_marks), "device_alloc", m["num_device_alloc"], "reserved_GB", round(m["reserved_bytes.all.current"] / 2 ** 30, 3),
-                      "active_GB", round(m["active_bytes.all.current"] / 2 ** 30, 3), "peak_active_GB", round(m["active_bytes.all.peak"] / 2 ** 30, 3), file=sys.stderr, flush=True)
-        ddist.barrier()
-        torch.cuda.synchronize()
-        repeats.append((ddist.allreduce_max_float(time.perf_counter() - t0, dev), [1e3 * (b - a) for a, b in zip([t0] + host_marks[:-1], host_marks)]))
-        starts.append(timed_total)
-        timed_total += repeats[-1][0]                # (the max over ranks: every rank takes the same number of repeats)
+        while True:
+            rep = len(repeats)
+            if (not sustained and rep >= n_repeats) or (sustained and rep >= 5 and timed_total >= args.min_seconds) or rep >= 2000:
+                break
+            if args.reset_every > 0 and since_reset + args.steps > args.reset_every and rep > 0:
+                reset()                              # (untimed, between two regions)
+            if live_profile:
+                scene.optix_mesh.profile_read()          # (drops the event pairs of the previous repeat: the stage rows are the last repeat's)
+            ddist.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            host_ms = []
+            for _ in range(args.steps):
+                ts = time.perf_counter()
+                if args.reset_every > 0 and since_reset >= args.reset_every:
+                    reset()                          # (a region longer than --reset-every; every rank at the same step)
+                loss = run()
+                since_reset += 1
+                host_ms.append(1e3 * (time.perf_counter() - ts))
+                if os.environ.get("DRT_BENCH_ALLOC_TRACE"):
+                    m = torch.cuda.memory_stats(dev)
+                    print("step", len(host_ms), "device_alloc", m["num_device_alloc"], "reserved_GB", round(m["reserved_bytes.all.current"] / 2 ** 30, 3),
+                          "active_GB", round(m["active_bytes.all.current"] / 2 ** 30, 3), "peak_active_GB", round(m["active_bytes.all.peak"] / 2 ** 30, 3), file=sys.stderr, flush=True)
+            ddist.barrier()
+            torch.cuda.synchronize()
+            repeats.append((ddist.allreduce_max_float(time.perf_counter() - t0, dev), host_ms))
+            starts.append(timed_total)
+            timed_total += repeats[-1][0]                # (the max over ranks: every rank takes the same number of repeats)
+        counted = [k for k in range(len(repeats)) if sustained and starts[k] >= args.settle_seconds] or list(range(len(repeats)))
+        order = sorted(counted, key=lambda k: repeats[k][0])
+        elapsed, host_ms = repeats[order[(len(order) - 1) // 2]]      # the median repeat (the lower one of an even count) among the counted ones
+        summary = {"n": len(repeats), "reported": f"median of the {len(counted)} repeats that started after {args.settle_seconds} s of timed steps" if sustained and len(counted) < len(repeats) else "median",
+                   "ms_per_step": [round(1e3 * t / args.steps, 3) for t, _ in repeats],
+                   "min": round(1e3 * min(repeats[k][0] for k in counted) / args.steps, 3), "median": round(1e3 * elapsed / args.steps, 3),
+                   "max": round(1e3 * max(repeats[k][0] for k in counted) / args.steps, 3), "timed_region_ms_total": round(1e3 * sum(t for t, _ in repeats), 1),
+                   "first_repeat": round(1e3 * repeats[0][0] / args.steps, 3), "sustained": sustained, "n_counted": len(counted),
+                   # the plateau, visibly: median ms/step of the repeats that started within each successive half second of timed steps
+                   "by_half_second": [round(1e3 * sorted(repeats[k][0] for k in ks)[(len(ks) - 1) // 2] / args.steps, 3)
+                                      for ks in ([k for k in range(len(repeats)) if int(starts[k] / 0.5) == b] for b in range(int(timed_total / 0.5) + 1)) if ks],
+                   "parameter_resets": n_resets, "reset_every_steps": args.reset_every}
+        return elapsed, host_ms, summary, since_reset
+
+    ms0 = torch.cuda.memory_stats(dev)
+    elapsed, host_ms, repeats_summary, since_reset = timed_region(args.repeats, untimed)
     ms1 = torch.cuda.memory_stats(dev)
-    counted = [k for k in range(len(repeats)) if sustained and starts[k] >= args.settle_seconds] or list(range(len(repeats)))
-    order = sorted(counted, key=lambda k: repeats[k][0])
-    elapsed, host_ms = repeats[order[(len(order) - 1) // 2]]      # the median repeat (the lower one of an even count) among the counted ones
+    final_loss = float(ddist.allreduce_sum_(loss.detach().clone().reshape(1).double()).item())     # (summed over the ranks: the loss of all views)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the loss, the parameter it updated in place, the gradient it applied (identical on every rank)
+        dump_outputs(args.dump_outputs, {"loss": np.array([final_loss]), "parameter": parameter.detach().cpu().numpy(),
+                                         "grad": parameter.grad.detach().cpu().numpy()})
     # the host's own pace (enqueue only): a step whose enqueue takes as long as the step itself means the host, not the GPU, set the time
     # device-level allocator traffic inside the timed region (a hipMalloc / hipFree there would be a host-side stall of milliseconds)
     alloc_stats = {k: int(ms1.get(k, 0) - ms0.get(k, 0)) for k in ("num_device_alloc", "num_device_free", "num_alloc_retries")}
@@ -625,23 +702,19 @@ def main():
         "metric": "M camera-rays/s (forward+backward) on 50k-tri mesh, 72 views",
         "value": round(value, 3), "unit": "M camera-rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "strong",
-        "repeats": {"n": len(repeats), "reported": f"median of the {len(counted)} repeats that started after {args.settle_seconds} s of timed steps" if sustained and len(counted) < len(repeats) else "median",
-                    "ms_per_step": [round(1e3 * t / args.steps, 3) for t, _ in repeats],
-                    "min": round(1e3 * min(repeats[k][0] for k in counted) / args.steps, 3), "median": round(1e3 * elapsed / args.steps, 3),
-                    "max": round(1e3 * max(repeats[k][0] for k in counted) / args.steps, 3), "timed_region_ms_total": round(1e3 * sum(t for t, _ in repeats), 1),
-                    "first_repeat": round(1e3 * repeats[0][0] / args.steps, 3), "sustained": sustained, "n_counted": len(counted),
-                    # the plateau, visibly: median ms/step of the repeats that started within each successive half second of timed steps
-                    "by_half_second": [round(1e3 * sorted(repeats[k][0] for k in ks)[(len(ks) - 1) // 2] / args.steps, 3)
-                                       for ks in ([k for k in range(len(repeats)) if int(starts[k] / 0.5) == b] for b in range(int(timed_total / 0.5) + 1)) if ks],
-                    "parameter_resets": n_resets, "reset_every_steps": args.reset_every},
+        "repeats": repeats_summary,
         "vs_baseline": None, "dtype": "f32 traversal + f64 shading/gradients", "data": "synthetic",
         "config": {"workload": f"{mesh_src} = {n_faces} tris / {n_verts} verts, {args.views} turntable views, "
                                f"{res}x{res} rays/view, LBVH rebuilt every step, forward+ray_loss+backward+all-reduce+SGD"
                                + ("" if args.distance_factor == 2.5 else f", cameras at {args.distance_factor} extents")
                                + (", no grid verdict cache" if args.no_grid_cache else ""),
-                   "targets": "random" if args.random_targets else target_src, "mode": args.mode, "hip_graph": bool(args.graph), "outputs_recycled": bool(args.mode == "dropin" and (args.bind or (Render.RECYCLE_OUTPUTS and P * len(my_views) >= Render.RECYCLE_MIN_RAYS and (not args.graph or Render.cache_report().get("recycle_graph_set", 0) > 0)))), "ray_binding": bool(args.bind), "views_per_gpu": len(my_views), "views_per_call": min(bv, len(my_views)), "ior": IOR, "valid_pixel_fraction": round(valid_frac, 4), "untimed_steps": max(args.warmup, 3), "allocator_in_timed_region": alloc_stats,
-                   "final_loss": float(ddist.allreduce_sum_(loss.detach().clone().reshape(1).double()).item())},     # (summed over the ranks: the loss of all views)
+                   "targets": "random" if args.random_targets else target_src, "mode": args.mode, "hip_graph": bool(args.graph), "outputs_recycled": bool(args.mode == "dropin" and (args.bind or (Render.RECYCLE_OUTPUTS and P * len(my_views) >= Render.RECYCLE_MIN_RAYS and (not args.graph or Render.cache_report().get("recycle_graph_set", 0) > 0)))), "ray_binding": bool(args.bind), "views_per_gpu": len(my_views), "views_per_call": min(bv, len(my_views)), "ior": IOR, "valid_pixel_fraction": round(valid_frac, 4), "untimed_steps": untimed, "allocator_in_timed_region": alloc_stats,
+                   "final_loss": final_loss},
     }
+    if args.full and not args.no_extras and args.repeats > 0:
+        # the sustained measurement (--repeats 0) after the headline: >= --min-seconds of timed steps, the median of the repeats after the clocks settled
+        s_elapsed, _, s_summary, since_reset = timed_region(0, since_reset)
+        out["sustained"] = {"value": round(total_rays / s_elapsed / 1e6, 3), "ms_per_step": round(1e3 * s_elapsed / args.steps, 3), "repeats": s_summary}
     # N > 1: what the line says about the exchange itself, so that the first run on a multi-GPU node explains itself -- the process group as
     # torch.distributed sees it, and the step's one all-reduce (grad[V,3] float64) timed alone on every rank, after the timed region
     if world > 1 or os.environ.get("DRT_DIST_FORCE", "") not in ("", "0"):
@@ -676,10 +749,12 @@ def main():
             "note": "the all-reduce figure is the collective alone (20 back-to-back calls after the timed region); inside the step it is one launch in the chain",
         }
     prof_live = scene.optix_mesh.profile_read() if live_profile else None
-    scene.optix_mesh.profile_select(None)
-    # the two modes at ONE parameter state (no optimiser step in between): same loss to rounding, or one of them is wrong
+    if live_profile:
+        scene.optix_mesh.profile_select(None)
+    # everything below is --full only.  The two modes at ONE parameter state (no optimiser step in between): same loss to rounding, or one
+    # of them is wrong
     loss_check = None
-    if not args.graph:
+    if args.full and not args.graph:
         scene.optix_mesh.profile_enable(0)
         opt.zero_grad(set_to_none=True)
         l_drop = float(O.local_loss_backward(scene, local_views, init_vertices, parameter, w_ray, fused=False).item())
@@ -698,7 +773,7 @@ def main():
             scene.optix_mesh.profile_enable(True)
             scene.optix_mesh.profile_read()
     fused_extra = None
-    if args.mode == "dropin" and not args.graph and not args.no_extras:   # (N = 1 and N > 1 alike)
+    if args.full and args.mode == "dropin" and not args.graph and not args.no_extras:   # (N = 1 and N > 1 alike)
         # same K steps through the one-pass API (Scene.ray_loss_fused: no dense out_ori/out_dir/mask, rays of
         # pixels without a target dropped before tracing) -- reported next to the headline, never as `value`
         def fused_step():
@@ -716,7 +791,7 @@ def main():
         scene.optix_mesh.profile_enable(1)
         scene.optix_mesh.profile_read()
     establish_extra = tight_extra = None
-    if args.mode == "dropin" and not args.graph and not args.no_extras:
+    if args.full and args.mode == "dropin" and not args.graph and not args.no_extras:
         # (a) the same steps WITHOUT the verdict cache: every call fits the image models and verifies every single ray again, as a caller
         #     does whose capture layer hands out fresh ray tensors per call (the reference's Data.get_view, captured_data.py:44-59)
         scene.optix_mesh.profile_enable(0)
@@ -785,7 +860,7 @@ def main():
         scene.optix_mesh.profile_enable(1)
         scene.optix_mesh.profile_read()
     route_b = None
-    if rank == 0 and world == 1 and not args.no_extras and args.mode == "dropin":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.mode == "dropin":
         # INTEGRATION.md route B: the reference's own DiffRender structure -- Dintersect / refract_ray / trace2 as float64
         # torch ops with autograd, the occlusion query, boolean-mask compaction between the steps -- on top of the HIP tracer
         # class only (drt_intersect behind optix_mesh.intersect), one view per call like the reference's loop.
@@ -821,17 +896,19 @@ def main():
     # every stage's event pairs: the same K steps repeated eagerly right after the timed region (same kernels, same inputs, same
     # launch streams).  N = 1: the traversal kernels' rows are then replaced by the ones recorded live INSIDE the timed region;
     # N > 1 and graph replay (no events inside a replayed graph): all rows come from this repeat.
-    scene.optix_mesh.profile_enable(1)
-    scene.optix_mesh.profile_read()
-    for _ in range(args.steps):
-        step(True)
-    prof = scene.optix_mesh.profile_read()
-    if prof_live:
-        prof.update({k: prof_live[k] for k in LIVE if prof_live[k][1] > 0})
+    prof = None
+    if args.full:
+        scene.optix_mesh.profile_enable(1)
+        scene.optix_mesh.profile_read()
+        for _ in range(args.steps):
+            step(True)
+        prof = scene.optix_mesh.profile_read()
+        if prof_live:
+            prof.update({k: prof_live[k] for k in LIVE if prof_live[k][1] > 0})
     # one extra, untimed step (on every rank: it contains the all-reduce) with the traversal statistics
     # switched on -- they cost contended atomics, so they are kept out of the timed region
     tstats, prof2 = {}, None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         scene.optix_mesh.profile_enable(2)
         step(False)
         prof2 = scene.optix_mesh.profile_read()
@@ -840,7 +917,7 @@ def main():
     # timed ALONE.  In the timed region the HBM-bound k_cull of one sub-batch overlaps the latency-bound k_trace of the
     # other, which makes the step faster and each of the two kernels look slower.
     prof_iso = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # (the next call's out_ori / mask are zeroed beside THIS call's loss + backward kernel by default, diffrender.PREFILL_NEXT: off
         # here, so that the fills and that kernel are each timed with the GPU to themselves like every other stage)
         prefill, Render.PREFILL_NEXT = Render.PREFILL_NEXT, False
@@ -851,8 +928,9 @@ def main():
             step(False)
         prof_iso = scene.optix_mesh.profile_read()
         Render.PREFILL_NEXT = prefill
-    scene.optix_mesh.profile_enable(0)
-    if rank == 0:
+    if args.full:
+        scene.optix_mesh.profile_enable(0)
+    if rank == 0 and args.full:
         wave_steps = {k: {"inner": ws - lf, "leaf": lf, "launches": max(1, prof2[k][1])} for k, (ws, ls, lf, mx) in tstats.items() if ws} if prof2 else None
         out["roofline"] = roofline(prof, args, P, len(my_views), n_verts, n_faces, elapsed, world, prof_iso, LIVE if prof_live else None, wave_steps,
                                    recycled=args.mode == "dropin" and not args.graph and (bool(args.bind) or (Render.RECYCLE_OUTPUTS and P * len(my_views) >= Render.RECYCLE_MIN_RAYS)))
@@ -878,7 +956,6 @@ def main():
             out["route_b"] = route_b
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(mesh, center, extent)
-        line = json.dumps(out)
     # RCCL writes its version banner through C stdio, which sits in libc's buffer until exit when stdout is a pipe: every rank
     # flushes it now and rank 0 prints after a barrier, so that the JSON line is the LAST line of the job's stdout
     import ctypes
@@ -886,7 +963,7 @@ def main():
     sys.stdout.flush()
     ddist.barrier()
     if rank == 0:
-        print(line, flush=True)
+        print(json.dumps(out), flush=True)
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 

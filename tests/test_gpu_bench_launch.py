@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -100,3 +101,38 @@ def test_eight_ranks_of_nine_views_the_drivers_8_gpu_line_on_one_gpu():
     a, b = one["config"]["final_loss"], eight["config"]["final_loss"]
     assert a > 0 and abs(a - b) <= 1e-12 * abs(a), (a, b)
     assert eight["value"] > 0 and eight["config"]["workload"] == one["config"]["workload"]
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_reproducible_outputs(tmp_path):
+    """A plain `bench.py` times ONE region of exactly --steps steps and carries no --full extras; --dump-outputs writes what the last
+    timed step returned (loss of all views, parameter after the update, the gradient it applied) as float64 .npy, and two runs with the
+    same arguments start from the same inputs: in the deterministic accumulation mode (no float atomics in the sums), the same bits.
+    --reset-every 4 puts parameter and momentum back inside the timed region (3 untimed steps -- the minimum -- and 1 timed one, reset, 2 more)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "DRT_BENCH_REPEATS")}
+    env["DRT_DETERMINISTIC"] = "1"
+    args = ["--steps", "3", "--warmup", "2", "--res", "256", "--views", "8", "--reset-every", "4"]
+    runs = [_run([sys.executable, "bench.py", "--gpus", "1"] + args + ["--dump-outputs", str(tmp_path / d)], env) for d in ("a", "b")]
+    for line in runs:
+        assert line["steps"] == 3 and line["repeats"]["n"] == 1 and len(line["repeats"]["ms_per_step"]) == 1
+        assert line["repeats"]["parameter_resets"] == 1
+        assert line["ms_per_step"] == line["repeats"]["ms_per_step"][0] > 0 and line["value"] > 0
+        assert not {"roofline", "cpu_baseline", "sustained", "fused_mode", "tight_framing", "establish_mode", "route_b", "paths"} & set(line)
+        assert "loss_check" not in line["config"]
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "parameter", "grad")}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in ("loss", "parameter", "grad")}
+    assert all(v.dtype == np.float64 for v in a.values()) and a["parameter"].shape == a["grad"].shape == (25126, 3)
+    assert a["loss"].tolist() == [runs[0]["config"]["final_loss"]] and a["loss"][0] > 0
+    assert np.abs(a["parameter"]).max() > 0 and np.abs(a["grad"]).max() > 0
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+
+
+def test_full_run_keeps_its_extras():
+    """`--full` (small images, no CPU baseline): the sustained measurement after the headline, the roofline, the regimes, the loss check."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "DRT_BENCH_REPEATS")}
+    line = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--res", "256", "--views", "8", "--full",
+                 "--no-cpu-baseline", "--min-seconds", "0.5", "--settle-seconds", "0.1"], env)
+    assert line["steps"] == 3 and line["repeats"]["n"] == 1
+    assert line["sustained"]["repeats"]["sustained"] is True and line["sustained"]["repeats"]["n"] >= 5 and line["sustained"]["ms_per_step"] > 0
+    assert {"roofline", "paths", "fused_mode", "establish_mode", "tight_framing", "route_b"} <= set(line) and "cpu_baseline" not in line
+    assert line["config"]["loss_check"]["rel_diff"] <= 1e-10

@@ -64,6 +64,24 @@ def test_pmc_counters_are_only_used_with_the_kernel_sources_they_were_collected_
     assert bench._pmc("dropin", rec["workload"])[1]["stale"] is True
 
 
+def test_bench_dump_outputs_are_float64_and_a_fixed_sample_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float64; a set above the limit is cut to the same seeded rows every time."""
+    bench = _load_bench()
+    x = np.arange(10000 * 3, dtype=np.float32).reshape(10000, 3)      # 240 000 bytes as float64
+    small = {"loss": np.array([1.5]), "x": x}
+    bench.dump_outputs(str(tmp_path / "all"), small)
+    assert np.load(tmp_path / "all" / "loss.npy").dtype == np.float64 and np.array_equal(np.load(tmp_path / "all" / "x.npy"), x)
+    limit = (1 << 16) + 100000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), small, limit=limit)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= limit
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float64 and 0 < len(a) < len(x) and np.array_equal(a, b)
+    rows = a[:, 0].astype(np.int64) // 3
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, x[rows])      # whole rows of the output, in order
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.5]
+
+
 def test_make_pmc_json_stamps_the_sources(tmp_path):
     src = tmp_path / "run"
     src.mkdir()
