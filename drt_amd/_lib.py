@@ -66,6 +66,9 @@ SIGNATURES = {
     "drt_subdivide_midpoint": (_c.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _c.c_int, _P, _P, _P]),
     "drt_limit_sgd_step": (_c.c_int, [_P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _D, _P]),
     "drt_limit_sgd_step3": (_c.c_int, [_P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _D, _P, _P, _P, _P, _P]),
+    "drt_weight_terms3": (_c.c_int, [_P, _P, _I64, _P, _P]),
+    "drt_limit_sgd_step_total": (_c.c_int, [_P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _D, _P, _P, _P, _P]),
+    "drt_fx_limbs_limit_sgd_step3": (_c.c_int, [_P, _I64, _P, _P, _P, _D, _D, _c.c_int, _c.c_int, _D, _P, _P, _P, _P]),
     "drt_internal_stream": (_c.c_int, [_P, _c.c_int, _c.POINTER(_P)]),
     "drt_closest_point": (_c.c_int, [_P, _P, _I64, _P, _P, _P, _P]),
     "drt_vh_loss_fused": (_c.c_int, [_P, _P, _P, _P, _I64, _c.c_int, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),

@@ -84,11 +84,17 @@ class Data:
     def _shuffle(self, index):
         (np.random if self.rng is None else self.rng).shuffle(index)
 
+    def ray_view_ids(self):
+        """The sorted view ids the refraction schedule draws from (drt_amd.dist.owner: a view's rank is its position here)."""
+        return ray_view_ids(self.n_total, self.num_view, self.name)
+
+    def silh_view_ids(self):
+        """The sorted view ids the silhouette schedule draws from."""
+        return silh_view_ids(self.n_total)
+
     def ray_view_generator(self):
         n = self.n_total
-        index = list(np.arange(0, n, n // self.num_view))
-        if self.name == "mouse":                                  # the reference's hand-picked subset (captured_data.py:66-69)
-            index = list(np.arange(-5, 10)) + list(np.arange(22, 40))
+        index = _ray_index(n, self.num_view, self.name)
         while True:
             self._shuffle(index)
             for i in index:
@@ -101,6 +107,22 @@ class Data:
             self._shuffle(index)
             for i in index:
                 yield int(i % n)
+
+
+def _ray_index(n_total, num_view, name):
+    """The refraction schedule's index list in the order ray_view_generator shuffles it (entries taken modulo n_total)."""
+    if name == "mouse":                                          # the reference's hand-picked subset (captured_data.py:66-69)
+        return list(np.arange(-5, 10)) + list(np.arange(22, 40))
+    return list(np.arange(0, n_total, n_total // num_view))
+
+
+def ray_view_ids(n_total, num_view, name=""):
+    """Sorted view ids of the refraction schedule of a capture of ``n_total`` views (Data.ray_view_ids without a Data object)."""
+    return sorted({int(i % n_total) for i in _ray_index(n_total, num_view, name)})
+
+
+def silh_view_ids(n_total):
+    return list(range(n_total))
 
 
 def _open_capture(path):

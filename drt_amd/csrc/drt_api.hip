@@ -51,9 +51,8 @@ __global__ void __launch_bounds__(256) k_fx_add(FxCell* __restrict__ dst, const 
         dst[i] = FxCell{r.hi, r.lo, a.flags | b.flags};
     }
 }
-// The exchange format of an all-reduce(SUM) over int64: a cell as four words whose plain per-word sums over up to 2^20 ranks cannot
-// overflow -- three limbs of 43 bits (the top one signed) and the three flags as counters in 20-bit digits.  value = l0 + l1 2^43 + l2 2^86.
-constexpr int kLimbBits = 43;
+// The exchange format of an all-reduce(SUM) over int64 (drt_fixed.h fx_from_limbs reads it back).
+constexpr int kLimbBits = kFxLimbBits;
 __global__ void __launch_bounds__(256) k_fx_to_limbs(const FxCell* __restrict__ cells, int64_t n, int64_t* __restrict__ limbs) {
     constexpr uint64_t kMask = (1ull << kLimbBits) - 1ull;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -67,17 +66,9 @@ __global__ void __launch_bounds__(256) k_fx_to_limbs(const FxCell* __restrict__ 
 }
 __global__ void __launch_bounds__(256) k_fx_from_limbs(const int64_t* __restrict__ limbs, int64_t n, FxCell* __restrict__ cells) {
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        // (each limb is a signed 64-bit number now: sign-extend it to 128 bits, shift it into place, add)
-        auto wide = [](int64_t v, int shift) {
-            Fx128 r{v < 0 ? -1 : 0, (uint64_t)v};
-            if (shift >= 64) { r.hi = (int64_t)((uint64_t)v << (shift - 64)); r.lo = 0; }
-            else if (shift > 0) { r.hi = (int64_t)(((uint64_t)r.hi << shift) | ((uint64_t)v >> (64 - shift))); r.lo = (uint64_t)v << shift; }
-            return r;
-        };
-        const Fx128 r = fx_add(fx_add(wide(limbs[4 * i], 0), wide(limbs[4 * i + 1], kLimbBits)), wide(limbs[4 * i + 2], 2 * kLimbBits));
-        const uint64_t f = (uint64_t)limbs[4 * i + 3];
-        const uint64_t flags = ((f & 0xFFFFFull) ? kFxNaN : 0u) | (((f >> 20) & 0xFFFFFull) ? kFxPosInf : 0u) | (((f >> 40) & 0xFFFFFull) ? kFxNegInf : 0u);
-        cells[i] = FxCell{r.hi, r.lo, flags};
+        uint32_t flags;
+        const Fx128 r = fx_from_limbs(limbs + 4 * i, flags);
+        cells[i] = FxCell{r.hi, r.lo, (uint64_t)flags};
     }
 }
 

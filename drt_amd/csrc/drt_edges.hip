@@ -240,27 +240,74 @@ __global__ void __launch_bounds__(kTraceBlock) k_vh_fused(TraceCtx c, const doub
 // primary_edge_sample.backward multiplies it in (DiffRender.py:263-267) -- the gradient of that term carries float32(w_vh), the loss itself
 // the float64 weight.  Found by the 60-iteration replay of the reference's loop (tests/golden/hand_trajectory.npz): with the float64 weight
 // the parameters left the reference's by 3e-11 mm per iteration, with this they stay within 1e-14.
+// (the weighted gradient of one element and the weighted loss: shared by every kernel below, so that all of them give the same bits)
+__device__ __forceinline__ double weighted_grad3(const double* __restrict__ w, double t0, double t1, double t2) {
+    return (w[0] * t0 + (double)(float)w[1] * t1) + w[2] * t2;
+}
+__device__ __forceinline__ double weighted_loss3(const double* __restrict__ w, double l0, double l1, double l2) {
+    return (w[0] * l0 + w[1] * l1) + w[2] * l2;
+}
+// limit_hook + SGD of element i for the gradient g; `store` writes the (sanitised) gradient back to grad[i]
+__device__ __forceinline__ void limit_sgd_one(double* __restrict__ param, double* __restrict__ grad, double* __restrict__ buf, int64_t i, double g,
+                                              double lr, double momentum, int nesterov, int first, double max_abs, bool store) {
+    if (max_abs > 0.0) {
+        g = g != g ? 0.0 : g;
+        g = g > max_abs ? max_abs : (g < -max_abs ? -max_abs : g);
+        grad[i] = g;
+    } else if (store) {
+        grad[i] = g;
+    }
+    double step = g;
+    if (momentum != 0.0) {
+        const double b = first ? g : buf[i] * momentum + g;
+        buf[i] = b;
+        step = nesterov ? g + momentum * b : b;
+    }
+    param[i] = param[i] + (-lr) * step;
+}
+
 __global__ void __launch_bounds__(256) k_limit_sgd(double* __restrict__ param, double* __restrict__ grad, double* __restrict__ buf, int64_t n,
                                                    double lr, double momentum, int nesterov, int first, double max_abs,
                                                    const double* __restrict__ terms, const double* __restrict__ w, const double* __restrict__ loss_parts,
                                                    double* __restrict__ loss_total) {
-    if (loss_total && blockIdx.x == 0 && threadIdx.x == 0) *loss_total = (w[0] * loss_parts[0] + w[1] * loss_parts[1]) + w[2] * loss_parts[2];
+    if (loss_total && blockIdx.x == 0 && threadIdx.x == 0) *loss_total = weighted_loss3(w, loss_parts[0], loss_parts[1], loss_parts[2]);
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        double g = terms ? (w[0] * terms[i] + (double)(float)w[1] * terms[n + i]) + w[2] * terms[2 * n + i] : grad[i];
-        if (max_abs > 0.0) {
-            g = g != g ? 0.0 : g;
-            g = g > max_abs ? max_abs : (g < -max_abs ? -max_abs : g);
-            grad[i] = g;
-        } else if (terms) {
-            grad[i] = g;
-        }
-        double step = g;
-        if (momentum != 0.0) {
-            const double b = first ? g : buf[i] * momentum + g;
-            buf[i] = b;
-            step = nesterov ? g + momentum * b : b;
-        }
-        param[i] = param[i] + (-lr) * step;
+        const double g = terms ? weighted_grad3(w, terms[i], terms[n + i], terms[2 * n + i]) : grad[i];
+        limit_sgd_one(param, grad, buf, i, g, lr, momentum, nesterov, first, max_abs, terms != nullptr);
+    }
+}
+
+// A rank's share of a multi-rank iteration in float64 (optim.ShardedIteration): out[i] = the weighted sum of the three terms' partial
+// gradients, the same expression k_limit_sgd forms, so that after the all-reduce (a sum over ranks) drt_limit_sgd_step_total applies what
+// drt_limit_sgd_step3 applies -- with one rank, the same bits.
+__global__ void __launch_bounds__(256) k_weight_terms3(const double* __restrict__ terms, const double* __restrict__ w, int64_t n, double* __restrict__ out) {
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        out[i] = weighted_grad3(w, terms[i], terms[n + i], terms[2 * n + i]);
+}
+
+// The deterministic form of the step's tail after the exchange: `limbs` int64 [3 n + 3, 4] = the rank-summed exchange words of the three
+// terms' gradient cells (term k, element i at cell k n + i) and of the three loss cells (3 n + k).  One pass does what drt_fx_from_limbs ->
+// drt_fx_finalize -> drt_limit_sgd_step3 do in three: the 128-bit sums rounded once (fx_to_double, flags and all), the weighted sum, the
+// limit, the SGD step, and the float64 loss parts and their weighted total.
+__global__ void __launch_bounds__(256) k_fx_limbs_limit_sgd(const int64_t* __restrict__ limbs, int64_t n, double* __restrict__ param,
+                                                            double* __restrict__ grad, double* __restrict__ buf, double lr, double momentum,
+                                                            int nesterov, int first, double max_abs, const double* __restrict__ w,
+                                                            double* __restrict__ loss_parts, double* __restrict__ loss_total) {
+    auto value = [&](int64_t cell) {
+        uint32_t flags;
+        const Fx128 v = fx_from_limbs(limbs + 4 * cell, flags);
+        return fx_to_double(v, flags);
+    };
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double l0 = value(3 * n), l1 = value(3 * n + 1), l2 = value(3 * n + 2);
+        loss_parts[0] = l0;
+        loss_parts[1] = l1;
+        loss_parts[2] = l2;
+        *loss_total = weighted_loss3(w, l0, l1, l2);
+    }
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double g = weighted_grad3(w, value(i), value(n + i), value(2 * n + i));
+        limit_sgd_one(param, grad, buf, i, g, lr, momentum, nesterov, first, max_abs, true);
     }
 }
 
@@ -433,6 +480,37 @@ int drt_limit_sgd_step3(double* d_param, double* d_grad, double* d_buf, int64_t 
     if (!d_param || !d_grad || (momentum != 0.0 && !d_buf) || !d_terms || !d_w3 || ((d_loss_parts == nullptr) != (d_loss_total == nullptr)))
         return fail(DRT_E_INVALID, "null pointer argument");
     k_limit_sgd<<<grid_for(n, 256, 1024), 256, 0, (hipStream_t)stream>>>(d_param, d_grad, d_buf, n, lr, momentum, nesterov, first, max_abs, d_terms, d_w3, d_loss_parts, d_loss_total);
+    HIP_TRY(hipGetLastError());
+    return DRT_OK;
+}
+
+int drt_weight_terms3(const double* d_terms, const double* d_w3, int64_t n, double* d_out, void* stream) {
+    if (n < 0) return fail(DRT_E_INVALID, "negative size");
+    if (n == 0) return DRT_OK;
+    if (!d_terms || !d_w3 || !d_out) return fail(DRT_E_INVALID, "null pointer argument");
+    k_weight_terms3<<<grid_for(n, 256, 1024), 256, 0, (hipStream_t)stream>>>(d_terms, d_w3, n, d_out);
+    HIP_TRY(hipGetLastError());
+    return DRT_OK;
+}
+
+int drt_limit_sgd_step_total(double* d_param, double* d_grad, double* d_buf, int64_t n, double lr, double momentum, int nesterov, int first,
+                             double max_abs, const double* d_w3, const double* d_loss_parts, double* d_loss_total, void* stream) {
+    if (n < 0) return fail(DRT_E_INVALID, "negative size");
+    if (n == 0) return DRT_OK;
+    if (!d_param || !d_grad || (momentum != 0.0 && !d_buf) || !d_w3 || !d_loss_parts || !d_loss_total) return fail(DRT_E_INVALID, "null pointer argument");
+    k_limit_sgd<<<grid_for(n, 256, 1024), 256, 0, (hipStream_t)stream>>>(d_param, d_grad, d_buf, n, lr, momentum, nesterov, first, max_abs, nullptr, d_w3, d_loss_parts, d_loss_total);
+    HIP_TRY(hipGetLastError());
+    return DRT_OK;
+}
+
+int drt_fx_limbs_limit_sgd_step3(const int64_t* d_limbs, int64_t n, double* d_param, double* d_grad, double* d_buf, double lr, double momentum,
+                                 int nesterov, int first, double max_abs, const double* d_w3, double* d_loss_parts, double* d_loss_total, void* stream) {
+    if (n < 0) return fail(DRT_E_INVALID, "negative size");
+    if (n == 0) return DRT_OK;
+    if (!d_limbs || !d_param || !d_grad || (momentum != 0.0 && !d_buf) || !d_w3 || !d_loss_parts || !d_loss_total)
+        return fail(DRT_E_INVALID, "null pointer argument");
+    k_fx_limbs_limit_sgd<<<grid_for(n, 256, 1024), 256, 0, (hipStream_t)stream>>>(d_limbs, n, d_param, d_grad, d_buf, lr, momentum, nesterov, first, max_abs,
+                                                                                    d_w3, d_loss_parts, d_loss_total);
     HIP_TRY(hipGetLastError());
     return DRT_OK;
 }

@@ -102,6 +102,23 @@ DRT_HD double fx_to_double(Fx128 a, uint32_t flags) {
     return neg ? -d : d;
 }
 
+// The exchange format of an all-reduce(SUM) over int64 (drt_fx_to_limbs): a cell as four words whose plain per-word sums over up to 2^20
+// ranks cannot overflow -- three limbs of 43 bits (the top one signed) and the three flags as counters in 20-bit digits.
+// value = l0 + l1 2^43 + l2 2^86.  fx_from_limbs reads the four (summed) words of one cell back: the 128-bit sum, and the sticky flags.
+constexpr int kFxLimbBits = 43;
+DRT_HD Fx128 fx_from_limbs(const int64_t* l, uint32_t& flags) {
+    // (each limb is a signed 64-bit number now: sign-extend it to 128 bits, shift it into place, add)
+    auto wide = [](int64_t v, int shift) {
+        Fx128 r{v < 0 ? -1 : 0, (uint64_t)v};
+        if (shift >= 64) { r.hi = (int64_t)((uint64_t)v << (shift - 64)); r.lo = 0; }
+        else if (shift > 0) { r.hi = (int64_t)(((uint64_t)r.hi << shift) | ((uint64_t)v >> (64 - shift))); r.lo = (uint64_t)v << shift; }
+        return r;
+    };
+    const uint64_t f = (uint64_t)l[3];
+    flags = ((f & 0xFFFFFull) ? kFxNaN : 0u) | (((f >> 20) & 0xFFFFFull) ? kFxPosInf : 0u) | (((f >> 40) & 0xFFFFFull) ? kFxNegInf : 0u);
+    return fx_add(fx_add(wide(l[0], 0), wide(l[1], kFxLimbBits)), wide(l[2], 2 * kFxLimbBits));
+}
+
 // A thread's own running sum (loss terms): exact, so the order of the items a thread happens to get does not matter.
 struct FxAcc {
     Fx128 v{0, 0};

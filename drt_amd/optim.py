@@ -11,7 +11,8 @@ Differences from the reference, all outside the per-view math:
   * the MeshLab remesh between passes (optim.py:12-52, an external program) is done in-process by
     drt_amd.remesh (same algorithm and parameters); ``remesh=`` takes any other callable, or None;
   * multi-GPU: ``full_batch_step`` shards views over ranks and all-reduces the vertex gradient
-    once per step (drt_amd.dist); the reference is single-GPU and one view per step.
+    once per step (drt_amd.dist); the reference is single-GPU and one view per step.  ``optimize_sharded`` is the whole
+    loop on N ranks (ShardedIteration: all three terms, one exchange per iteration; the remesh on rank 0, broadcast).
 """
 from __future__ import annotations
 
@@ -304,6 +305,237 @@ class FusedIteration:
             self.first = False
             self._vertices = vertices          # (alive until the next step: kernels enqueued above read it)
         return total, self.losses
+
+
+def sharded_loss_weights(hp, resy, mean_len, views_per_step=1):
+    """The weights of a ShardedIteration: loss_weights with the refraction weight divided by the step's view count (the refraction term
+    is the MEAN over the step's views); ``views_per_step = 1`` gives loss_weights exactly."""
+    w_ray, w_vh, w_sm = loss_weights(hp, resy, mean_len)
+    return (w_ray / views_per_step if views_per_step != 1 else w_ray), w_vh, w_sm
+
+
+class ShardedIteration:
+    """The rank-local form of FusedIteration: one iteration of the pass loop on ``world`` ranks with ONE collective.
+
+    Every rank draws the same schedule -- ``views_per_step`` refraction views, then the reference's 8 silhouette views, from the capture's
+    generators (same seed on every rank) -- and evaluates only the views it owns (drt_amd.dist.owner: a view's position in the schedule's
+    sorted id list, modulo world); the smoothness term is rank 0's.  The rank's contribution goes into one contiguous buffer, all-reduced
+    once: in float64 mode the weighted partial gradient and the three loss parts (n + 3 values; drt_weight_terms3), in deterministic mode
+    the exchange words of the three terms' gradient cells and the three loss cells ((3n + 3) x 4 int64; drt_fx_to_limbs).  After it every
+    rank applies the same weighted sum, limit_hook and SGD(nesterov) (drt_limit_sgd_step_total / drt_fx_limbs_limit_sgd_step3), so the
+    parameters stay bit-identical across ranks without a broadcast.  A rank that owns nothing in an iteration still joins the exchange.
+    With one rank and ``views_per_step = 1`` this is FusedIteration: same schedule, kernels, weights and update (in deterministic mode the
+    same bits).  ``n_allreduce`` counts the collectives issued; ``collective_events`` holds (start, end) CUDA events around each of them
+    until the caller reads them."""
+
+    N_SILHOUETTE_VIEWS = 8
+
+    def __init__(self, scene, data, HyperParams, lr, views_per_step=1, concurrent=True):
+        from . import _lib, det
+        self._lib = _lib
+        self.scene, self.data, self.hp = scene, data, HyperParams
+        self.k = int(views_per_step)
+        if self.k < 1:
+            raise ValueError("views_per_step must be >= 1")
+        self.rank, self.world = ddist.rank_world()
+        self.ray_view = data.ray_view_generator()
+        self.silh_view = data.silh_view_generator()
+        ray_ids, silh_ids = data.ray_view_ids(), data.silh_view_ids()
+        self.own_ray = set(ddist.owned_views(ray_ids, self.rank, self.world))
+        self.own_silh = set(ddist.owned_views(silh_ids, self.rank, self.world))
+        dev = scene.vertices.device
+        self.init_vertices = scene.vertices.detach().clone()
+        self.parameter = torch.zeros_like(self.init_vertices)
+        n = self.n = self.init_vertices.numel()
+        self.det = det.on()
+        if self.det:
+            # one contiguous block of 3n + 3 cells (term k, element i at cell k n + i; loss k at cell 3n + k): ONE drt_fx_to_limbs launch
+            self.cells = torch.zeros((3 * n + 3) * det._CELL_WORDS, dtype=torch.int64, device=dev)
+            self.limbs = torch.empty((3 * n + 3) * 4, dtype=torch.int64, device=dev)
+            self.losses = torch.zeros(3, dtype=Float, device=dev)
+            self.total_grad = torch.empty_like(self.init_vertices)
+        else:
+            self.grads = torch.zeros((3,) + tuple(self.init_vertices.shape), dtype=Float, device=dev)
+            self.xbuf = torch.zeros(n + 3, dtype=Float, device=dev)        # [weighted partial gradient (n), loss parts (3)]: the exchange
+            self.losses = self.xbuf[n:]
+            self.total_grad = self.xbuf[:n].view(self.init_vertices.shape)
+        self.total = torch.zeros((), dtype=Float, device=dev)
+        self.buf = torch.empty_like(self.init_vertices) if HyperParams["momentum"] != 0 else None
+        self.first = True
+        self.lr, self.momentum = float(lr), float(HyperParams["momentum"])
+        self.n_allreduce = 0
+        self.collective_events = []
+        self.side = None
+        if concurrent:          # (the library's idle pipeline stream: a hardware queue of its own, see FusedIteration)
+            import ctypes
+            h = ctypes.c_void_p()
+            rc = _lib.lib().drt_internal_stream(scene.optix_mesh._h, 2, ctypes.byref(h))
+            self.side = torch.cuda.ExternalStream(h.value, device=dev) if rc == 0 and h.value else torch.cuda.Stream(device=dev)
+        self._w = None
+
+    def draw(self):
+        """This iteration's schedule, the same on every rank: (refraction view ids, silhouette view ids)."""
+        hp = self.hp
+        ray = [next(self.ray_view) for _ in range(self.k)] if hp["ray_w"] != 0 else []
+        silh = [next(self.silh_view) for _ in range(self.N_SILHOUETTE_VIEWS)] if hp["vh_w"] != 0 else []
+        return ray, silh
+
+    def step(self):
+        """Runs the iteration; returns (weighted total, parts [ray, vh, sm]) of the WHOLE iteration (all ranks) as device tensors that the
+        next call overwrites."""
+        import ctypes
+        from . import det, diffrender as R
+        from .optix_mesh import _stream
+        lib, check, ptr = self._lib.lib(), self._lib.check, self._lib.ptr
+        scene, hp, data, n = self.scene, self.hp, self.data, self.n
+        dev = self.init_vertices.device
+        ray_ids, silh_ids = self.draw()
+        ray_ids = [v for v in ray_ids if v in self.own_ray]
+        silh_ids = [v for v in silh_ids if v in self.own_silh]
+        self.last_owned = (len(ray_ids), len(silh_ids))       # (this rank's share of the iteration: refraction views, silhouette views)
+        with torch.no_grad(), torch.cuda.device(dev):
+            vertices = self.init_vertices + self.parameter
+            scene.update_verticex(vertices)
+            if self.det:
+                self.cells.zero_()
+                words = det._CELL_WORDS
+                g_ptr = [self.cells[k * n * words:].data_ptr() for k in range(3)]
+                l_ptr = [self.cells[(3 * n + k) * words:].data_ptr() for k in range(3)]
+            else:
+                self.grads.zero_()
+                self.xbuf[n:].zero_()
+                g_ptr = [self.grads[k].data_ptr() for k in range(3)]
+                l_ptr = [self.xbuf[n + k:].data_ptr() for k in range(3)]
+            h = scene.optix_mesh._h
+            main = torch.cuda.current_stream()
+            if self.side is not None:
+                self.side.wait_stream(main)
+            keep = []
+            for v in ray_ids:
+                target, valid, _, origin, ray_dir, _ = data.get_view(v)
+                nr = origin.shape[0]
+                o, d, sp = R._f64c(origin, "origin"), R._f64c(ray_dir, "ray_dir"), R._f64c(target, "screen_pixel")
+                va = R._flag_bytes(valid, "valid", nr)
+                keep += [o, d, sp, va]
+                grid = R._grid_cache(origin, ray_dir, nr, *R._tile_hint(nr)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
+                R._arm_seed(h, grid, nr)
+                check(lib.drt_render_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), nr,
+                                                    float(R.intIOR), float(R.extIOR), l_ptr[0], g_ptr[0], None,
+                                                    *R._tile_hint(nr), grid[0], ptr(grid[1]), _stream()))
+            ctx = torch.cuda.stream(self.side) if self.side is not None else torch.no_grad()
+            with ctx:
+                if hp["sm_w"] != 0 and self.rank == 0:     # one rank only: the sum over ranks is the term itself, not world times it
+                    check(lib.drt_sm_loss_fused(vertices.data_ptr(), scene.E2F.data_ptr(), scene.E2F.shape[0], l_ptr[2], g_ptr[2], _stream()))
+                if silh_ids:
+                    m = len(silh_ids)
+                    cams, orgs, softs = (ctypes.c_void_p * m)(), (ctypes.c_void_p * m)(), (ctypes.c_void_p * m)()
+                    for j, v in enumerate(silh_ids):
+                        _, _, soft_mask, origin, _, camera_M = data.get_view(v)
+                        cam, o3, sm_ = R.pack_camera(camera_M), R._f64c(origin[0], "origin"), R._f64c(soft_mask, "soft_mask")
+                        keep += [cam, o3, sm_]
+                        cams[j], orgs[j], softs[j] = cam.data_ptr(), o3.data_ptr(), sm_.data_ptr()
+                    check(lib.drt_vh_loss_fused(h, vertices.data_ptr(), scene.Edges.data_ptr(), scene.E2F.data_ptr(), scene.E2F.shape[0], m,
+                                                cams, orgs, softs, int(data.resx), int(data.resy), 1, l_ptr[1], g_ptr[1], _stream()))
+            if self.side is not None:
+                main.wait_stream(self.side)
+            w = sharded_loss_weights(hp, data.resy, scene.mean_len, self.k)
+            if self._w is None or self._w[0] != w:
+                self._w = (w, torch.tensor(w, dtype=Float, device=dev))
+            wv = self._w[1]
+            ev = None
+            if ddist.active():
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            if self.det:
+                check(lib.drt_fx_to_limbs(self.cells.data_ptr(), 3 * n + 3, self.limbs.data_ptr(), _stream()))
+                self._exchange(self.limbs, ev)
+                check(lib.drt_fx_limbs_limit_sgd_step3(self.limbs.data_ptr(), n, self.parameter.data_ptr(), self.total_grad.data_ptr(), ptr(self.buf),
+                                                       self.lr, self.momentum, 1, int(self.first), 1.0, wv.data_ptr(), self.losses.data_ptr(),
+                                                       self.total.data_ptr(), _stream()))
+            else:
+                check(lib.drt_weight_terms3(self.grads.data_ptr(), wv.data_ptr(), n, self.xbuf.data_ptr(), _stream()))
+                self._exchange(self.xbuf, ev)
+                check(lib.drt_limit_sgd_step_total(self.parameter.data_ptr(), self.xbuf.data_ptr(), ptr(self.buf), n, self.lr, self.momentum, 1,
+                                                   int(self.first), 1.0, wv.data_ptr(), self.xbuf[n:].data_ptr(), self.total.data_ptr(), _stream()))
+            self.first = False
+            self._vertices, self._keep = vertices, keep      # (alive until the next step: kernels enqueued above read them)
+        return self.total, self.losses
+
+    def _exchange(self, t, ev):
+        """The iteration's one collective (a sum over ranks; nothing to do for a single process)."""
+        if not ddist.active():
+            return
+        ev[0].record()
+        ddist.allreduce_sum_(t)
+        ev[1].record()
+        self.n_allreduce += 1
+        self.collective_events.append(ev)
+
+    def collective_seconds(self):
+        """Seconds spent in the collectives since the last call (synchronises the device)."""
+        if not self.collective_events:
+            return 0.0
+        self.collective_events[-1][1].synchronize()
+        s = sum(a.elapsed_time(b) for a, b in self.collective_events) / 1e3
+        self.collective_events = []
+        return s
+
+
+def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotropic", output=True):
+    """``optimize(..., fused=True)`` on every rank of the default process group (one process without one): the pass / iteration loop with
+    ShardedIteration steps, ONE all-reduce per iteration, and before every pass the remesh on rank 0 with its result broadcast to the
+    others (drt_amd.dist.broadcast_mesh_: the remesher need not give the same mesh in two processes).  ``remesh`` as in optimize (run on
+    rank 0 only).  Returns (scene, history, stats): history = the weighted loss every 100 iterations; stats counts the collectives
+    (``allreduces`` and ``allreduces_per_iteration``, mesh ``broadcasts`` and ``broadcasts_per_pass``) and times the steps
+    (``step_seconds``: the iterations without the remesh, device-synchronised at the end of each pass; ``collective_seconds``: CUDA-event
+    time between the start and the end of the all-reduces)."""
+    rank, world = ddist.rank_world()
+    if remesh == "isotropic":
+        from .remesh_gpu import GpuMeshlabserver
+        remesh = GpuMeshlabserver().remesh
+    elif remesh == "isotropic-host":
+        from .remesh import Meshlabserver
+        remesh = Meshlabserver().remesh
+    say = output and rank == 0
+    Render.intIOR = HyperParams["IOR"]
+    Render.resy, Render.resx = data.resy, data.resx
+    ray_view, silh_view = data.ray_view_generator(), data.silh_view_generator()      # one view schedule across passes
+    stats = {"world": world, "views_per_step": int(views_per_step), "passes": 0, "iterations": 0, "allreduces": 0, "broadcasts": 0,
+             "step_seconds": 0.0, "collective_seconds": 0.0}
+    start_time = time.time()
+    history = []
+    for i_pass in range(HyperParams["Pass"]):
+        if HyperParams["Pass"] > 1:
+            remesh_len = interp_R(HyperParams["start_len"], HyperParams["end_len"], i_pass, HyperParams["Pass"])
+            lr = interp_R(HyperParams["start_lr"], HyperParams["lr_decay"] * HyperParams["start_lr"], i_pass, HyperParams["Pass"])
+        else:
+            remesh_len, lr = HyperParams["start_len"], HyperParams["start_lr"]
+        if say:
+            print(f"remesh_len {remesh_len:g} lr {lr:g}")
+        if remesh is not None:
+            if rank == 0:
+                remesh(scene, remesh_len)
+            stats["broadcasts"] += int(ddist.broadcast_mesh_(scene, src=0))
+        stepper = ShardedIteration(scene, data, HyperParams, lr, views_per_step)
+        stepper.ray_view, stepper.silh_view = ray_view, silh_view
+        torch.cuda.synchronize(scene.vertices.device)
+        t0 = time.perf_counter()
+        for it in range(HyperParams["Iters"]):
+            total, parts = stepper.step()
+            if it % 100 == 0:
+                if say:
+                    print(f"Iteration {it}: {loss_string(tuple(parts))} maxgrad={stepper.total_grad.abs().max():g}")
+                history.append(float(total))
+        torch.cuda.synchronize(scene.vertices.device)
+        stats["step_seconds"] += time.perf_counter() - t0
+        stats["collective_seconds"] += stepper.collective_seconds()
+        stats["allreduces"] += stepper.n_allreduce
+        stats["iterations"] += HyperParams["Iters"]
+        stats["passes"] += 1
+    stats["allreduces_per_iteration"] = stats["allreduces"] / max(1, stats["iterations"])
+    stats["broadcasts_per_pass"] = stats["broadcasts"] / max(1, stats["passes"])
+    if say:
+        print(f"optimize time : {time.time() - start_time}")
+    return scene, history, stats
 
 
 def setup_opt(scene, lr, HyperParams, hook=True, fused=False):

@@ -1,6 +1,7 @@
 """Whole reconstruction, end to end -- the reference's ``python optim.py`` (optim.py:173-229).
 
     python -m drt_amd.reconstruct --name horse [--capture horse.npz] [--res 512] [--passes 20] [--iters 200]
+    python -m torch.distributed.run --nproc-per-node 8 -m drt_amd.reconstruct --name monkey --views 144 --res 1024 --views-per-step all
 
 ``optimize(HyperParams)`` of the reference builds the scene from ``<data>/<name>_vh.ply``, loads the capture,
 runs Pass x Iters iterations with a remesh before every pass and writes ``<result>/<name>_recons.ply``
@@ -8,6 +9,9 @@ runs Pass x Iters iterations with a remesh before every pass and writes ``<resul
 module does the same on the HIP path.  The captures (HDF5) are not distributed with the reference: when
 ``--capture`` is not given, a synthetic capture is traced through the scanned mesh (or, without a scan,
 through a displaced copy of the hull) with the same tuple layout.
+
+``--views-per-step`` (or a launch with more than one rank) runs the multi-rank loop, optim.optimize_sharded: each rank renders and
+evaluates only its own views, one all-reduce per iteration, and rank 0 alone prints, writes the PLY and ``<name>_report.json``.
 """
 from __future__ import annotations
 
@@ -21,7 +25,12 @@ import torch
 from . import captured_data, diffrender as Render, mesh_io, metrics, optim, views
 
 
-def run(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, fused=True, output=True, device=0, n_views=72):
+def run(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, fused=True, output=True, device=0, n_views=72,
+        views_per_step=None):
+    """``views_per_step=None``: the single-process loop (optim.optimize).  An int, or "all" (one epoch of the refraction schedule per
+    iteration), goes through optim.optimize_sharded on every rank of the default process group (one process without one)."""
+    if views_per_step is not None or torch.distributed.is_available() and torch.distributed.is_initialized():
+        return run_sharded(HyperParams, data_path, result_path, capture, res, output, device, n_views, views_per_step or 1)
     name = HyperParams["name"]
     hull_path = os.path.join(data_path, f"{name}_vh.ply")
     scan_path = os.path.join(data_path, f"{name}_scan.ply")
@@ -54,6 +63,67 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
     return scene, report
 
 
+def run_sharded(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, output=True, device=0, n_views=72,
+                views_per_step=1):
+    """The reconstruction on every rank (optim.optimize_sharded): each rank renders only the views it owns of the synthetic capture; rank 0
+    alone prints, measures and writes ``<name>_recons.ply`` and ``<name>_report.json``.  Returns (scene, report) -- the report on rank 0,
+    None elsewhere."""
+    from . import dist as ddist
+    rank, world = ddist.rank_world()
+    name = HyperParams["name"]
+    hull_path = os.path.join(data_path, f"{name}_vh.ply")
+    scan_path = os.path.join(data_path, f"{name}_scan.ply")
+    Render.intIOR = HyperParams["IOR"]
+    scene = Render.Scene(hull_path, device)
+    scan_scene = Render.Scene(scan_path, device) if os.path.exists(scan_path) else None
+    if capture is not None:
+        data = captured_data.get_data(HyperParams, path=capture)
+    else:
+        resx = resy = int(res or 512)
+        Render.resx, Render.resy = resx, resy
+        num_view = min(HyperParams["num_view"], n_views)
+        ray_ids = captured_data.ray_view_ids(n_views, num_view, name)
+        mine = sorted(set(ddist.owned_views(ray_ids, rank, world)) | set(ddist.owned_views(captured_data.silh_view_ids(n_views), rank, world)))
+        gt = scan_scene if scan_scene is not None else Render.Scene(views.displaced_ground_truth(scene.mesh, 0.5, 0), device)
+        center, extent = views.mesh_frame(gt.mesh.vertices)
+        data = captured_data.SyntheticData(gt, center, extent, resx, resy, num_view=num_view, n_total=n_views, name=name, view_ids=mine)
+    k = len(data.ray_view_ids()) if views_per_step == "all" else int(views_per_step)
+    report = {"name": name, "resx": data.resx, "resy": data.resy, "views": data.n_total, "hull_faces": int(scene.faces.shape[0]),
+              "world": world, "views_per_step": k}
+    if scan_scene is not None and rank == 0:
+        report["hull_to_scan"] = metrics.hausdorff(scene, scan_scene)
+    t0 = time.time()
+    scene, history, stats = optim.optimize_sharded(scene, data, HyperParams, views_per_step=k, output=output)
+    torch.cuda.synchronize()
+    report["optimize_seconds"] = time.time() - t0
+    report["iterations"] = stats["iterations"]
+    report["seconds_per_iteration"] = stats["step_seconds"] / max(1, stats["iterations"])
+    report["collectives_per_iteration"] = stats["allreduces_per_iteration"]
+    report["broadcasts_per_pass"] = stats["broadcasts_per_pass"]
+    report["collective_share"] = stats["collective_seconds"] / stats["step_seconds"] if stats["step_seconds"] > 0 else 0.0
+    report["result_faces"] = int(scene.faces.shape[0])
+    if rank != 0:
+        return scene, None
+    if scan_scene is not None:
+        report["result_to_scan"] = metrics.hausdorff(scene, scan_scene)
+    os.makedirs(result_path, exist_ok=True)
+    out = os.path.join(result_path, f"{name}_recons.ply")
+    scene.mesh.export(out)
+    report["result"] = out
+    with open(os.path.join(result_path, f"{name}_report.json"), "w") as f:
+        json.dump(report, f, indent=1)
+    return scene, report
+
+
+def _views_per_step(text):
+    if text == "all":
+        return text
+    k = int(text)
+    if k < 1:
+        raise argparse.ArgumentTypeError("--views-per-step takes a positive integer or 'all'")
+    return k
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--name", default=optim.HyperParams["name"])
@@ -68,12 +138,31 @@ def main(argv=None):
     ap.add_argument("--ior", type=float, default=optim.HyperParams["IOR"])
     ap.add_argument("--dropin", action="store_true", help="use the reference-shaped (unfused) loss terms")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--views-per-step", type=_views_per_step, default=None, metavar="N|all",
+                    help="refraction views per iteration (all: every view of the schedule once) on the multi-rank loop; "
+                         "under torch.distributed.run the default is 1")
     a = ap.parse_args(argv)
     import numpy as np
     np.random.seed(a.seed)
     hp = dict(optim.HyperParams, name=a.name, Pass=a.passes, Iters=a.iters, num_view=a.num_view, IOR=a.ior)
-    _, report = run(hp, a.data_path, a.result_path, a.capture, a.res, fused=not a.dropin, n_views=a.views)
-    print(json.dumps(report))
+    from . import dist as ddist
+    if a.views_per_step is None and ddist.env_world()[2] == 1:
+        _, report = run(hp, a.data_path, a.result_path, a.capture, a.res, fused=not a.dropin, n_views=a.views)
+        print(json.dumps(report))
+        return
+    if a.dropin:
+        raise SystemExit("--dropin has no multi-rank form: the sharded loop runs the one-pass terms")
+    _, local_rank, world = ddist.init()
+    device = local_rank % torch.cuda.device_count()
+    torch.cuda.set_device(device)
+    try:
+        _, report = run_sharded(hp, a.data_path, a.result_path, a.capture, a.res, output=True, device=device, n_views=a.views,
+                                views_per_step=a.views_per_step or 1)
+        if report is not None:
+            print(json.dumps(report))
+    finally:
+        if torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

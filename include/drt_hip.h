@@ -455,6 +455,18 @@ int drt_limit_sgd_step(double* d_param, double* d_grad, double* d_buf, int64_t n
  * optional (both or neither) d_loss_parts float64 [3] -> *d_loss_total = (w0 l0 + w1 l1) + w2 l2. */
 int drt_limit_sgd_step3(double* d_param, double* d_grad, double* d_buf, int64_t n, double lr, double momentum, int nesterov, int first,
                         double max_abs, const double* d_terms, const double* d_w3, const double* d_loss_parts, double* d_loss_total, void* stream);
+/* The step's tail split around ONE all-reduce over ranks (optim.ShardedIteration).  Float64: drt_weight_terms3 writes a rank's weighted
+ * partial gradient d_out [n] = (w0 t0[i] + w1 t1[i]) + w2 t2[i] (the expression of drt_limit_sgd_step3) from d_terms [3, n]; after the sum
+ * over ranks drt_limit_sgd_step_total is drt_limit_sgd_step that also writes *d_loss_total = (w0 l0 + w1 l1) + w2 l2 from d_loss_parts [3].
+ * Deterministic: d_limbs int64 [3n + 3, 4] = the rank-summed exchange words (drt_fx_to_limbs) of 3n + 3 cells -- the three terms' gradient
+ * cells (term k, element i at cell k n + i), then the three loss cells; drt_fx_limbs_limit_sgd_step3 does drt_fx_from_limbs +
+ * drt_fx_finalize + drt_limit_sgd_step3 (nesterov, first, max_abs as there) in one pass, same bits, and writes the float64 loss parts
+ * d_loss_parts [3] and *d_loss_total. */
+int drt_weight_terms3(const double* d_terms, const double* d_w3, int64_t n, double* d_out, void* stream);
+int drt_limit_sgd_step_total(double* d_param, double* d_grad, double* d_buf, int64_t n, double lr, double momentum, int nesterov, int first,
+                             double max_abs, const double* d_w3, const double* d_loss_parts, double* d_loss_total, void* stream);
+int drt_fx_limbs_limit_sgd_step3(const int64_t* d_limbs, int64_t n, double* d_param, double* d_grad, double* d_buf, double lr, double momentum,
+                                 int nesterov, int first, double max_abs, const double* d_w3, double* d_loss_parts, double* d_loss_total, void* stream);
 /* The library's own HIP streams (which = 0: the build stream, idle once the tree is built; 1 .. DRT_STREAMS: the pipeline streams, of which
  * a call below 2^25 rays uses only the first).  A process gets four hardware queues and further streams are multiplexed onto them: a
  * caller that wants side work to run BESIDE a render call -- not behind the barrier with which the caller's own stream waits for it in
