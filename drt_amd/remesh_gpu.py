@@ -43,7 +43,7 @@ SUB_ROUNDS = int(__import__("os").environ.get("DRT_REMESH_SUB_ROUNDS", 3))     #
 ROUND_BATCH = int(__import__("os").environ.get("DRT_REMESH_ROUND_BATCH", 4))  # rounds enqueued between two read-backs of the step's control block: the DEVICE ends a step
                            # (drt_rm_round_end); the rounds of a batch that come after the end are no-ops (every kernel returns at its first instruction)
 TAIL_CUT = int(__import__("os").environ.get("DRT_REMESH_TAIL_CUT", 32))       # a step ends when a round applies less than 1 / TAIL_CUT of what its first round applied
-DEBUG = False
+DEBUG = False              # True: check the sizes the compactions are given (computed from the collapse count) against a count on the device
 
 
 def _check(rc):
@@ -176,6 +176,10 @@ class _Work:
                 break
         self.stats["collapse_rounds"] += ran
         self.stats["collapse_unfinished"] += int(bool(still_live))        # candidates were still being applied when the rounds ran out
+        if DEBUG:
+            alive = int((self.F[:, 0] >= 0).sum())
+            if alive != nf - 2 * done:
+                raise RuntimeError(f"collapse step: {alive} faces alive, {nf} - 2 x {done} collapses expected")
         if done:
             # every collapse killed exactly two faces and one vertex (closed manifold, link condition): the sizes are known, so the compaction
             # needs no read-back
@@ -264,6 +268,8 @@ class _Work:
             return
         used = torch.zeros(self.V.shape[0], dtype=torch.bool, device=self.dev)
         used[self.F.reshape(-1)] = True
+        if DEBUG and int(used.sum()) != self.V.shape[0] - self.n_dead_vertices:
+            raise RuntimeError(f"compact: {int(used.sum())} vertices in use, {self.V.shape[0]} - {self.n_dead_vertices} dead expected")
         remap = torch.cumsum(used.long(), 0) - 1
         keep = torch.nonzero_static(used, size=self.V.shape[0] - self.n_dead_vertices).squeeze(1)      # (the collapses' count: no read-back)
         self.V = self.V[keep].contiguous()
@@ -271,12 +277,32 @@ class _Work:
         self.n_dead_vertices = 0
 
 
+def _require_closed_oriented(F, nv):
+    """ValueError unless F [nf,3] is a closed oriented manifold's face array over nv vertices: indices in range, every directed edge
+    exactly once, its reverse present.  The kernels assume it (next_in_face, valence = number of faces, the lo -> hi slot owns an edge)
+    and the compactions size their outputs by it.  Sorts on the device and reads four flags back; nothing is indexed by F."""
+    if F.dim() != 2 or F.shape[1] != 3 or F.shape[0] == 0:
+        raise ValueError(f"isotropic_remesh_gpu needs a non-empty [F, 3] face array, got {tuple(F.shape)}")
+    a, b = F.reshape(-1), F[:, [1, 2, 0]].reshape(-1)
+    key = torch.sort(a * nv + b).values
+    rev = torch.sort(b * nv + a).values
+    low, high, twice, unpaired = torch.stack([F.min() < 0, F.max() >= nv, (key[1:] == key[:-1]).any(), (key != rev).any()]).tolist()
+    if low or high:
+        raise ValueError(f"isotropic_remesh_gpu: face indices outside [0, {nv})")
+    if twice:
+        raise ValueError("isotropic_remesh_gpu needs a closed oriented manifold: a directed edge appears twice (a flipped face, or an edge of more than two faces)")
+    if unpaired:
+        raise ValueError("isotropic_remesh_gpu needs a closed oriented manifold: a directed edge without its reverse (an open boundary)")
+
+
 def isotropic_remesh_gpu(vertices, faces, target_len, surface=None, iterations=3, max_surf_dist=1.0, flags=ALL, return_stats=False):
     """(vertices float64 [V,3], faces int64 [F,3]) on the device -> the same, re-tessellated to edge lengths around ``target_len``.
     ``surface``: an ``optix_mesh`` holding the INPUT surface (closest-point queries for the projection step and MaxSurfDist); None skips
-    both.  Closed manifold in, closed manifold out."""
+    both.  Closed oriented manifold in (anything else raises ValueError before a kernel runs), closed oriented manifold out."""
     if not vertices.is_cuda:
         raise RuntimeError("isotropic_remesh_gpu needs device tensors (drt_amd.remesh is the host version)")
+    with torch.no_grad(), torch.cuda.device(vertices.device):
+        _require_closed_oriented(faces.to(device=vertices.device, dtype=torch.long), vertices.shape[0])
     w = _Work(vertices.detach().to(torch.float64), faces.to(torch.long), surface, float(max_surf_dist) if (flags & CHECK_DIST) and max_surf_dist > 0 else float("inf"), hint=float(target_len))
     min_len, max_len = 0.8 * target_len, 4.0 / 3.0 * target_len
     stats = {"split": 0, "collapsed": 0, "flipped": 0, "iterations": 0}

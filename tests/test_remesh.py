@@ -121,3 +121,26 @@ def test_remesh_rejects_bad_input(hand):
         remesh.isotropic_remesh(open_mesh, 4.0)
     with pytest.raises(_lib.DrtError):
         remesh.isotropic_remesh(hand, -1.0)
+
+
+def test_device_remesh_input_check(hand):
+    """isotropic_remesh_gpu's entry check (drt_amd.remesh_gpu._require_closed_oriented) on host tensors: the closed oriented input passes,
+    an open one, a flipped face, an edge of four faces and an index out of range raise ValueError."""
+    import torch
+    from drt_amd.remesh_gpu import _require_closed_oriented
+    F = torch.tensor(hand.faces, dtype=torch.long)
+    nv = len(hand.vertices)
+    _require_closed_oriented(F, nv)
+    flipped = F.clone()
+    flipped[7] = flipped[7].flip(0)
+    high = F.clone()
+    high[3, 1] = nv
+    low = F.clone()
+    low[3, 1] = -1
+    tet = torch.tensor([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]])
+    two_tets = torch.cat([tet, torch.tensor([[0, 4, 1], [0, 1, 5], [0, 5, 4], [1, 4, 5]])])
+    _require_closed_oriented(tet, 4)
+    for bad, n in ((F[1:], nv), (F[torch.arange(len(F)) % 500 != 7], nv), (flipped, nv), (high, nv), (low, nv), (two_tets, 6),
+                   (F[:0], nv), (F[:, :2], nv)):
+        with pytest.raises(ValueError):
+            _require_closed_oriented(bad, n)
