@@ -51,6 +51,8 @@ SIGNATURES = {
     "drt_ray_loss_listed_grad_split": (_c.c_int, [_P, _P, _P, _P, _I64, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drt_scale_rows3": (_c.c_int, [_P, _P, _P, _P, _P]),
     "drt_render_backward_ray_loss": (_c.c_int, [_P, _P, _P, _P, _I64, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drt_render_backward_inputs": (_c.c_int, [_P, _P, _P, _P, _I64, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drt_render_backward_ray_loss_inputs": (_c.c_int, [_P, _P, _P, _P, _I64, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drt_render_ray_loss_fused": (_c.c_int, [_P, _P, _P, _P, _P, _P, _I64, _D, _D, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
     "drt_dihedral_forward": (_c.c_int, [_P, _P, _I64, _P, _P]),
     "drt_dihedral_backward": (_c.c_int, [_P, _P, _I64, _P, _P, _P]),

@@ -81,4 +81,36 @@ DRT_HD void path_recompute_backward(const PathCtx& c, d3 o, d3 d, int32_t f1, in
     add(vid1[0], ga); add(vid1[1], gb); add(vid1[2], gc);
 }
 
+// Adjoint of a recomputed path (b1, b2 on the faces vid1, vid2) w.r.t. the vertices -- the same gradients, in the same order, as
+// path_recompute_backward -- AND the camera ray (g_o0, g_d0; set) and the two indices of refraction (g_int, g_ext; set).
+template <typename Add>
+DRT_HD void path_backward_inputs(const PathCtx& c, const Bounce& b1, const Bounce& b2, const int32_t (&vid1)[3], const int32_t (&vid2)[3],
+                                 d3 g_ori, d3 g_dir, Add add, d3& g_o0, d3& g_d0, double& g_int, double& g_ext) {
+    const d3 z{0.0, 0.0, 0.0};
+    d3 ga = z, gb = z, gc = z, g_o, g_d;
+    double g_eta;
+    g_int = 0.0; g_ext = 0.0;
+    bounce_backward_eta(b2, g_ori, g_dir, ga, gb, gc, g_o, g_d, g_eta);
+    eta_to_ior(b2, c.ior_int, c.ior_ext, g_eta, g_int, g_ext);
+    add(vid2[0], ga); add(vid2[1], gb); add(vid2[2], gc);
+    ga = z; gb = z; gc = z;
+    bounce_backward_eta(b1, g_o, g_d, ga, gb, gc, g_o0, g_d0, g_eta);
+    eta_to_ior(b1, c.ior_int, c.ior_ext, g_eta, g_int, g_ext);
+    add(vid1[0], ga); add(vid1[1], gb); add(vid1[2], gc);
+}
+
+// path_recompute_backward that also hands back the camera-ray adjoints and the IOR partials (path_backward_inputs).
+template <typename Add>
+DRT_HD void path_recompute_backward_inputs(const PathCtx& c, d3 o, d3 d, int32_t f1, int32_t f2, d3 g_ori, d3 g_dir, Add add,
+                                           d3& g_o0, d3& g_d0, double& g_int, double& g_ext) {
+    d3 v0, v1, v2;
+    int32_t vid1[3], vid2[3];
+    Bounce b1, b2;
+    load_tri64(c, f1, v0, v1, v2, vid1);
+    bounce_forward(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b1);
+    load_tri64(c, f2, v0, v1, v2, vid2);
+    bounce_forward(b1.new_o, b1.wt, v0, v1, v2, c.ior_ext, c.ior_int, b2);
+    path_backward_inputs(c, b1, b2, vid1, vid2, g_ori, g_dir, add, g_o0, g_d0, g_int, g_ext);
+}
+
 }  // namespace drt

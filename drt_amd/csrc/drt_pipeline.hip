@@ -1047,16 +1047,44 @@ __global__ void __launch_bounds__(kPathBlock) k_collect_valid(const int32_t* __r
 
 // Backward (full waves over the list of valid rays): recompute both bounces from (face1, face2),
 // reverse them, scatter the six vertex gradients.
+// The gradients w.r.t. the inputs of the render call besides the vertices (drt_render_backward_inputs and _ray_loss_inputs), each
+// optional (NULL = not computed): d / d origin and d / d ray_dir float64 [N,3], added to row by row (one writer per row: deterministic
+// by construction), and d / d (ior_int, ior_ext): two float64 -- or, deterministic, two FxCells -- summed with LossAcc.
+struct InputGrads {
+    double* origin;
+    double* dir;
+    double* ior;
+};
 template <bool DET>
+__device__ __forceinline__ double* ior_slot(double* ior, int k) {
+    return DET ? reinterpret_cast<double*>(reinterpret_cast<FxCell*>(ior) + k) : ior + k;
+}
+// What one thread of a path backward adds to InputGrads: the rows at once, the IOR partials at the end of the kernel (whole waves).
+template <bool DET>
+struct InputAcc {
+    LossAcc<DET> g_int, g_ext;
+    __device__ __forceinline__ void add(const InputGrads& in, int64_t i, d3 g_o0, d3 g_d0, double gi, double ge) {
+        if (in.origin) store_d3(in.origin, i, load_d3(in.origin, i) + g_o0);
+        if (in.dir) store_d3(in.dir, i, load_d3(in.dir, i) + g_d0);
+        if (in.ior) { g_int.add(gi); g_ext.add(ge); }
+    }
+    __device__ __forceinline__ void flush(const InputGrads& in) {
+        if (in.ior) { g_int.flush(ior_slot<DET>(in.ior, 0)); g_ext.flush(ior_slot<DET>(in.ior, 1)); }
+    }
+};
+
+// INPUTS: also the gradients w.r.t. the camera rays and the IOR (InputGrads); the vertex scatter is the same either way.
+template <bool DET, bool INPUTS = false>
 __global__ void __launch_bounds__(256) k_render_bwd(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir,
                                                     const int32_t* __restrict__ face1, const int32_t* __restrict__ face2,
                                                     const double* __restrict__ g_out_ori, const double* __restrict__ g_out_dir,
                                                     double* grad_verts, const int32_t* __restrict__ list, const unsigned* __restrict__ n_u32,
-                                                    const int64_t* __restrict__ n_i64) {
+                                                    const int64_t* __restrict__ n_i64, InputGrads in) {
     __shared__ int32_t hkeys[kHashSize];
     __shared__ double hsums[3 * kHashSize];
     const int64_t n = n_i64 ? *n_i64 : (int64_t)*n_u32;
     const PathSink<DET> add{hkeys, hsums, grad_verts};
+    InputAcc<DET> inp;
     for (int64_t base = blockIdx.x * (int64_t)kBwdBatch; base < n; base += (int64_t)gridDim.x * kBwdBatch) {
         add.clear();
         const int64_t end = base + kBwdBatch < n ? base + kBwdBatch : n;
@@ -1065,10 +1093,18 @@ __global__ void __launch_bounds__(256) k_render_bwd(PathCtx c, const double* __r
             const d3 z{0.0, 0.0, 0.0};
             const d3 g_ori = g_out_ori ? load_d3(g_out_ori, i) : z;
             const d3 g_dir = g_out_dir ? load_d3(g_out_dir, i) : z;
-            path_recompute_backward(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], g_ori, g_dir, add);
+            if constexpr (INPUTS) {
+                d3 g_o0, g_d0;
+                double gi, ge;
+                path_recompute_backward_inputs(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], g_ori, g_dir, add, g_o0, g_d0, gi, ge);
+                inp.add(in, i, g_o0, g_d0, gi, ge);
+            } else {
+                path_recompute_backward(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], g_ori, g_dir, add);
+            }
         }
         add.flush();
     }
+    if constexpr (INPUTS) inp.flush(in);
 }
 
 
@@ -1250,16 +1286,18 @@ __global__ void __launch_bounds__(256) k_loss_bwd_fused(PathCtx c, const double*
 // Backward of render_transparent + ray_loss for the rows ray_loss reported as contributing (drt_ray_loss's list):
 // the loss gradient d loss / d out_dir = 2 (out_dir - target) * scale is recomputed from the path (bit-identical to the
 // stored outputs: same code) instead of being read from a dense [N,3] tensor that is zero almost everywhere.
-template <bool DET>
+template <bool DET, bool INPUTS = false>
 __global__ void __launch_bounds__(256) k_render_bwd_rows(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir,
                                                          const double* __restrict__ screen_pixel, const int32_t* __restrict__ face1,
                                                          const int32_t* __restrict__ face2, const int32_t* __restrict__ rows,
-                                                         const unsigned* __restrict__ n_rows, const double* __restrict__ scale, double* grad_verts) {
+                                                         const unsigned* __restrict__ n_rows, const double* __restrict__ scale, double* grad_verts,
+                                                         InputGrads in) {
     __shared__ int32_t hkeys[kHashSize];
     __shared__ double hsums[3 * kHashSize];
     const unsigned n = *n_rows;
     const double sc = *scale;
     const PathSink<DET> add{hkeys, hsums, grad_verts};
+    InputAcc<DET> inp;
     for (unsigned base = blockIdx.x * kBwdBatch; base < n; base += gridDim.x * kBwdBatch) {
         add.clear();
         const unsigned end = base + kBwdBatch < n ? base + kBwdBatch : n;
@@ -1276,6 +1314,13 @@ __global__ void __launch_bounds__(256) k_render_bwd_rows(PathCtx c, const double
             (void)ray_loss_term(b2.new_o, b2.wt, load_d3(screen_pixel, i), g_dir);
             g_dir = sc * g_dir;
             const d3 z{0.0, 0.0, 0.0};
+            if constexpr (INPUTS) {
+                d3 g_o0, g_d0;
+                double gi, ge;
+                path_backward_inputs(c, b1, b2, vid1, vid2, z, g_dir, add, g_o0, g_d0, gi, ge);
+                inp.add(in, i, g_o0, g_d0, gi, ge);
+                continue;
+            }
             d3 ga = z, gb = z, gc = z, g_o, g_d, g_o0, g_d0;
             bounce_backward(b2, z, g_dir, ga, gb, gc, g_o, g_d);
             add(vid2[0], ga); add(vid2[1], gb); add(vid2[2], gc);
@@ -1285,6 +1330,7 @@ __global__ void __launch_bounds__(256) k_render_bwd_rows(PathCtx c, const double
         }
         add.flush();
     }
+    if constexpr (INPUTS) inp.flush(in);
 }
 
 // ray_loss AND its vertex gradient over the forward's list of completed paths, in one pass: what k_ray_loss_listed (loss, row list)
@@ -1848,10 +1894,20 @@ int drt_prefill_wait(drt_scene_t* s, void* stream) {
     return DRT_OK;
 }
 
-int drt_render_backward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
-                        double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
-                        const int32_t* d_valid_idx, const int64_t* d_n_valid,
-                        const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts, void* stream) {
+}  // extern "C"
+
+// The bodies of drt_render_backward / drt_render_backward_ray_loss and their _inputs forms (INPUTS: k_render_bwd<DET, true> and
+// k_render_bwd_rows<DET, true> with the caller's InputGrads; otherwise the plain kernels with an empty one).
+#define DET_LAUNCH_IN(kern, grid, block, st, ...)                                               \
+    do {                                                                                        \
+        if (det_mode()) kern<true, INPUTS><<<grid, block, 0, st>>>(__VA_ARGS__);                \
+        else kern<false, INPUTS><<<grid, block, 0, st>>>(__VA_ARGS__);                          \
+    } while (0)
+template <bool INPUTS>
+static int render_backward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                           double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
+                           const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                           const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts, InputGrads in, void* stream) {
     CHECK_BUILT(s);
     if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
     if (n_rays == 0 || (!d_grad_out_ori && !d_grad_out_dir)) return DRT_OK;
@@ -1861,8 +1917,8 @@ int drt_render_backward(drt_scene_t* s, const double* d_verts, const double* d_o
     const PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
     if (d_valid_idx) {   // the forward's list of completed paths: no pass over the dense arrays at all
         StageTimer t(s, st, kStageBackward);
-        DET_LAUNCH(k_render_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_face1, d_face2, d_grad_out_ori, d_grad_out_dir, d_grad_verts,
-                                                   d_valid_idx, nullptr, d_n_valid);
+        DET_LAUNCH_IN(k_render_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_face1, d_face2, d_grad_out_ori, d_grad_out_dir, d_grad_verts,
+                                                   d_valid_idx, nullptr, d_n_valid, in);
     } else {             // no list saved: compact face2 >= 0 first (on the caller's stream, workspace of sub-stream 0)
         drt_scene::Sub& w = s->sub[0];
         const int64_t chunk = n_rays < s->chunk_rays ? n_rays : s->chunk_rays;
@@ -1874,8 +1930,8 @@ int drt_render_backward(drt_scene_t* s, const double* d_verts, const double* d_o
             { StageTimer t(s, st, kStageCollect);
               k_collect_valid<<<grid_for(n, kPathBlock, 8 * s->n_cu), kPathBlock, 0, st>>>(d_face2 + b, n, b, w.q_idx[0], s->vcount); }
             { StageTimer t(s, st, kStageBackward);
-              DET_LAUNCH(k_render_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_face1, d_face2, d_grad_out_ori, d_grad_out_dir, d_grad_verts,
-                                                         w.q_idx[0], s->vcount, nullptr); }
+              DET_LAUNCH_IN(k_render_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_face1, d_face2, d_grad_out_ori, d_grad_out_dir, d_grad_verts,
+                                                         w.q_idx[0], s->vcount, nullptr, in); }
             if (s->prof_on) k_prof_counts_bwd<<<1, 64, 0, st>>>(s->vcount, (unsigned long long)n, s->prof_counts);
         }
     }
@@ -1884,10 +1940,11 @@ int drt_render_backward(drt_scene_t* s, const double* d_verts, const double* d_o
     return DRT_OK;
 }
 
-int drt_render_backward_ray_loss(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
-                                 double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
-                                 const int32_t* d_rows, const uint32_t* d_n_rows, const double* d_screen_pixel, const double* d_scale,
-                                 double* d_grad_verts, void* stream) {
+template <bool INPUTS>
+static int render_backward_ray_loss(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                                    double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
+                                    const int32_t* d_rows, const uint32_t* d_n_rows, const double* d_screen_pixel, const double* d_scale,
+                                    double* d_grad_verts, InputGrads in, void* stream) {
     CHECK_BUILT(s);
     if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
     if (n_rays == 0) return DRT_OK;
@@ -1896,10 +1953,47 @@ int drt_render_backward_ray_loss(drt_scene_t* s, const double* d_verts, const do
     hipStream_t st = (hipStream_t)stream;
     const PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
     { StageTimer t(s, st, kStageBackward);
-      DET_LAUNCH(k_render_bwd_rows, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_screen_pixel, d_face1, d_face2, d_rows, d_n_rows, d_scale, d_grad_verts); }
+      DET_LAUNCH_IN(k_render_bwd_rows, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_screen_pixel, d_face1, d_face2, d_rows, d_n_rows, d_scale,
+                    d_grad_verts, in); }
     if (s->prof_on) s->prof_stream = st;
     HIP_TRY(hipGetLastError());
     return DRT_OK;
+}
+#undef DET_LAUNCH_IN
+
+extern "C" {
+
+int drt_render_backward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                        double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
+                        const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                        const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts, void* stream) {
+    return render_backward<false>(s, d_verts, d_origin, d_dir, n_rays, ior_int, ior_ext, d_face1, d_face2, d_valid_idx, d_n_valid,
+                                  d_grad_out_ori, d_grad_out_dir, d_grad_verts, InputGrads{}, stream);
+}
+
+int drt_render_backward_inputs(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                               double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
+                               const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                               const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts,
+                               double* d_grad_origin, double* d_grad_dir, double* d_grad_ior, void* stream) {
+    return render_backward<true>(s, d_verts, d_origin, d_dir, n_rays, ior_int, ior_ext, d_face1, d_face2, d_valid_idx, d_n_valid,
+                                 d_grad_out_ori, d_grad_out_dir, d_grad_verts, InputGrads{d_grad_origin, d_grad_dir, d_grad_ior}, stream);
+}
+
+int drt_render_backward_ray_loss(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                                 double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
+                                 const int32_t* d_rows, const uint32_t* d_n_rows, const double* d_screen_pixel, const double* d_scale,
+                                 double* d_grad_verts, void* stream) {
+    return render_backward_ray_loss<false>(s, d_verts, d_origin, d_dir, n_rays, ior_int, ior_ext, d_face1, d_face2, d_rows, d_n_rows,
+                                           d_screen_pixel, d_scale, d_grad_verts, InputGrads{}, stream);
+}
+
+int drt_render_backward_ray_loss_inputs(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                                        double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
+                                        const int32_t* d_rows, const uint32_t* d_n_rows, const double* d_screen_pixel, const double* d_scale,
+                                        double* d_grad_verts, double* d_grad_origin, double* d_grad_dir, double* d_grad_ior, void* stream) {
+    return render_backward_ray_loss<true>(s, d_verts, d_origin, d_dir, n_rays, ior_int, ior_ext, d_face1, d_face2, d_rows, d_n_rows,
+                                          d_screen_pixel, d_scale, d_grad_verts, InputGrads{d_grad_origin, d_grad_dir, d_grad_ior}, stream);
 }
 
 int drt_ray_loss(const double* d_out_ori, const double* d_out_dir, const uint8_t* d_mask, const double* d_screen_pixel,

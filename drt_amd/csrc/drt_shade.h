@@ -122,6 +122,30 @@ DRT_HD void bounce_backward(const Bounce& b, d3 g_new_o, d3 g_wt, d3& gv0, d3& g
     gv0 -= (g_s + g_e1) + g_e2;
 }
 
+// bounce_backward plus the adjoint of eta (g_eta; set).  eta enters only through w = eta*d + k*n and k = eta*ci - ct, so
+// g_eta = dot(g_w, d) + g_k*ci; g_w and g_k are recomputed with bounce_backward's own statements (the same bits, which the
+// compiler shares).  bounce_backward itself is left alone: the kernels that do not need g_eta keep their code.
+DRT_HD void bounce_backward_eta(const Bounce& b, d3 g_new_o, d3 g_wt, d3& gv0, d3& gv1, d3& gv2, d3& g_o, d3& g_d, double& g_eta) {
+    bounce_backward(b, g_new_o, g_wt, gv0, gv1, gv2, g_o, g_d);
+    const d3 G = g_wt + 1e-5 * g_new_o;
+    const d3 g_w = (G - dot(b.wt, G) * b.wt) / b.wl;
+    const double g_k = dot(g_w, b.n);
+    g_eta = dot(g_w, b.d) + g_k * b.ci;
+}
+
+// eta -> (ior_int, ior_ext) through bounce_forward's `entering` branch (sg = 1: eta = ext / int; sg = -1: eta = int / ext); the
+// branch and the TIR flag carry no gradient, as in torch.  Torch's quotient rule: d/d num = g / den, d/d den = -g * ((num / den) / den).
+// Accumulates into g_int / g_ext.
+DRT_HD void eta_to_ior(const Bounce& b, double ior_int, double ior_ext, double g_eta, double& g_int, double& g_ext) {
+    if (b.sg > 0.0) {
+        g_ext += g_eta / ior_int;
+        g_int += -g_eta * (b.eta / ior_int);
+    } else {
+        g_int += g_eta / ior_ext;
+        g_ext += -g_eta * (b.eta / ior_ext);
+    }
+}
+
 // ray_loss term of one completed path (reference optim.py:100-106):
 //   target = normalize(screen_pixel - out_ori.detach()); diff = out_dir - target; loss += |diff|^2
 // Returns the term and d loss / d out_dir (no gradient reaches out_ori: it is detached).

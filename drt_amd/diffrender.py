@@ -54,7 +54,25 @@ resy = 960
 resx = 1280
 Float = torch.float64
 device = "cuda"
-extIOR, intIOR = 1.00029, 1.5
+extIOR, intIOR = 1.00029, 1.5      # floats, or 0-dim float64 tensors (CPU or GPU, requires_grad for a learnable IOR: see _ior_host)
+
+
+def _ior_host(x, what):
+    """The float value of an index of refraction.  A tensor (0-dim, e.g. a learnable float64 leaf) is read to the host ONCE per render
+    call -- for a GPU tensor a device->host copy that waits for the work queued in front of it; a graph capture cannot do that read."""
+    if not isinstance(x, torch.Tensor):
+        return float(x)
+    if x.numel() != 1:
+        raise ValueError(f"{what} must be a float or a 0-dim tensor, got shape {tuple(x.shape)}")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what} is a tensor: its value is read to the host by every render call, which a graph capture cannot do "
+                           "(capture with a float IOR; a learnable IOR belongs to the eager loop)")
+    return float(x.detach())
+
+
+def _wants_input_grads(*xs):
+    """True when autograd would need d / d x for one of these render inputs (rays, IORs): tensors that require grad, grad mode on."""
+    return torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in xs)
 
 
 class Ray:
@@ -362,6 +380,7 @@ class _RenderTransparent(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertices, origin, ray_dir, scene, ior_int, ior_ext, link, grid=(0, None), binding=None):
+        ior = (_ior_host(ior_int, "intIOR"), _ior_host(ior_ext, "extIOR"))
         ctx.link = link
         ctx.binding = binding
         v = _f64c(vertices.detach(), "vertices")
@@ -370,7 +389,13 @@ class _RenderTransparent(torch.autograd.Function):
         n = o.shape[0]
         om = scene.optix_mesh            # owns the buffers zeroed ahead of time: its drt_destroy waits for the zeroing before they are released
         capturing = torch.cuda.is_current_stream_capturing()
-        need_bwd = ctx.needs_input_grad[0]
+        # gradients of the rays / IORs requested (drt_render_backward_inputs): the backward needs the list of completed paths, and
+        # ray_loss hands over its row list instead of the eager vertex-only stash
+        nig = ctx.needs_input_grad
+        need_inputs = nig[1] or nig[2] or nig[4] or nig[5]
+        ctx.need_inputs = need_inputs
+        ctx.ior_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
+        need_bwd = nig[0] or need_inputs
         recycle = binding is not None or (RECYCLE_OUTPUTS and n >= RECYCLE_MIN_RAYS)  # (any grid mode: a call that verifies every ray -- no cache, or the
                                                                                   #  establishing one -- then at least does not write the dead rows again)
         # Inside a graph capture: REPLAY = RECYCLE.  A set the eager warm-up calls left in the pool is taken out of it for good and becomes the
@@ -441,7 +466,7 @@ class _RenderTransparent(torch.autograd.Function):
             counts = tuple(_use_count(t) for t in bases)          # with nobody but these three names holding them
         face1 = torch.empty(n, dtype=torch.int32, device=o.device)
         face2 = torch.empty(n, dtype=torch.int32, device=o.device)
-        if (SPLIT_LOSS and need_bwd and EAGER_LOSS_GRAD and link is not None and not capturing and n >= SPLIT_LOSS_MIN_RAYS):
+        if (SPLIT_LOSS and need_bwd and not need_inputs and EAGER_LOSS_GRAD and link is not None and not capturing and n >= SPLIT_LOSS_MIN_RAYS):
             link.pre = (det.acc(v), det.scalar(o.device))
         _render_seq[0] += 1
         if link is not None:
@@ -462,7 +487,7 @@ class _RenderTransparent(torch.autograd.Function):
                                                             took[5].data_ptr(), took[6].data_ptr(), stream_id))
                 _arm_seed(scene.optix_mesh._h, grid, n)
                 _lib.check(_lib.lib().drt_render_forward(
-                    scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), n, float(ior_int), float(ior_ext),
+                    scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), n, ior[0], ior[1],
                     out_ori.data_ptr(), out_dir.data_ptr(), mask.data_ptr(), face1.data_ptr(), face2.data_ptr(),
                     _lib.ptr(valid_idx), _lib.ptr(n_valid), *_tile_hint(n), grid[0] | (0 if DENSE_FACE_IDS else 16), _lib.ptr(grid[1]), stream_id))
             except BaseException:
@@ -498,11 +523,11 @@ class _RenderTransparent(torch.autograd.Function):
         if not need_bwd:
             valid_idx = n_valid = None
         ctx.scene = scene
-        ctx.ior = (float(ior_int), float(ior_ext))
+        ctx.ior = ior
         ctx.save_for_backward(v, o, d, face1, face2, valid_idx, n_valid)
         if link is not None:
             link.paths = (valid_idx, n_valid)        # the rays with mask = 1: ray_loss walks this list instead of all N rays
-            link.render = (scene, v, o, d, face1, face2, ctx.ior) if need_bwd else None
+            link.render = (scene, v, o, d, face1, face2, ctx.ior) if need_bwd and not need_inputs else None     # (None: no eager stash)
         # an output the loss does not use must reach backward() as None, not as a materialised [N,3] float64 zero tensor:
         # the reference's ray_loss detaches out_ori (optim.py:100), and filling 1.8 GB of zeros per step cost 0.3 ms
         ctx.set_materialize_grads(False)
@@ -524,29 +549,51 @@ class _RenderTransparent(torch.autograd.Function):
         # (the usual step -- one ray_loss, eager stash, nothing dense -- is ONE small launch: stash * scale)
         grad_v = None if (g_ori is None and g_dir is None and pending and all(e[0] is None for e in pending)) else det.acc(v)
         h = ctx.scene.optix_mesh._h
+        # rays / IORs (ctx.need_inputs): zeros for rows without a completed path; no origin gradient when nothing reached out_ori (the
+        # reference's ray_loss detaches it, and with flat faces the exit direction does not depend on the origin)
+        g_in = (None, None, None)
+        if ctx.need_inputs:
+            nig, n = ctx.needs_input_grad, o.shape[0]
+            g_in = (torch.zeros((n, 3), dtype=torch.float64, device=o.device) if nig[1] and g_ori is not None else None,
+                    torch.zeros((n, 3), dtype=torch.float64, device=o.device) if nig[2] else None,
+                    det.acc(torch.empty(2, dtype=torch.float64, device=o.device)) if nig[4] or nig[5] else None)
+        in_ptrs = tuple(_lib.ptr(t) for t in g_in)
         with _on(o.device):
             if g_ori is not None or g_dir is not None:
                 g_ori = None if g_ori is None else _f64c(g_ori, "grad_out_ori")
                 g_dir = None if g_dir is None else _f64c(g_dir, "grad_out_dir")
-                _lib.check(_lib.lib().drt_render_backward(
-                    h, v.data_ptr(), o.data_ptr(), d.data_ptr(), o.shape[0], ctx.ior[0], ctx.ior[1],
-                    face1.data_ptr(), face2.data_ptr(), _lib.ptr(valid_idx), _lib.ptr(n_valid),
-                    _lib.ptr(g_ori), _lib.ptr(g_dir), grad_v.data_ptr(), _stream()))
+                args = (h, v.data_ptr(), o.data_ptr(), d.data_ptr(), o.shape[0], ctx.ior[0], ctx.ior[1],
+                        face1.data_ptr(), face2.data_ptr(), _lib.ptr(valid_idx), _lib.ptr(n_valid),
+                        _lib.ptr(g_ori), _lib.ptr(g_dir), grad_v.data_ptr())
+                if ctx.need_inputs:
+                    _lib.check(_lib.lib().drt_render_backward_inputs(*args, *in_ptrs, _stream()))
+                else:
+                    _lib.check(_lib.lib().drt_render_backward(*args, _stream()))
             for rows, n_rows, sp, scale in pending:
                 if rows is None:                # eager entry: n_rows is the unit-seed vertex gradient ray_loss's forward left
                     continue
-                _lib.check(_lib.lib().drt_render_backward_ray_loss(
-                    h, v.data_ptr(), o.data_ptr(), d.data_ptr(), o.shape[0], ctx.ior[0], ctx.ior[1], face1.data_ptr(), face2.data_ptr(),
-                    rows.data_ptr(), n_rows.data_ptr(), sp.data_ptr(), scale.data_ptr(), grad_v.data_ptr(), _stream()))
+                args = (h, v.data_ptr(), o.data_ptr(), d.data_ptr(), o.shape[0], ctx.ior[0], ctx.ior[1], face1.data_ptr(), face2.data_ptr(),
+                        rows.data_ptr(), n_rows.data_ptr(), sp.data_ptr(), scale.data_ptr(), grad_v.data_ptr())
+                if ctx.need_inputs:
+                    _lib.check(_lib.lib().drt_render_backward_ray_loss_inputs(*args, *in_ptrs, _stream()))
+                else:
+                    _lib.check(_lib.lib().drt_render_backward_ray_loss(*args, _stream()))
         if grad_v is not None:
             grad_v = det.value(grad_v, v)          # (deterministic mode: the exact integer sums, rounded once)
+        g_ior = [None, None]
+        if g_in[2] is not None:
+            both = det.value(g_in[2], torch.empty(2, dtype=torch.float64))       # [d / d ior_int, d / d ior_ext] on the rays' device
+            for k in (0, 1):
+                if ctx.needs_input_grad[4 + k]:
+                    shape, dtype, dev = ctx.ior_like[k]
+                    g_ior[k] = both[k].reshape(shape).to(dtype=dtype, device=dev)
         for rows, stash, wide, scale in pending:
             if rows is None:
                 if det.SINK is not None and wide is not None:
                     det.SINK.append((wide, scale))        # full_batch_step sums the cells of all calls and ranks exactly, then converts once
                     continue
                 grad_v = torch.addcmul(grad_v, stash, scale) if grad_v is not None else stash * scale
-        return grad_v, None, None, None, None, None, None, None, None
+        return grad_v, g_in[0], g_in[1], None, g_ior[0], g_ior[1], None, None, None
 
 
 class _RayLoss(torch.autograd.Function):
@@ -645,11 +692,12 @@ class _RenderRayLossFused(torch.autograd.Function):
         va = _flag_bytes(valid, "valid", o.shape[0])
         loss = det.scalar(o.device)
         grad_v = det.acc(v)
+        ior = (_ior_host(ior_int, "intIOR"), _ior_host(ior_ext, "extIOR"))
         with _on(o.device):
             _arm_seed(scene.optix_mesh._h, grid, o.shape[0])
             _lib.check(_lib.lib().drt_render_ray_loss_fused(
                 scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), o.shape[0],
-                float(ior_int), float(ior_ext), loss.data_ptr(), grad_v.data_ptr(), None, *_tile_hint(o.shape[0]), grid[0], _lib.ptr(grid[1]), _stream()))
+                ior[0], ior[1], loss.data_ptr(), grad_v.data_ptr(), None, *_tile_hint(o.shape[0]), grid[0], _lib.ptr(grid[1]), _stream()))
         ctx.wide = grad_v if grad_v.dtype == torch.int64 else None
         ctx.save_for_backward(det.value(grad_v, v))
         return det.value(loss)
@@ -839,7 +887,13 @@ class Scene(StepwiseMixin):
         return out_ori, out_dir, mask
 
     def ray_loss_fused(self, origin, ray_dir, screen_pixel, valid):
-        """ray_loss of this view without materialising out_ori/out_dir/mask."""
+        """ray_loss of this view without materialising out_ori/out_dir/mask.  The fused kernel differentiates the vertices only: when
+        a gradient of the rays or of a tensor IOR is requested, this is render_transparent + ray_loss (`fused_fallback_inputs` in
+        cache_report())."""
+        if _wants_input_grads(intIOR, extIOR) or (not isinstance(origin, RayBinding) and _wants_input_grads(origin, ray_dir)):
+            _stats["fused_fallback_inputs"] += 1
+            out_ori, out_dir, mask = self.render_transparent(origin, ray_dir)
+            return ray_loss(out_ori, out_dir, mask, screen_pixel, valid)
         if isinstance(origin, RayBinding):
             b = origin
             return _RenderRayLossFused.apply(self.vertices, b.origin, b.ray_dir, screen_pixel, valid, self, intIOR, extIOR, b._grid())

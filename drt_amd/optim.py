@@ -495,6 +495,9 @@ def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotrop
     elif remesh == "isotropic-host":
         from .remesh import Meshlabserver
         remesh = Meshlabserver().remesh
+    if float(HyperParams.get("ior_lr", 0) or 0) > 0:
+        raise NotImplementedError("HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by optimize_sharded: use the drop-in loop "
+                                  "optimize(..., fused=False)")
     say = output and rank == 0
     Render.intIOR = HyperParams["IOR"]
     Render.resy, Render.resx = data.resy, data.resx
@@ -557,14 +560,26 @@ def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=Fa
     """The reference's pass / iteration loop (optim.py:190-215) for an existing scene and data object.
     ``remesh``: "isotropic" (default) re-tessellates to ``remesh_len`` before every pass like the reference's
     ``meshlabserver.remesh`` (optim.py:195), with the device remesher of drt_amd.remesh_gpu ("isotropic-host": the sequential
-    host version of drt_amd.remesh); ``None`` keeps the topology; or any callable ``remesh(scene, remesh_len)``."""
+    host version of drt_amd.remesh); ``None`` keeps the topology; or any callable ``remesh(scene, remesh_len)``.
+
+    ``HyperParams["ior_lr"] > 0`` (absent or 0: the reference's loop): the index of refraction is learned too -- a float64 leaf, starting
+    at ``HyperParams["IOR"]``, in its own SGD param group with that learning rate (same momentum / Nesterov, not clamped by limit_hook),
+    carried across passes and remeshes.  The drop-in loop only (``fused=False``); returns (scene, history, fitted IOR), and
+    ``Render.intIOR`` is the fitted float afterwards."""
+    ior_lr = float(HyperParams.get("ior_lr", 0) or 0)
+    if ior_lr > 0 and fused:
+        raise NotImplementedError("HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by the fused loop: use the drop-in loop "
+                                  "optimize(..., fused=False)")
     if remesh == "isotropic":               # on the device (drt_amd.remesh_gpu); "isotropic-host": the sequential host version, its checker
         from .remesh_gpu import GpuMeshlabserver
         remesh = GpuMeshlabserver().remesh
     elif remesh == "isotropic-host":
         from .remesh import Meshlabserver
         remesh = Meshlabserver().remesh
-    Render.intIOR = HyperParams["IOR"]
+    ior = None
+    if ior_lr > 0:
+        ior = torch.tensor(float(HyperParams["IOR"]), dtype=Float, device=scene.vertices.device, requires_grad=True)
+    Render.intIOR = HyperParams["IOR"] if ior is None else ior
     Render.resy, Render.resx = data.resy, data.resx
     loss_calculator = Loss_calculator(scene, data, HyperParams, fused=fused)
     start_time = time.time()
@@ -590,6 +605,8 @@ def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=Fa
                     history.append(float(total))
             continue
         init_vertices, parameter, opt = setup_opt(scene, lr, HyperParams)
+        if ior is not None:
+            opt.add_param_group({"params": [ior], "lr": ior_lr})
         for it in range(HyperParams["Iters"]):
             opt.zero_grad()
             vertices = init_vertices + parameter
@@ -600,8 +617,13 @@ def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=Fa
                 print(f"Iteration {it}: {loss_string(parts)} maxgrad={parameter.grad.abs().max():g}")
             history.append(float(loss.detach())) if (it % 100 == 0) else None
             opt.step()
+        if ior is not None and output:
+            print(f"IOR {float(ior.detach()):.6f}")
     if output:
         print(f"optimize time : {time.time() - start_time}")
+    if ior is not None:
+        Render.intIOR = float(ior.detach())
+        return scene, history, Render.intIOR
     return scene, history
 
 

@@ -26,9 +26,11 @@ from . import captured_data, diffrender as Render, mesh_io, metrics, optim, view
 
 
 def run(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, fused=True, output=True, device=0, n_views=72,
-        views_per_step=None):
+        views_per_step=None, ior_start=None):
     """``views_per_step=None``: the single-process loop (optim.optimize).  An int, or "all" (one epoch of the refraction schedule per
-    iteration), goes through optim.optimize_sharded on every rank of the default process group (one process without one)."""
+    iteration), goes through optim.optimize_sharded on every rank of the default process group (one process without one).
+    ``HyperParams["ior_lr"] > 0``: the IOR is fitted too (the drop-in loop, optim.optimize), starting at ``ior_start`` (default
+    ``HyperParams["IOR"]``, which is also the IOR the synthetic capture is traced with); the report gains ``ior``, the fitted value."""
     if views_per_step is not None or torch.distributed.is_available() and torch.distributed.is_initialized():
         return run_sharded(HyperParams, data_path, result_path, capture, res, output, device, n_views, views_per_step or 1)
     name = HyperParams["name"]
@@ -49,7 +51,12 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
     if scan_scene is not None:
         report["hull_to_scan"] = metrics.hausdorff(scene, scan_scene)
     t0 = time.time()
-    scene, history = optim.optimize(scene, data, HyperParams, output=output, fused=fused)
+    if float(HyperParams.get("ior_lr", 0) or 0) > 0:
+        start = HyperParams["IOR"] if ior_start is None else float(ior_start)
+        report["ior_start"] = start
+        scene, history, report["ior"] = optim.optimize(scene, data, dict(HyperParams, IOR=start), output=output, fused=False)
+    else:
+        scene, history = optim.optimize(scene, data, HyperParams, output=output, fused=fused)
     torch.cuda.synchronize()
     report["optimize_seconds"] = time.time() - t0
     report["iterations"] = HyperParams["Pass"] * HyperParams["Iters"]
@@ -137,6 +144,9 @@ def main(argv=None):
     ap.add_argument("--views", type=int, default=72, help="views of the synthetic capture (the real captures have 72)")
     ap.add_argument("--ior", type=float, default=optim.HyperParams["IOR"])
     ap.add_argument("--dropin", action="store_true", help="use the reference-shaped (unfused) loss terms")
+    ap.add_argument("--fit-ior", type=float, default=0.0, metavar="LR",
+                    help="also learn the index of refraction with this SGD learning rate (implies --dropin); the report gains \"ior\"")
+    ap.add_argument("--ior-start", type=float, default=None, help="with --fit-ior: the IOR the fit starts from (default: --ior)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--views-per-step", type=_views_per_step, default=None, metavar="N|all",
                     help="refraction views per iteration (all: every view of the schedule once) on the multi-rank loop; "
@@ -145,13 +155,16 @@ def main(argv=None):
     import numpy as np
     np.random.seed(a.seed)
     hp = dict(optim.HyperParams, name=a.name, Pass=a.passes, Iters=a.iters, num_view=a.num_view, IOR=a.ior)
+    if a.fit_ior > 0:
+        hp["ior_lr"] = a.fit_ior
     from . import dist as ddist
     if a.views_per_step is None and ddist.env_world()[2] == 1:
-        _, report = run(hp, a.data_path, a.result_path, a.capture, a.res, fused=not a.dropin, n_views=a.views)
+        _, report = run(hp, a.data_path, a.result_path, a.capture, a.res, fused=not (a.dropin or a.fit_ior > 0), n_views=a.views,
+                        ior_start=a.ior_start)
         print(json.dumps(report))
         return
-    if a.dropin:
-        raise SystemExit("--dropin has no multi-rank form: the sharded loop runs the one-pass terms")
+    if a.dropin or a.fit_ior > 0:
+        raise SystemExit("--dropin / --fit-ior have no multi-rank form: the sharded loop runs the one-pass terms")
     _, local_rank, world = ddist.init()
     device = local_rank % torch.cuda.device_count()
     torch.cuda.set_device(device)

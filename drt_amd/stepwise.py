@@ -54,6 +54,14 @@ def hit_point_terms(origin, direction, triangles):
     return u, v, t, n / n.norm(p=2, dim=1, keepdim=True)
 
 
+def _ior_like(x, t):
+    """An IOR as a tensor shaped like ``t``: a float fills one; a tensor IOR (0-dim, e.g. a learnable leaf on any device) is moved and
+    broadcast, so that autograd differentiates it through the torch.where of refract_ray."""
+    if isinstance(x, torch.Tensor):
+        return x.to(dtype=t.dtype, device=t.device).expand_as(t)
+    return torch.full_like(t, x)
+
+
 class StepwiseMixin:
     """Mixed into drt_amd.diffrender.Scene."""
 
@@ -71,8 +79,9 @@ class StepwiseMixin:
         cos_i = _dot(wo, intersect.n).clamp(-1, 1)
         leaving = torch.logical_not(cos_i > 0)
         sign = torch.where(leaving, -torch.ones_like(t), torch.ones_like(t))
-        eta_i = torch.where(leaving, torch.full_like(t, Render.intIOR), torch.full_like(t, Render.extIOR))
-        eta_t = torch.where(leaving, torch.full_like(t, Render.extIOR), torch.full_like(t, Render.intIOR))
+        ior_int, ior_ext = _ior_like(Render.intIOR, t), _ior_like(Render.extIOR, t)
+        eta_i = torch.where(leaving, ior_int, ior_ext)
+        eta_t = torch.where(leaving, ior_ext, ior_int)
         n = intersect.n * sign.view(-1, 1)
         intersect.n = n                                 # the reference flips the stored normal in place
         cos_i = cos_i * sign

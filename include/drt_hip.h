@@ -163,6 +163,21 @@ int drt_render_backward(drt_scene_t* s, const double* d_verts, const double* d_o
                         const int32_t* d_valid_idx, const int64_t* d_n_valid,
                         const double* d_grad_out_ori, const double* d_grad_out_dir,
                         double* d_grad_verts, void* stream);
+/* drt_render_backward that also returns the gradients w.r.t. the other inputs of the render call (the reference differentiates
+ * them all: its path is plain torch autograd).  Each output is optional (NULL = not computed) and added to (+=):
+ *   d_grad_origin float64 [N,3]  d / d origin of every ray with a completed path (other rows untouched; one writer per row),
+ *   d_grad_dir    float64 [N,3]  d / d ray_dir, likewise,
+ *   d_grad_ior    [2]            d / d ior_int, d / d ior_ext -- two float64, or in deterministic mode two fixed-point cells
+ *                                (DRT_FX_BYTES_PER_VALUE each) like d_grad_verts.
+ * Through the `entering` branch of each bounce eta is ior_ext / ior_int or ior_int / ior_ext; the branch and the total-internal-
+ * reflection test carry no gradient.  d_grad_verts gets the same gradient drt_render_backward adds (bit for bit in deterministic mode). */
+int drt_render_backward_inputs(drt_scene_t* s, const double* d_verts, const double* d_origin,
+                               const double* d_dir, int64_t n_rays, double ior_int, double ior_ext,
+                               const int32_t* d_face1, const int32_t* d_face2,
+                               const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                               const double* d_grad_out_ori, const double* d_grad_out_dir,
+                               double* d_grad_verts, double* d_grad_origin, double* d_grad_dir,
+                               double* d_grad_ior, void* stream);
 
 /* ---- Loss_calculator.ray_loss, optim.py:91-108 ------------------------------------------
  * loss = sum over rays with valid & mask of |out_dir - normalize(screen_pixel - out_ori)|^2.
@@ -251,6 +266,16 @@ int drt_render_backward_ray_loss(drt_scene_t* s, const double* d_verts, const do
                                  const int32_t* d_rows, const uint32_t* d_n_rows,
                                  const double* d_screen_pixel, const double* d_scale,
                                  double* d_grad_verts, void* stream);
+/* drt_render_backward_ray_loss plus the input gradients of drt_render_backward_inputs (same conventions: each optional, +=).
+ * No gradient reaches d_grad_origin from this loss: it detaches out_ori, and with flat faces the exit direction does not depend on
+ * the origin (the rows it touches get exact zeros added). */
+int drt_render_backward_ray_loss_inputs(drt_scene_t* s, const double* d_verts, const double* d_origin,
+                                        const double* d_dir, int64_t n_rays, double ior_int, double ior_ext,
+                                        const int32_t* d_face1, const int32_t* d_face2,
+                                        const int32_t* d_rows, const uint32_t* d_n_rows,
+                                        const double* d_screen_pixel, const double* d_scale,
+                                        double* d_grad_verts, double* d_grad_origin, double* d_grad_dir,
+                                        double* d_grad_ior, void* stream);
 
 /* One pass: render_transparent + ray_loss + d ray_loss / d vertices, nothing dense written.
  * *d_loss += loss, d_grad_verts [V,3] += gradient (both float64, zero them first);
