@@ -207,16 +207,19 @@ def get_data(HyperParams, **kw):
 
 class SyntheticData(Data):
     """Turntable views of a ground-truth mesh traced through the same path, with the tuple layout of
-    Data.get_view; built on the device and resident there (stands in for the undistributed captures)."""
+    Data.get_view; built on the device and resident there (stands in for the undistributed captures).
+    ``path_law``: None (the default: the reference's two-bounce path, so pixels whose true light path has three or more surface
+    interactions carry no target), or (max_bounces, tir) to trace the ground truth with ``Scene.render_paths``."""
 
-    def __init__(self, scene_gt, center, extent, resx, resy, num_view=72, device="cuda", n_total=72, view_ids=None, seed=0, name="synthetic"):
+    def __init__(self, scene_gt, center, extent, resx, resy, num_view=72, device="cuda", n_total=72, view_ids=None, seed=0, name="synthetic",
+                 path_law=None):
         self.resx, self.resy, self.num_view, self.n_total = resx, resy, num_view, n_total
         self.name, self.device = name, device
         self.rng = np.random.RandomState(seed)
 
         def render_gt(o, d):
             with torch.no_grad():
-                return scene_gt.render_transparent(o, d)
+                return scene_gt.render_transparent(o, d) if path_law is None else scene_gt.render_paths(o, d, *path_law)
 
         def hit_gt(o, d):
             return scene_gt.render_mask(o, d) > 0
@@ -237,9 +240,10 @@ class SyntheticData(Data):
 CAMERAS = {"pointgray": Data_Pointgray, "redmi": Data_Redmi}
 
 
-def synthetic_capture_arrays(scene_gt, center, extent, camera="pointgray", n_views=N_CAPTURE_VIEWS, view_ids=None, device="cuda"):
+def synthetic_capture_arrays(scene_gt, center, extent, camera="pointgray", n_views=N_CAPTURE_VIEWS, view_ids=None, device="cuda", path_law=None):
     """Trace a ground-truth scene (``drt_amd.diffrender.Scene``) from a turntable of ``n_views`` cameras of the given
-    kind and return the capture's datasets as numpy arrays (``view_ids``: store only these views, in this order)."""
+    kind and return the capture's datasets as numpy arrays (``view_ids``: store only these views, in this order).
+    ``path_law``: as in SyntheticData."""
     cls = CAMERAS[camera]
     resy, resx = cls.resy, cls.resx
     cams = views.turntable_cameras(center, extent, n_views, resx, resy)
@@ -251,7 +255,7 @@ def synthetic_capture_arrays(scene_gt, center, extent, camera="pointgray", n_vie
         R, K, Rinv, Kinv = cams[k]
         origin, ray_dir = views.generate_ray(resy, resx, Kinv, Rinv, device=device)
         with torch.no_grad():
-            out_ori, out_dir, m = scene_gt.render_transparent(origin, ray_dir)
+            out_ori, out_dir, m = scene_gt.render_transparent(origin, ray_dir) if path_law is None else scene_gt.render_paths(origin, ray_dir, *path_law)
             hit = scene_gt.render_mask(origin, ray_dir) > 0
         sp = views.screen_targets(out_ori, out_dir, m, cams[k], center, extent).cpu().numpy()
         out["cam_proj"].append(np.asarray(R, dtype=np.float64))

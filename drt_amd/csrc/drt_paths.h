@@ -1,0 +1,99 @@
+// drt_paths.h -- one camera ray through a refraction path of up to K surface interactions, with optional internal reflection,
+// and its adjoint w.r.t. the vertices.
+//
+// The path law (opt-in: Scene.render_paths; DESIGN.md "Paths of up to K interactions").  A camera ray repeats:
+//   trace   closest hit under the tracer contract (float32 cast of the float64 ray); once K interactions are used up the any-hit form
+//   miss    the path ends; it is valid iff it has made an even, non-zero number of refractions
+//   hit     before the K-th interaction is used up: bounce_forward on the float64 ray and triangle, unchanged
+//             not TIR            -> continues as (new_o, wt), one more refraction
+//             TIR, tir = drop    -> the path dies
+//             TIR, tir = reflect -> continues mirrored (bounce_reflect), no refraction counted
+//   hit     with K interactions used up: invalid
+// K = 2 with tir = drop is trace_path (drt_path.h): the same rule through the same device functions, the same bits.
+//
+//   trace_path_k              forward; records the face of every interaction and their number
+//   path_recompute_backward_k recomputes the path from the camera ray and that face tape, reverses it
+// Plain C++ (also compiled by tests/hostsim); the gradient sink is a functor as in drt_path.h.
+#pragma once
+#include "drt_path.h"
+
+namespace drt {
+
+constexpr int kMaxBounces = 8;
+
+// A miss ends the path: valid iff an even, non-zero number of refractions was made.
+DRT_HD bool path_exit_valid(int n_refr) { return n_refr > 0 && (n_refr & 1) == 0; }
+
+// One interaction of the law on face `face`: the continuing ray in (o, d), the refraction count bumped.  False: the path dies (TIR, drop).
+DRT_HD bool path_interact(const PathCtx& c, int32_t face, bool reflect, d3& o, d3& d, int& n_refr) {
+    d3 v0, v1, v2;
+    int32_t vid[3];
+    Bounce b;
+    load_tri64(c, face, v0, v1, v2, vid);
+    bounce_forward(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b);
+    if (!b.tir) {
+        o = b.new_o; d = b.wt;
+        ++n_refr;
+        return true;
+    }
+    if (!reflect) return false;
+    d3 no, wr;
+    bounce_reflect(b, o, no, wr);
+    o = no; d = wr;
+    return true;
+}
+
+// Returns true when the path completes; out_o / out_d are then the exit ray.  faces[0 .. n_hits) are the faces of the interactions that
+// took place (also on a path that ends invalid: the caller decides what it reports for those), faces[n_hits .. K) are left alone.
+DRT_HD bool trace_path_k(const PathCtx& c, Stack& st, d3 o, d3 d, int max_bounces, bool reflect, int32_t* faces, int& n_hits, d3& out_o, d3& out_d) {
+    int n_refr = 0;
+    n_hits = 0;
+    for (int k = 0; k <= max_bounces; ++k) {
+        const Hit h = k < max_bounces ? traverse<false>(c.tc.nodes, c.tc.tris, c.tc.n_tris, to_f32(o), to_f32(d), st)
+                                      : traverse<true>(c.tc.nodes, c.tc.tris, c.tc.n_tris, to_f32(o), to_f32(d), st);
+        if (h.face < 0) {
+            if (!path_exit_valid(n_refr)) return false;
+            out_o = o; out_d = d;
+            return true;
+        }
+        if (k == max_bounces) return false;
+        faces[k] = h.face;
+        n_hits = k + 1;
+        if (!path_interact(c, h.face, reflect, o, d, n_refr)) return false;
+    }
+    return false;
+}
+
+// Adjoint of a completed path w.r.t. the vertices: recompute the n_hits interactions from the camera ray and the face tape (element k
+// at faces[k * face_stride]; the TIR flags are recomputed, the same bits as in the forward: a set flag on a completed path means the ray
+// was mirrored), reverse them, hand the vertex gradients to `add(vertex_id, d3)`.  Only the incoming ray of every interaction is kept
+// (6 doubles each); its Bounce (about 45 doubles) is rebuilt right before it is reversed.
+template <typename Add>
+DRT_HD void path_recompute_backward_k(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 g_ori, d3 g_dir, Add add) {
+    d3 ro[kMaxBounces], rd[kMaxBounces];
+    d3 v0, v1, v2;
+    int32_t vid[3];
+    Bounce b;
+    if (n_hits > kMaxBounces) n_hits = kMaxBounces;
+    for (int k = 0; k < n_hits; ++k) {
+        ro[k] = o; rd[k] = d;
+        if (k + 1 == n_hits) break;              // (the last interaction is rebuilt by the reverse loop)
+        load_tri64(c, faces[k * face_stride], v0, v1, v2, vid);
+        bounce_forward(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b);
+        if (b.tir) { d3 no, wr; bounce_reflect(b, o, no, wr); o = no; d = wr; }
+        else { o = b.new_o; d = b.wt; }
+    }
+    const d3 z{0.0, 0.0, 0.0};
+    d3 g_o = g_ori, g_d = g_dir;
+    for (int k = n_hits - 1; k >= 0; --k) {
+        load_tri64(c, faces[k * face_stride], v0, v1, v2, vid);
+        bounce_forward(ro[k], rd[k], v0, v1, v2, c.ior_ext, c.ior_int, b);
+        d3 ga = z, gb = z, gc = z, g_o_in, g_d_in;
+        if (b.tir) bounce_reflect_backward(b, g_o, g_d, ga, gb, gc, g_o_in, g_d_in);
+        else bounce_backward(b, g_o, g_d, ga, gb, gc, g_o_in, g_d_in);
+        add(vid[0], ga); add(vid[1], gb); add(vid[2], gc);
+        g_o = g_o_in; g_d = g_d_in;
+    }
+}
+
+}  // namespace drt

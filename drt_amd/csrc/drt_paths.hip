@@ -1,0 +1,278 @@
+// drt_paths.hip -- refraction paths of up to K surface interactions with optional internal reflection (drt_paths.h: the law) as a
+// wavefront loop over compact ray lists, and their backward.
+//
+//   k_paths_start   all rays : top-box test; candidates -> list 0 (index + float32 ray), their float64 ray parked in rows of out_ori / out_dir
+//   per interaction k = 0 .. K:
+//     k_trace       list k   : closest hit (k < K) or any hit (k = K: every interaction is used up) -> face per list slot
+//     k_paths_shade list k   : miss -> the path ends (valid iff an even, non-zero number of refractions); hit -> face into the tape,
+//                              float64 bounce_forward / bounce_reflect on the parked ray, survivors -> list k + 1 (the other ping-pong buffer)
+//   k_paths_finish  all rays : dead values on invalid rows, valid rows -> the list the backward walks
+// The float64 state of a ray in flight lives in ITS rows of out_ori / out_dir (as k_shade2's `parked` mode of the two-bounce pipeline), so
+// the exit ray of a completed path is in place when the path ends.  Every list size stays on the device, grids are sized from N, and all
+// launches go to the caller's stream: the call can be captured in a hipGraph.  k_trace is the two-bounce pipeline's (launch_trace_list,
+// instantiated in drt_trace.hip); the staged list append and the gradient sink are shared with it (drt_pathsink.h).
+#include "drt_device.h"
+#include "drt_trace_kernel.h"
+#include "drt_pathsink.h"
+#include "drt_paths.h"
+
+// per-ray state byte while a call is in flight: refractions made so far (<= 8) | kPathDone once the path has ended valid
+constexpr uint8_t kPathDone = 0x80;
+// words of the counter block: sizes of lists 0 .. K, the second-pass counts of the K + 1 traversals, k_trace's retired-workgroup counter,
+// the number of valid rays
+constexpr int kCntList = 0, kCntRedo = 16, kCntDone = 32, kCntValid = 33, kCntWords = 40;
+static_assert(kMaxBounces + 1 <= kCntRedo - kCntList && kMaxBounces + 1 <= kCntDone - kCntRedo, "counter block layout");
+
+struct PathsWs {
+    int64_t cap = 0;
+    int32_t* idx[2] = {nullptr, nullptr};
+    float* ray[2] = {nullptr, nullptr};
+    int32_t* face[2] = {nullptr, nullptr};
+    int32_t* redo = nullptr;
+    uint8_t* state = nullptr;
+    unsigned* cnt = nullptr;
+    int32_t* slow_stack = nullptr;       // overflow area of k_trace's second pass: [kPathBlock * kStackSlowDev]
+};
+
+// each block takes one contiguous run of [0, n), so that what it appends stays in input order
+__device__ __forceinline__ void block_run(unsigned n, unsigned& first, unsigned& last) {
+    const unsigned per_block = ((n + gridDim.x - 1) / gridDim.x + kPathBlock - 1) / kPathBlock * kPathBlock;
+    first = blockIdx.x * per_block;
+    last = min(n, first + per_block);
+    if (first > last) first = last;
+}
+
+__global__ void __launch_bounds__(kPathBlock) k_paths_start(const Node4Q* __restrict__ nodes, int n_tris, const double* __restrict__ origin,
+                                                             const double* __restrict__ dir, unsigned n, double* __restrict__ out_ori,
+                                                             double* __restrict__ out_dir, uint8_t* __restrict__ state, uint8_t* __restrict__ hits,
+                                                             RayList out, unsigned* count) {
+    __shared__ StageMem stage;
+    stage_init(stage);
+    unsigned first, last;
+    block_run(n, first, last);
+    for (unsigned base = first; base < last; base += kPathBlock) {
+        const unsigned i = base + threadIdx.x;
+        bool cand = false;
+        f3 o32{0.f, 0.f, 0.f}, d32{0.f, 0.f, 1.f};
+        if (i < n) {
+            const d3 o = load_d3(origin, i), d = load_d3(dir, i);
+            o32 = to_f32(o); d32 = to_f32(d);
+            cand = n_tris > 0 && hits_top_boxes(nodes, o32, d32);
+            state[i] = 0;
+            hits[i] = 0;
+            if (cand) { store_d3(out_ori, i, o); store_d3(out_dir, i, d); }
+        }
+        stage_push(stage, cand, (int32_t)i, o32, d32, out, count);
+    }
+    stage_flush(stage, out, count);
+}
+
+// list k -> list k + 1.  k == max_bounces: every interaction is used up, the list was traced in the any-hit form and nothing continues.
+__global__ void __launch_bounds__(kPathBlock) k_paths_shade(PathCtx c, int64_t n_rays, int k, int max_bounces, bool reflect, RayList in,
+                                                             const unsigned* __restrict__ n_in, RayList out, unsigned* n_out,
+                                                             double* __restrict__ out_ori, double* __restrict__ out_dir,
+                                                             uint8_t* __restrict__ state, uint8_t* __restrict__ hits, int32_t* __restrict__ tape) {
+    __shared__ StageMem stage;
+    stage_init(stage);
+    const unsigned n = *n_in;
+    const bool last_stage = k >= max_bounces;
+    unsigned first, last;
+    block_run(n, first, last);
+    for (unsigned base = first; base < last; base += kPathBlock) {
+        const unsigned e = base + threadIdx.x;
+        bool go = false;
+        int64_t i = 0;
+        f3 o32{0.f, 0.f, 0.f}, d32{0.f, 0.f, 1.f};
+        if (e < n) {
+            i = in.idx[e];
+            const int32_t f = in.face[e];
+            if (i >= 0 && i < n_rays) {
+                int n_refr = state[i];
+                if (f < 0) {
+                    if (path_exit_valid(n_refr)) state[i] = (uint8_t)n_refr | kPathDone;
+                } else if (!last_stage) {
+                    tape[(int64_t)k * n_rays + i] = f;
+                    hits[i] = (uint8_t)(k + 1);
+                    d3 o = load_d3(out_ori, i), d = load_d3(out_dir, i);
+                    go = path_interact(c, f, reflect, o, d, n_refr);
+                    if (go) {
+                        store_d3(out_ori, i, o); store_d3(out_dir, i, d);
+                        state[i] = (uint8_t)n_refr;
+                        o32 = to_f32(o); d32 = to_f32(d);
+                    }
+                }
+            }
+        }
+        if (!last_stage) stage_push(stage, go, (int32_t)i, o32, d32, out, n_out);
+    }
+    if (!last_stage) stage_flush(stage, out, n_out);
+}
+
+// Dead values on the rows whose path did not complete (their rows may hold a parked ray), flags on the others, valid rows -> valid_idx.
+__global__ void __launch_bounds__(kPathBlock) k_paths_finish(unsigned n, double* __restrict__ out_ori, double* __restrict__ out_dir, uint8_t* __restrict__ mask,
+                                                              const uint8_t* __restrict__ state, uint8_t* __restrict__ hits, int32_t* __restrict__ valid_idx,
+                                                              unsigned* n_valid) {
+    __shared__ StageMem stage;
+    stage_init(stage);
+    const RayList out{valid_idx, nullptr, nullptr};              // index-only list
+    unsigned first, last;
+    block_run(n, first, last);
+    for (unsigned base = first; base < last; base += kPathBlock) {
+        const unsigned i = base + threadIdx.x;
+        bool keep = false;
+        if (i < n) {
+            keep = (state[i] & kPathDone) != 0;
+            const uint8_t m = keep ? 1 : 0;
+            mask[3 * (int64_t)i] = m; mask[3 * (int64_t)i + 1] = m; mask[3 * (int64_t)i + 2] = m;
+            if (!keep) {
+                const d3 z{0.0, 0.0, 0.0};
+                store_d3(out_ori, i, z);
+                store_d3(out_dir, i, z);
+                hits[i] = 0;
+            }
+        }
+        stage_push(stage, keep, (int32_t)i, f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 0.f}, out, n_valid);
+    }
+    stage_flush(stage, out, n_valid);
+}
+
+__global__ void k_paths_count(const unsigned* __restrict__ count, int64_t* __restrict__ out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *out = (int64_t)*count;
+}
+
+// Backward over the list of valid rays: recompute every interaction from the camera ray and the face tape, reverse, scatter the vertex
+// gradients through the LDS hash sink.  A ray brings up to 3 * K vertex references (24 at K = 8, against 6 of the two-bounce path), so a
+// table fill takes a quarter of k_render_bwd's rays; neighbouring rays still share most of their vertices.
+constexpr int kPathsBwdBatch = 256;
+template <bool DET>
+__global__ void __launch_bounds__(256) k_paths_bwd(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir, int64_t n_rays,
+                                                   int max_bounces, const int32_t* __restrict__ tape, const uint8_t* __restrict__ hits,
+                                                   const double* __restrict__ g_out_ori, const double* __restrict__ g_out_dir, double* grad_verts,
+                                                   const int32_t* __restrict__ list, const int64_t* __restrict__ n_list) {
+    __shared__ int32_t hkeys[kHashSize];
+    __shared__ double hsums[3 * kHashSize];
+    int64_t n = *n_list;
+    if (n > n_rays) n = n_rays;
+    const PathSink<DET> add{hkeys, hsums, grad_verts};
+    for (int64_t base = blockIdx.x * (int64_t)kPathsBwdBatch; base < n; base += (int64_t)gridDim.x * kPathsBwdBatch) {
+        add.clear();
+        const int64_t end = base + kPathsBwdBatch < n ? base + kPathsBwdBatch : n;
+        for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
+            const int64_t i = list[k];
+            if (i < 0 || i >= n_rays) continue;
+            const d3 z{0.0, 0.0, 0.0};
+            const d3 g_ori = g_out_ori ? load_d3(g_out_ori, i) : z;
+            const d3 g_dir = g_out_dir ? load_d3(g_out_dir, i) : z;
+            path_recompute_backward_k(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces), g_ori, g_dir, add);
+        }
+        add.flush();
+    }
+}
+
+static PathsWs* ws_of(drt_scene* s) { return static_cast<PathsWs*>(s->paths_ws); }
+
+static int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st) {
+    PathsWs* w = ws_of(s);
+    if (w && n <= w->cap) return DRT_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(DRT_E_INVALID, "drt_render_paths_forward: the first call of this size allocates its ray lists and cannot run inside a stream "
+                                   "capture: issue one such call eagerly before capturing");
+    if (!w) {
+        w = new (std::nothrow) PathsWs();
+        if (!w) return fail(DRT_E_NOMEM, "host allocation failed");
+        s->paths_ws = w;
+        HIP_TRY(hipMalloc(&w->cnt, sizeof(unsigned) * kCntWords));
+        HIP_TRY(hipMalloc(&w->slow_stack, sizeof(int32_t) * (size_t)kPathBlock * kStackSlowDev));
+    }
+    for (int k = 0; k < 2; ++k) {
+        (void)hipFree(w->idx[k]); (void)hipFree(w->ray[k]); (void)hipFree(w->face[k]);
+        w->idx[k] = nullptr; w->ray[k] = nullptr; w->face[k] = nullptr;
+    }
+    (void)hipFree(w->redo); (void)hipFree(w->state);
+    w->redo = nullptr; w->state = nullptr; w->cap = 0;
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(hipMalloc(&w->idx[k], sizeof(int32_t) * n));
+        HIP_TRY(hipMalloc(&w->ray[k], sizeof(float) * 6 * n));
+        HIP_TRY(hipMalloc(&w->face[k], sizeof(int32_t) * n));
+    }
+    HIP_TRY(hipMalloc(&w->redo, sizeof(int32_t) * n));
+    HIP_TRY(hipMalloc(&w->state, (size_t)n));
+    w->cap = n;
+    return DRT_OK;
+}
+
+static int check_law(int max_bounces, int reflect) {
+    if (max_bounces < 2 || max_bounces > kMaxBounces) return fail(DRT_E_INVALID, "max_bounces = %d: must be 2 .. %d", max_bounces, kMaxBounces);
+    if (reflect != 0 && reflect != 1) return fail(DRT_E_INVALID, "reflect = %d: must be 0 (a TIR hit ends the path) or 1 (the ray is mirrored)", reflect);
+    return DRT_OK;
+}
+
+void paths_free(drt_scene* s) {
+    PathsWs* w = ws_of(s);
+    if (!w) return;
+    for (int k = 0; k < 2; ++k) { (void)hipFree(w->idx[k]); (void)hipFree(w->ray[k]); (void)hipFree(w->face[k]); }
+    (void)hipFree(w->redo); (void)hipFree(w->state); (void)hipFree(w->cnt); (void)hipFree(w->slow_stack);
+    delete w;
+    s->paths_ws = nullptr;
+}
+
+extern "C" {
+
+int drt_render_paths_forward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                             double ior_int, double ior_ext, int max_bounces, int reflect,
+                             double* d_out_ori, double* d_out_dir, uint8_t* d_mask, int32_t* d_tape, uint8_t* d_hits,
+                             int32_t* d_valid_idx, int64_t* d_n_valid, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+    if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rays == 0) {
+        if (d_n_valid) HIP_TRY(hipMemsetAsync(d_n_valid, 0, sizeof(int64_t), st));
+        return DRT_OK;
+    }
+    if (!d_verts || !d_origin || !d_dir || !d_out_ori || !d_out_dir || !d_mask || !d_tape || !d_hits || !d_valid_idx || !d_n_valid)
+        return fail(DRT_E_INVALID, "null pointer argument");
+    { int rc = ensure_paths_ws(s, n_rays, st); if (rc) return rc; }
+    { int rc = wait_build(s, st); if (rc) return rc; }
+    const PathsWs& w = *ws_of(s);
+    PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
+    pc.tc.slow_stack = w.slow_stack;
+    const unsigned n = (unsigned)n_rays;
+    const int gs = grid_for(n_rays, kPathBlock, 8 * s->n_cu);
+    HIP_TRY(hipMemsetAsync(w.cnt, 0, sizeof(unsigned) * kCntWords, st));
+    HIP_TRY(hipMemsetAsync(d_tape, 0xFF, sizeof(int32_t) * (size_t)max_bounces * (size_t)n_rays, st));
+    const RayList l0{w.idx[0], w.ray[0], w.face[0]}, l1{w.idx[1], w.ray[1], w.face[1]};
+    k_paths_start<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, d_origin, d_dir, n, d_out_ori, d_out_dir, w.state, d_hits, l0, w.cnt + kCntList);
+    for (int k = 0; k <= max_bounces; ++k) {
+        const RayList& in = (k & 1) ? l1 : l0;
+        const RayList& out = (k & 1) ? l0 : l1;
+        launch_trace_list(k < max_bounces ? kTraceClosest : kTraceAny, s->grid_path, st, pc.tc, in.ray, w.cnt + kCntList + k,
+                          TraceOut{in.face, nullptr, nullptr, nullptr}, w.redo, w.cnt + kCntRedo + k, w.cnt + kCntDone, s->refill_min, s->inner_min, nullptr);
+        k_paths_shade<<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect != 0, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1,
+                                                 d_out_ori, d_out_dir, w.state, d_hits, d_tape);
+    }
+    k_paths_finish<<<gs, kPathBlock, 0, st>>>(n, d_out_ori, d_out_dir, d_mask, w.state, d_hits, d_valid_idx, w.cnt + kCntValid);
+    k_paths_count<<<1, 64, 0, st>>>(w.cnt + kCntValid, d_n_valid);
+    HIP_TRY(hipGetLastError());
+    return DRT_OK;
+}
+
+int drt_render_paths_backward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                              double ior_int, double ior_ext, int max_bounces, int reflect,
+                              const int32_t* d_tape, const uint8_t* d_hits, const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                              const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+    if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
+    if (n_rays == 0 || (!d_grad_out_ori && !d_grad_out_dir)) return DRT_OK;
+    if (!d_verts || !d_origin || !d_dir || !d_tape || !d_hits || !d_valid_idx || !d_n_valid || !d_grad_verts) return fail(DRT_E_INVALID, "null pointer argument");
+    hipStream_t st = (hipStream_t)stream;
+    const PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
+    DET_LAUNCH(k_paths_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, n_rays, max_bounces, d_tape, d_hits, d_grad_out_ori, d_grad_out_dir, d_grad_verts,
+               d_valid_idx, d_n_valid);
+    HIP_TRY(hipGetLastError());
+    return DRT_OK;
+}
+
+}  // extern "C"

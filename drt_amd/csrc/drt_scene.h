@@ -1,6 +1,6 @@
 // drt_scene.h -- what the translation units of libdrt_hip.so share: the scene object behind drt_scene_t, launch
 // constants, error plumbing, the per-stage timer.  (drt_build.hip: LBVH build + checks; drt_trace.hip: B1 queries and
-// closest point; drt_pipeline.hip: the refraction pipeline, its backward and losses; drt_edges.hip: silhouette and
+// closest point; drt_pipeline.hip: the refraction pipeline, its backward and losses; drt_paths.hip: paths of up to K interactions; drt_edges.hip: silhouette and
 // smoothness branches; drt_api.hip: create / destroy / profiling.)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared.  Wave size is 64 throughout.
@@ -200,6 +200,7 @@ struct drt_scene {
     bool hit_seed = true;          // DRT_HIT_SEED=0: drt_render_seed's seeds are ignored (A/B measurement)
     bool use_raster = true;        // DRT_RASTER=0: every primary ray takes the BVH path (A/B measurement)
     bool built = false;
+    void* paths_ws = nullptr;      // ray lists and counters of drt_render_paths_forward (drt_paths.hip), allocated on first use
 };
 
 
@@ -212,6 +213,9 @@ int mega_blocks_per_cu();
 int ensure_raster(drt_scene* s, drt_scene::Sub& w, int64_t n_rays, int n_views, hipStream_t st);
 int launch_raster(drt_scene* s, drt_scene::Sub& w, hipStream_t st, const double* d_origin, const double* d_dir, int n_views, int iw, int ih,
                   ViewModel* trusted);
+
+// defined in drt_paths.hip
+void paths_free(drt_scene* s);
 
 // defined in drt_api.hip
 int ensure_slow_stack(drt_scene* s, hipStream_t st);

@@ -146,6 +146,56 @@ DRT_HD void eta_to_ior(const Bounce& b, double ior_int, double ior_ext, double g
     }
 }
 
+// The reflect continuation of a bounce whose TIR flag is set (paths of up to K interactions, drt_paths.h): the reference's Reflect
+// (DiffRender.py:31-33) with refract_ray's flipped normal, wr = -wo + (2 * dot(wo, n)) * n in that operation order (-wo is d itself and
+// dot(wo, n) is b.ci: the same three products summed in the same order), NOT renormalised, and the 1e-5 offset along wr -- the route the
+// reference leaves commented out at DiffRender.py:530.  `o` is the incoming origin bounce_forward was given.
+DRT_HD void bounce_reflect(const Bounce& b, d3 o, d3& new_o, d3& wr) {
+    wr = b.d + (2.0 * b.ci) * b.n;
+    new_o = (o + b.t * b.d) + 1e-5 * wr;
+}
+
+// Adjoint of bounce_reflect over bounce_forward's tape (torch's conventions, like bounce_backward).  In: g_new_o, g_wr.  Out: gradients of
+// the three vertices (accumulated into gv0/gv1/gv2) and of the incoming ray (g_o, g_d; set).  g_wr -> g_d, g_ci, g_n, then the normal and t
+// chains, statement for statement those of bounce_backward.
+DRT_HD void bounce_reflect_backward(const Bounce& b, d3 g_new_o, d3 g_wr, d3& gv0, d3& gv1, d3& gv2, d3& g_o, d3& g_d) {
+    // new_o = o + t*d + 1e-5*wr
+    g_o = g_new_o;
+    const double g_t = dot(g_new_o, b.d);
+    g_d = b.t * g_new_o;
+    const d3 G = g_wr + 1e-5 * g_new_o;
+    // wr = d + (2*ci)*n
+    g_d += G;
+    const double g_ci = 2.0 * dot(G, b.n);
+    d3 g_n = (2.0 * b.ci) * G;
+    // ci = n . wo = -(n . d)
+    g_n += (-g_ci) * b.d;
+    g_d += (-g_ci) * b.n;
+    // n = sg*n0 ; n0 = m/|m| ; m = e1 x e2
+    const d3 g_n0 = b.sg * g_n;
+    const d3 g_m = (g_n0 - dot(b.n0, g_n0) * b.n0) / b.len;
+    d3 g_e1 = cross(b.e2, g_m);
+    d3 g_e2 = cross(g_m, b.e1);
+    // t = (e2 . q) * inv
+    g_e2 += (g_t * b.inv) * b.q;
+    const d3 g_q = (g_t * b.inv) * b.e2;
+    const double g_inv = g_t * b.e2q;
+    // q = s x e1
+    const d3 g_s = cross(b.e1, g_q);
+    g_e1 += cross(g_q, b.s);
+    // s = o - v0
+    g_o += g_s;
+    // inv = 1/det ; det = e1 . p ; p = d x e2
+    const double g_det = -g_inv * b.inv * b.inv;
+    g_e1 += g_det * b.p;
+    const d3 g_p = g_det * b.e1;
+    g_d += cross(b.e2, g_p);
+    g_e2 += cross(g_p, b.d);
+    gv1 += g_e1;
+    gv2 += g_e2;
+    gv0 -= (g_s + g_e1) + g_e2;
+}
+
 // ray_loss term of one completed path (reference optim.py:100-106):
 //   target = normalize(screen_pixel - out_ori.detach()); diff = out_dir - target; loss += |diff|^2
 // Returns the term and d loss / d out_dir (no gradient reaches out_ori: it is detached).

@@ -596,6 +596,54 @@ class _RenderTransparent(torch.autograd.Function):
         return grad_v, g_in[0], g_in[1], None, g_ior[0], g_ior[1], None, None, None
 
 
+class _RenderPaths(torch.autograd.Function):
+    """render_paths (paths of up to K interactions, drt_render_paths_forward) as a function of the vertices."""
+
+    @staticmethod
+    def forward(ctx, vertices, origin, ray_dir, scene, ior, max_bounces, reflect):
+        v = _f64c(vertices.detach(), "vertices")
+        o = _f64c(origin.detach(), "origin")
+        d = _f64c(ray_dir.detach(), "ray_dir")
+        n = o.shape[0]
+        dev = o.device
+        # (the call writes every row of every output: dead values on the rows without a completed path, -1 through the whole tape first)
+        out_ori = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        out_dir = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        mask = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+        tape = torch.empty((max_bounces, n), dtype=torch.int32, device=dev)
+        hits = torch.empty(n, dtype=torch.uint8, device=dev)
+        valid_idx = torch.empty(n, dtype=torch.int32, device=dev)
+        n_valid = torch.zeros(1, dtype=torch.int64, device=dev)
+        if n:
+            with _on(dev):
+                _lib.check(_lib.lib().drt_render_paths_forward(
+                    scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), n, ior[0], ior[1], max_bounces, int(reflect),
+                    out_ori.data_ptr(), out_dir.data_ptr(), mask.data_ptr(), tape.data_ptr(), hits.data_ptr(),
+                    valid_idx.data_ptr(), n_valid.data_ptr(), _stream()))
+        ctx.scene, ctx.ior, ctx.law = scene, ior, (max_bounces, int(reflect))
+        ctx.save_for_backward(v, o, d, tape, hits, valid_idx, n_valid)
+        ctx.set_materialize_grads(False)
+        mask_b = mask.view(torch.bool)
+        ctx.mark_non_differentiable(mask_b)
+        scene.last_path_hits, scene.last_path_faces = hits, tape
+        return out_ori, out_dir, mask_b
+
+    @staticmethod
+    def backward(ctx, g_ori, g_dir, g_mask):
+        v, o, d, tape, hits, valid_idx, n_valid = ctx.saved_tensors
+        if o.shape[0] == 0 or (g_ori is None and g_dir is None):
+            return torch.zeros_like(v), None, None, None, None, None, None
+        grad_v = det.acc(v)
+        g_ori = None if g_ori is None else _f64c(g_ori, "grad_out_ori")
+        g_dir = None if g_dir is None else _f64c(g_dir, "grad_out_dir")
+        with _on(o.device):
+            _lib.check(_lib.lib().drt_render_paths_backward(
+                ctx.scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), o.shape[0], ctx.ior[0], ctx.ior[1], *ctx.law,
+                tape.data_ptr(), hits.data_ptr(), valid_idx.data_ptr(), n_valid.data_ptr(), _lib.ptr(g_ori), _lib.ptr(g_dir),
+                grad_v.data_ptr(), _stream()))
+        return det.value(grad_v, v), None, None, None, None, None, None
+
+
 class _RayLoss(torch.autograd.Function):
     """Loss_calculator.ray_loss (reference optim.py:100-106) in one pass over the rays."""
 
@@ -885,6 +933,25 @@ class Scene(StepwiseMixin):
         link.mask = weakref.ref(mask)
         link.out_ori = weakref.ref(out_ori)
         return out_ori, out_dir, mask
+
+    def render_paths(self, origin, ray_dir, max_bounces=4, tir="reflect"):
+        """Refraction paths of up to ``max_bounces`` (2..8) surface interactions: (out_ori, out_dir, mask) as render_transparent.
+        ``tir``: what a hit with total internal reflection does -- "drop" ends the path (the reference's rule), "reflect" mirrors the
+        ray (the reference's Reflect with refract_ray's flipped normal) and goes on.  A path is valid when it leaves the object after an
+        even, non-zero number of refractions within ``max_bounces`` interactions; ``render_paths(o, d, 2, "drop")`` is
+        ``render_transparent(o, d)`` bit for bit.  Differentiable w.r.t. ``self.vertices`` only: a gradient requested for ``origin``,
+        ``ray_dir`` or a tensor IOR raises NotImplementedError.  Afterwards ``self.last_path_hits`` (uint8 [N]: interactions of each valid
+        path, 0 elsewhere) and ``self.last_path_faces`` (int32 [K, N]: face per interaction, -1 past the end) describe the call.  Works
+        with ``ray_loss`` through its dense gradient route."""
+        if isinstance(max_bounces, bool) or int(max_bounces) != max_bounces or not 2 <= int(max_bounces) <= 8:
+            raise ValueError(f"max_bounces must be an integer in 2..8, got {max_bounces!r}")
+        if tir not in ("drop", "reflect"):
+            raise ValueError(f"tir must be 'drop' or 'reflect', got {tir!r}")
+        if _wants_input_grads(origin, ray_dir, intIOR, extIOR):
+            raise NotImplementedError("render_paths differentiates the vertices only: origin, ray_dir and the IORs must not require grad "
+                                      "(render_transparent has those gradients for the two-bounce path)")
+        ior = (_ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR"))
+        return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), tir == "reflect")
 
     def ray_loss_fused(self, origin, ray_dir, screen_pixel, valid):
         """ray_loss of this view without materialising out_ori/out_dir/mask.  The fused kernel differentiates the vertices only: when

@@ -35,6 +35,25 @@ HyperParams = {          # reference config.py:18-39
 }
 
 
+def path_law(hp):
+    """(max_bounces, tir) of ``HyperParams``, or None for the reference's path (both absent, or 2 and "drop"): what selects
+    ``Scene.render_paths`` instead of ``render_transparent`` in the drop-in loop.  Bad values raise ValueError here, before a pass starts."""
+    k, tir = hp.get("max_bounces", 2), hp.get("tir", "drop")
+    k = 2 if k is None else k
+    tir = "drop" if tir is None else tir
+    if isinstance(k, bool) or int(k) != k or not 2 <= int(k) <= 8:
+        raise ValueError(f"HyperParams['max_bounces'] must be an integer in 2..8, got {k!r}")
+    if tir not in ("drop", "reflect"):
+        raise ValueError(f"HyperParams['tir'] must be 'drop' or 'reflect', got {tir!r}")
+    return None if (int(k) == 2 and tir == "drop") else (int(k), tir)
+
+
+def _refuse_path_law(hp, who):
+    if path_law(hp) is not None:
+        raise NotImplementedError(f"HyperParams['max_bounces'] / ['tir'] other than 2 / 'drop' are not supported by {who}: use the drop-in "
+                                  "loop optimize(..., fused=False)")
+
+
 def loss_weights(hp, resy, mean_len):
     """(w_ray, w_vh, w_sm): the fixed scalings of reference optim.py:127-129."""
     return hp["ray_w"] * 217.5 / resy / resy, hp["vh_w"] * 217.5 / resy, hp["sm_w"] * mean_len / 10
@@ -89,6 +108,14 @@ class Loss_calculator:
         bind = getattr(self.data, "get_binding", None)       # a capture whose views are resident constants offers a handle per view (RayBinding)
         if bind is not None:
             origin, ray_dir = bind(self.scene, view_id), None
+        law = path_law(self.HyperParams)
+        if law is not None:                 # paths of up to K interactions (Scene.render_paths): dense outputs, ray_loss's dense gradient
+            if self.fused:
+                _refuse_path_law(self.HyperParams, "the fused terms")
+            if ray_dir is None:
+                origin, ray_dir = origin.origin, origin.ray_dir
+            exit_o, exit_d, exit_mask = self.scene.render_paths(origin, ray_dir, *law)
+            return Render.ray_loss(exit_o, exit_d, exit_mask, target, valid)
         if self.fused:
             return self.scene.ray_loss_fused(origin, ray_dir, target, valid)
         exit_o, exit_d, exit_mask = self.scene.render_transparent(origin, ray_dir)
@@ -204,6 +231,7 @@ class FusedIteration:
 
     def __init__(self, scene, data, HyperParams, lr, concurrent=True):
         from . import _lib
+        _refuse_path_law(HyperParams, "FusedIteration")
         self._lib = _lib
         self.scene, self.data, self.hp = scene, data, HyperParams
         self.ray_view = data.ray_view_generator()
@@ -333,6 +361,7 @@ class ShardedIteration:
     def __init__(self, scene, data, HyperParams, lr, views_per_step=1, concurrent=True):
         from . import _lib, det
         self._lib = _lib
+        _refuse_path_law(HyperParams, "ShardedIteration")
         self.scene, self.data, self.hp = scene, data, HyperParams
         self.k = int(views_per_step)
         if self.k < 1:
@@ -498,6 +527,7 @@ def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotrop
     if float(HyperParams.get("ior_lr", 0) or 0) > 0:
         raise NotImplementedError("HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by optimize_sharded: use the drop-in loop "
                                   "optimize(..., fused=False)")
+    _refuse_path_law(HyperParams, "optimize_sharded")
     say = output and rank == 0
     Render.intIOR = HyperParams["IOR"]
     Render.resy, Render.resx = data.resy, data.resx
@@ -565,11 +595,21 @@ def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=Fa
     ``HyperParams["ior_lr"] > 0`` (absent or 0: the reference's loop): the index of refraction is learned too -- a float64 leaf, starting
     at ``HyperParams["IOR"]``, in its own SGD param group with that learning rate (same momentum / Nesterov, not clamped by limit_hook),
     carried across passes and remeshes.  The drop-in loop only (``fused=False``); returns (scene, history, fitted IOR), and
-    ``Render.intIOR`` is the fitted float afterwards."""
+    ``Render.intIOR`` is the fitted float afterwards.
+
+    ``HyperParams["max_bounces"]`` (absent or 2) and ``HyperParams["tir"]`` (absent or "drop"): with any other value the refraction term
+    traces paths of up to that many interactions (``Scene.render_paths`` + ``Render.ray_loss``); the drop-in loop only, and not together
+    with ``ior_lr``."""
     ior_lr = float(HyperParams.get("ior_lr", 0) or 0)
     if ior_lr > 0 and fused:
         raise NotImplementedError("HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by the fused loop: use the drop-in loop "
                                   "optimize(..., fused=False)")
+    law = path_law(HyperParams)
+    if law is not None and fused:
+        _refuse_path_law(HyperParams, "the fused loop")
+    if law is not None and ior_lr > 0:
+        raise NotImplementedError("HyperParams['max_bounces'] / ['tir'] cannot be combined with ior_lr > 0: Scene.render_paths differentiates "
+                                  "the vertices only")
     if remesh == "isotropic":               # on the device (drt_amd.remesh_gpu); "isotropic-host": the sequential host version, its checker
         from .remesh_gpu import GpuMeshlabserver
         remesh = GpuMeshlabserver().remesh

@@ -30,7 +30,10 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
     """``views_per_step=None``: the single-process loop (optim.optimize).  An int, or "all" (one epoch of the refraction schedule per
     iteration), goes through optim.optimize_sharded on every rank of the default process group (one process without one).
     ``HyperParams["ior_lr"] > 0``: the IOR is fitted too (the drop-in loop, optim.optimize), starting at ``ior_start`` (default
-    ``HyperParams["IOR"]``, which is also the IOR the synthetic capture is traced with); the report gains ``ior``, the fitted value."""
+    ``HyperParams["IOR"]``, which is also the IOR the synthetic capture is traced with); the report gains ``ior``, the fitted value.
+    ``HyperParams["max_bounces"]`` / ``["tir"]`` other than 2 / "drop" (optim.path_law): the synthetic capture AND the fit trace paths of up
+    to that many interactions (the drop-in loop); the report echoes both."""
+    law = optim.path_law(HyperParams)
     if views_per_step is not None or torch.distributed.is_available() and torch.distributed.is_initialized():
         return run_sharded(HyperParams, data_path, result_path, capture, res, output, device, n_views, views_per_step or 1)
     name = HyperParams["name"]
@@ -46,8 +49,10 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
         Render.resx, Render.resy = resx, resy
         gt = scan_scene if scan_scene is not None else Render.Scene(views.displaced_ground_truth(scene.mesh, 0.5, 0), device)
         center, extent = views.mesh_frame(gt.mesh.vertices)
-        data = captured_data.SyntheticData(gt, center, extent, resx, resy, num_view=min(HyperParams["num_view"], n_views), n_total=n_views, name=name)
-    report = {"name": name, "resx": data.resx, "resy": data.resy, "views": data.n_total, "hull_faces": int(scene.faces.shape[0])}
+        data = captured_data.SyntheticData(gt, center, extent, resx, resy, num_view=min(HyperParams["num_view"], n_views), n_total=n_views, name=name,
+                                           path_law=law)
+    report = {"name": name, "resx": data.resx, "resy": data.resy, "views": data.n_total, "hull_faces": int(scene.faces.shape[0]),
+              "max_bounces": law[0] if law else 2, "tir": law[1] if law else "drop"}
     if scan_scene is not None:
         report["hull_to_scan"] = metrics.hausdorff(scene, scan_scene)
     t0 = time.time()
@@ -56,7 +61,7 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
         report["ior_start"] = start
         scene, history, report["ior"] = optim.optimize(scene, data, dict(HyperParams, IOR=start), output=output, fused=False)
     else:
-        scene, history = optim.optimize(scene, data, HyperParams, output=output, fused=fused)
+        scene, history = optim.optimize(scene, data, HyperParams, output=output, fused=fused and law is None)
     torch.cuda.synchronize()
     report["optimize_seconds"] = time.time() - t0
     report["iterations"] = HyperParams["Pass"] * HyperParams["Iters"]
@@ -147,6 +152,9 @@ def main(argv=None):
     ap.add_argument("--fit-ior", type=float, default=0.0, metavar="LR",
                     help="also learn the index of refraction with this SGD learning rate (implies --dropin); the report gains \"ior\"")
     ap.add_argument("--ior-start", type=float, default=None, help="with --fit-ior: the IOR the fit starts from (default: --ior)")
+    ap.add_argument("--max-bounces", type=int, default=2, metavar="K", help="surface interactions per light path, 2..8 (other than 2 / drop: "
+                    "Scene.render_paths for the synthetic capture and the fit; implies --dropin)")
+    ap.add_argument("--tir", choices=("drop", "reflect"), default="drop", help="what a hit with total internal reflection does to a path")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--views-per-step", type=_views_per_step, default=None, metavar="N|all",
                     help="refraction views per iteration (all: every view of the schedule once) on the multi-rank loop; "
@@ -157,14 +165,16 @@ def main(argv=None):
     hp = dict(optim.HyperParams, name=a.name, Pass=a.passes, Iters=a.iters, num_view=a.num_view, IOR=a.ior)
     if a.fit_ior > 0:
         hp["ior_lr"] = a.fit_ior
+    hp["max_bounces"], hp["tir"] = a.max_bounces, a.tir
+    law = optim.path_law(hp)
     from . import dist as ddist
     if a.views_per_step is None and ddist.env_world()[2] == 1:
         _, report = run(hp, a.data_path, a.result_path, a.capture, a.res, fused=not (a.dropin or a.fit_ior > 0), n_views=a.views,
                         ior_start=a.ior_start)
         print(json.dumps(report))
         return
-    if a.dropin or a.fit_ior > 0:
-        raise SystemExit("--dropin / --fit-ior have no multi-rank form: the sharded loop runs the one-pass terms")
+    if a.dropin or a.fit_ior > 0 or law is not None:
+        raise SystemExit("--dropin / --fit-ior / --max-bounces / --tir have no multi-rank form: the sharded loop runs the one-pass terms")
     _, local_rank, world = ddist.init()
     device = local_rank % torch.cuda.device_count()
     torch.cuda.set_device(device)

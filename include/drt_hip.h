@@ -32,7 +32,7 @@ extern "C" {
 typedef struct drt_scene drt_scene_t;
 
 const char* drt_last_error(void);
-int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize */
+int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -178,6 +178,39 @@ int drt_render_backward_inputs(drt_scene_t* s, const double* d_verts, const doub
                                const double* d_grad_out_ori, const double* d_grad_out_dir,
                                double* d_grad_verts, double* d_grad_origin, double* d_grad_dir,
                                double* d_grad_ior, void* stream);
+
+/* ---- refraction paths of up to K surface interactions, with optional internal reflection (opt-in; drt_render_forward is the
+ * reference's path and is not altered by this) ---------------------------------------------------------------------------------
+ * max_bounces = K, 2 <= K <= 8: at most K surface interactions.  reflect: 0 = a hit with total internal reflection ends the path
+ * (as the reference does), 1 = the ray continues mirrored: wr = -wo + (2 dot(wo, n)) n with refract_ray's flipped normal (the
+ * reference's Reflect, DiffRender.py:31-33; not renormalised), origin (o + t d) + 1e-5 wr, and counts no refraction.
+ * A camera ray repeats { closest hit (the tracer contract of drt_intersect; once K interactions are used up the any-hit form);
+ * miss: the path ends, valid iff it has made an even, non-zero number of refractions; hit with K interactions used up: invalid;
+ * hit: JIT_Dintersect + refract_ray on the float64 ray, as in drt_render_forward }.  K = 2, reflect = 0 is drt_render_forward's
+ * path: the same outputs bit for bit.  Geometry only: no Fresnel weights (the reference drops R too).
+ * In : as drt_render_forward.
+ * Out: out_ori, out_dir float64 [N,3] (zeros where the path is invalid), mask uint8 [N,3];
+ *      d_tape int32 [K,N]: the face of interaction k of ray i at [k * N + i], -1 where the ray had no k-th interaction (the
+ *      interactions of a path that ends invalid stay recorded); d_hits uint8 [N]: the number of interactions of a valid path, 0
+ *      on invalid rows; d_valid_idx int32 [N] / *d_n_valid (int64, device): the rays with mask = 1, in ray order.
+ * All launches go to `stream`, list sizes stay on the device: the call can be captured in a graph once an eager call of at least
+ * this many rays has allocated the scene's ray lists.  A K outside 2..8 is DRT_E_INVALID. */
+int drt_render_paths_forward(drt_scene_t* s, const double* d_verts, const double* d_origin,
+                             const double* d_dir, int64_t n_rays, double ior_int, double ior_ext,
+                             int max_bounces, int reflect,
+                             double* d_out_ori, double* d_out_dir, uint8_t* d_mask,
+                             int32_t* d_tape, uint8_t* d_hits,
+                             int32_t* d_valid_idx, int64_t* d_n_valid, void* stream);
+/* Adjoint of drt_render_paths_forward w.r.t. the vertices: d_grad_verts float64 [V,3] += ... (or accumulator cells in deterministic
+ * mode, like drt_render_backward).  Every listed path is recomputed from its camera ray and its column of the tape; the total-internal-
+ * reflection flags are recomputed too (the same bits).  Either incoming gradient may be NULL (= zeros). */
+int drt_render_paths_backward(drt_scene_t* s, const double* d_verts, const double* d_origin,
+                              const double* d_dir, int64_t n_rays, double ior_int, double ior_ext,
+                              int max_bounces, int reflect,
+                              const int32_t* d_tape, const uint8_t* d_hits,
+                              const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                              const double* d_grad_out_ori, const double* d_grad_out_dir,
+                              double* d_grad_verts, void* stream);
 
 /* ---- Loss_calculator.ray_loss, optim.py:91-108 ------------------------------------------
  * loss = sum over rays with valid & mask of |out_dir - normalize(screen_pixel - out_ori)|^2.
