@@ -13,6 +13,7 @@
 //
 //   trace_path_k              forward; records the face of every interaction and their number
 //   path_recompute_backward_k recomputes the path from the camera ray and that face tape, reverses it
+//   path_loss_backward_k      the ray_loss term of a completed path and its adjoint in one go (the one-pass form)
 // Plain C++ (also compiled by tests/hostsim); the gradient sink is a functor as in drt_path.h.
 #pragma once
 #include "drt_path.h"
@@ -94,6 +95,17 @@ DRT_HD void path_recompute_backward_k(const PathCtx& c, d3 o, d3 d, const int32_
         add(vid[0], ga); add(vid[1], gb); add(vid[2], gc);
         g_o = g_o_in; g_d = g_d_in;
     }
+}
+
+// The one-pass form of a completed path: its ray_loss term (ray_loss_term, drt_shade.h) on the exit ray the forward left behind, and the
+// adjoint of that term w.r.t. the vertices with a unit seed (no gradient reaches the exit origin: the loss detaches it).  Returns the term.
+template <typename Add>
+DRT_HD double path_loss_backward_k(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 exit_o, d3 exit_d,
+                                   d3 screen_pixel, Add add) {
+    d3 g_dir;
+    const double term = ray_loss_term(exit_o, exit_d, screen_pixel, g_dir);
+    path_recompute_backward_k(c, o, d, faces, face_stride, n_hits, d3{0.0, 0.0, 0.0}, g_dir, add);
+    return term;
 }
 
 }  // namespace drt

@@ -11,6 +11,14 @@
 // the exit ray of a completed path is in place when the path ends.  Every list size stays on the device, grids are sized from N, and all
 // launches go to the caller's stream: the call can be captured in a hipGraph.  k_trace is the two-bounce pipeline's (launch_trace_list,
 // instantiated in drt_trace.hip); the staged list append and the gradient sink are shared with it (drt_pathsink.h).
+//
+// The one-pass form (drt_render_paths_ray_loss_fused: loss + vertex gradient of one view, nothing dense written) runs the same loop with
+// the ray in flight, the face tape and the hit counts in the scene's workspace instead of caller tensors:
+//   k_paths_start_fused all rays : as k_paths_start, but a ray without a target is no candidate; one state byte per ray, nothing else
+//   k_trace / k_paths_shade      : unchanged (they are handed the workspace rows)
+//   k_paths_collect     all rays : reads the state byte, completed paths -> index list
+//   k_paths_loss_bwd    that list: ray_loss term on the parked exit ray + adjoint (path_loss_backward_k), LossAcc / PathSink
+// The tape needs no -1 preset there: hits[i], written with the last face of a path, bounds what the last kernel reads.
 #include "drt_device.h"
 #include "drt_trace_kernel.h"
 #include "drt_pathsink.h"
@@ -32,6 +40,11 @@ struct PathsWs {
     uint8_t* state = nullptr;
     unsigned* cnt = nullptr;
     int32_t* slow_stack = nullptr;       // overflow area of k_trace's second pass: [kPathBlock * kStackSlowDev]
+    // the one-pass form only (ensure_paths_fused_ws): float64 ray in flight [2][fused_cap,3], face tape [kMaxBounces, fused_cap], hit counts
+    int64_t fused_cap = 0;
+    double* park = nullptr;
+    int32_t* tape = nullptr;
+    uint8_t* hits = nullptr;
 };
 
 // each block takes one contiguous run of [0, n), so that what it appends stays in input order
@@ -61,6 +74,34 @@ __global__ void __launch_bounds__(kPathBlock) k_paths_start(const Node4Q* __rest
             state[i] = 0;
             hits[i] = 0;
             if (cand) { store_d3(out_ori, i, o); store_d3(out_dir, i, d); }
+        }
+        stage_push(stage, cand, (int32_t)i, o32, d32, out, count);
+    }
+    stage_flush(stage, out, count);
+}
+
+// k_paths_start of the one-pass form: a ray without a target cannot contribute and is never traced; the float64 ray parks in the workspace;
+// per camera ray one state byte is written and origin / dir / valid are read once.
+__global__ void __launch_bounds__(kPathBlock) k_paths_start_fused(const Node4Q* __restrict__ nodes, int n_tris, const double* __restrict__ origin,
+                                                                   const double* __restrict__ dir, const uint8_t* __restrict__ valid, unsigned n,
+                                                                   double* __restrict__ park_ori, double* __restrict__ park_dir,
+                                                                   uint8_t* __restrict__ state, RayList out, unsigned* count) {
+    __shared__ StageMem stage;
+    stage_init(stage);
+    unsigned first, last;
+    block_run(n, first, last);
+    for (unsigned base = first; base < last; base += kPathBlock) {
+        const unsigned i = base + threadIdx.x;
+        bool cand = false;
+        f3 o32{0.f, 0.f, 0.f}, d32{0.f, 0.f, 1.f};
+        if (i < n) {
+            state[i] = 0;
+            if (n_tris > 0 && valid[i]) {
+                const d3 o = load_d3(origin, i), d = load_d3(dir, i);
+                o32 = to_f32(o); d32 = to_f32(d);
+                cand = hits_top_boxes(nodes, o32, d32);
+                if (cand) { store_d3(park_ori, i, o); store_d3(park_dir, i, d); }
+            }
         }
         stage_push(stage, cand, (int32_t)i, o32, d32, out, count);
     }
@@ -169,15 +210,63 @@ __global__ void __launch_bounds__(256) k_paths_bwd(PathCtx c, const double* __re
     }
 }
 
+// The one-pass form: the rays whose path completed (state byte) -> index list; order does not matter to the sums.
+__global__ void __launch_bounds__(kPathBlock) k_paths_collect(unsigned n, const uint8_t* __restrict__ state, int32_t* __restrict__ done_idx, unsigned* n_done) {
+    __shared__ StageMem stage;
+    stage_init(stage);
+    const RayList out{done_idx, nullptr, nullptr};              // index-only list
+    unsigned first, last;
+    block_run(n, first, last);
+    for (unsigned base = first; base < last; base += kPathBlock) {
+        const unsigned i = base + threadIdx.x;
+        const bool keep = i < n && (state[i] & kPathDone) != 0;
+        stage_push(stage, keep, (int32_t)i, f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 0.f}, out, n_done);
+    }
+    stage_flush(stage, out, n_done);
+}
+
+// Loss AND vertex gradient (unit seed) over the list of completed paths: the ray_loss term on the exit ray the forward parked -- the bits a
+// recompute would give -- then recompute, reverse, scatter as k_paths_bwd does (same table fill).  Every listed ray has a target:
+// k_paths_start_fused admits no other.
+template <bool DET>
+__global__ void __launch_bounds__(256) k_paths_loss_bwd(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir,
+                                                        const double* __restrict__ screen_pixel, int64_t n_rays, int max_bounces,
+                                                        const double* __restrict__ park_ori, const double* __restrict__ park_dir,
+                                                        const int32_t* __restrict__ tape, const uint8_t* __restrict__ hits,
+                                                        const int32_t* __restrict__ list, const unsigned* __restrict__ n_list, double* loss,
+                                                        double* grad_verts, unsigned long long* n_valid) {
+    __shared__ int32_t hkeys[kHashSize];
+    __shared__ double hsums[3 * kHashSize];
+    int64_t n = *n_list;
+    if (n > n_rays) n = n_rays;
+    const PathSink<DET> add{hkeys, hsums, grad_verts};
+    LossAcc<DET> acc;
+    unsigned cnt = 0;
+    for (int64_t base = blockIdx.x * (int64_t)kPathsBwdBatch; base < n; base += (int64_t)gridDim.x * kPathsBwdBatch) {
+        add.clear();
+        const int64_t end = base + kPathsBwdBatch < n ? base + kPathsBwdBatch : n;
+        for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
+            const int64_t i = list[k];
+            if (i < 0 || i >= n_rays) continue;
+            acc.add(path_loss_backward_k(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
+                                         load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), add));
+            ++cnt;
+        }
+        add.flush();
+    }
+    acc.flush(loss);
+    if (n_valid && cnt) atomicAdd(n_valid, (unsigned long long)cnt);
+}
+
 static PathsWs* ws_of(drt_scene* s) { return static_cast<PathsWs*>(s->paths_ws); }
 
-static int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st) {
+static int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st, const char* who) {
     PathsWs* w = ws_of(s);
     if (w && n <= w->cap) return DRT_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(DRT_E_INVALID, "drt_render_paths_forward: the first call of this size allocates its ray lists and cannot run inside a stream "
-                                   "capture: issue one such call eagerly before capturing");
+        return fail(DRT_E_INVALID, "%s: the first call of this size allocates its ray lists and cannot run inside a stream "
+                                   "capture: issue one such call eagerly before capturing", who);
     if (!w) {
         w = new (std::nothrow) PathsWs();
         if (!w) return fail(DRT_E_NOMEM, "host allocation failed");
@@ -202,6 +291,23 @@ static int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st) {
     return DRT_OK;
 }
 
+// the workspace rows of the one-pass form, grown like the ray lists
+static int ensure_paths_fused_ws(drt_scene* s, int64_t n, hipStream_t st) {
+    PathsWs* w = ws_of(s);
+    if (n <= w->fused_cap) return DRT_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(DRT_E_INVALID, "drt_render_paths_ray_loss_fused: the first call of this size allocates its parked rays and face tape and cannot "
+                                   "run inside a stream capture: issue one such call eagerly before capturing");
+    (void)hipFree(w->park); (void)hipFree(w->tape); (void)hipFree(w->hits);
+    w->park = nullptr; w->tape = nullptr; w->hits = nullptr; w->fused_cap = 0;
+    HIP_TRY(hipMalloc(&w->park, sizeof(double) * 6 * (size_t)n));
+    HIP_TRY(hipMalloc(&w->tape, sizeof(int32_t) * (size_t)kMaxBounces * (size_t)n));
+    HIP_TRY(hipMalloc(&w->hits, (size_t)n));
+    w->fused_cap = n;
+    return DRT_OK;
+}
+
 static int check_law(int max_bounces, int reflect) {
     if (max_bounces < 2 || max_bounces > kMaxBounces) return fail(DRT_E_INVALID, "max_bounces = %d: must be 2 .. %d", max_bounces, kMaxBounces);
     if (reflect != 0 && reflect != 1) return fail(DRT_E_INVALID, "reflect = %d: must be 0 (a TIR hit ends the path) or 1 (the ray is mirrored)", reflect);
@@ -213,8 +319,24 @@ void paths_free(drt_scene* s) {
     if (!w) return;
     for (int k = 0; k < 2; ++k) { (void)hipFree(w->idx[k]); (void)hipFree(w->ray[k]); (void)hipFree(w->face[k]); }
     (void)hipFree(w->redo); (void)hipFree(w->state); (void)hipFree(w->cnt); (void)hipFree(w->slow_stack);
+    (void)hipFree(w->park); (void)hipFree(w->tape); (void)hipFree(w->hits);
     delete w;
     s->paths_ws = nullptr;
+}
+
+// The wavefront loop behind list 0: trace list k, shade it into list k + 1 (the other ping-pong buffer), K + 1 times.  ray_ori / ray_dir
+// [N,3]: the rows the float64 ray in flight parks in; hits [N], tape [K,N]: written per list item.
+static void trace_lists(drt_scene* s, const PathsWs& w, const PathCtx& pc, hipStream_t st, int gs, int64_t n_rays, int max_bounces, int reflect,
+                        double* ray_ori, double* ray_dir, uint8_t* hits, int32_t* tape) {
+    const RayList l0{w.idx[0], w.ray[0], w.face[0]}, l1{w.idx[1], w.ray[1], w.face[1]};
+    for (int k = 0; k <= max_bounces; ++k) {
+        const RayList& in = (k & 1) ? l1 : l0;
+        const RayList& out = (k & 1) ? l0 : l1;
+        launch_trace_list(k < max_bounces ? kTraceClosest : kTraceAny, s->grid_path, st, pc.tc, in.ray, w.cnt + kCntList + k,
+                          TraceOut{in.face, nullptr, nullptr, nullptr}, w.redo, w.cnt + kCntRedo + k, w.cnt + kCntDone, s->refill_min, s->inner_min, nullptr);
+        k_paths_shade<<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect != 0, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1,
+                                                 ray_ori, ray_dir, w.state, hits, tape);
+    }
 }
 
 extern "C" {
@@ -233,7 +355,7 @@ int drt_render_paths_forward(drt_scene_t* s, const double* d_verts, const double
     }
     if (!d_verts || !d_origin || !d_dir || !d_out_ori || !d_out_dir || !d_mask || !d_tape || !d_hits || !d_valid_idx || !d_n_valid)
         return fail(DRT_E_INVALID, "null pointer argument");
-    { int rc = ensure_paths_ws(s, n_rays, st); if (rc) return rc; }
+    { int rc = ensure_paths_ws(s, n_rays, st, "drt_render_paths_forward"); if (rc) return rc; }
     { int rc = wait_build(s, st); if (rc) return rc; }
     const PathsWs& w = *ws_of(s);
     PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
@@ -242,16 +364,9 @@ int drt_render_paths_forward(drt_scene_t* s, const double* d_verts, const double
     const int gs = grid_for(n_rays, kPathBlock, 8 * s->n_cu);
     HIP_TRY(hipMemsetAsync(w.cnt, 0, sizeof(unsigned) * kCntWords, st));
     HIP_TRY(hipMemsetAsync(d_tape, 0xFF, sizeof(int32_t) * (size_t)max_bounces * (size_t)n_rays, st));
-    const RayList l0{w.idx[0], w.ray[0], w.face[0]}, l1{w.idx[1], w.ray[1], w.face[1]};
+    const RayList l0{w.idx[0], w.ray[0], w.face[0]};
     k_paths_start<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, d_origin, d_dir, n, d_out_ori, d_out_dir, w.state, d_hits, l0, w.cnt + kCntList);
-    for (int k = 0; k <= max_bounces; ++k) {
-        const RayList& in = (k & 1) ? l1 : l0;
-        const RayList& out = (k & 1) ? l0 : l1;
-        launch_trace_list(k < max_bounces ? kTraceClosest : kTraceAny, s->grid_path, st, pc.tc, in.ray, w.cnt + kCntList + k,
-                          TraceOut{in.face, nullptr, nullptr, nullptr}, w.redo, w.cnt + kCntRedo + k, w.cnt + kCntDone, s->refill_min, s->inner_min, nullptr);
-        k_paths_shade<<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect != 0, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1,
-                                                 d_out_ori, d_out_dir, w.state, d_hits, d_tape);
-    }
+    trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, d_out_ori, d_out_dir, d_hits, d_tape);
     k_paths_finish<<<gs, kPathBlock, 0, st>>>(n, d_out_ori, d_out_dir, d_mask, w.state, d_hits, d_valid_idx, w.cnt + kCntValid);
     k_paths_count<<<1, 64, 0, st>>>(w.cnt + kCntValid, d_n_valid);
     HIP_TRY(hipGetLastError());
@@ -271,6 +386,37 @@ int drt_render_paths_backward(drt_scene_t* s, const double* d_verts, const doubl
     const PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
     DET_LAUNCH(k_paths_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, n_rays, max_bounces, d_tape, d_hits, d_grad_out_ori, d_grad_out_dir, d_grad_verts,
                d_valid_idx, d_n_valid);
+    HIP_TRY(hipGetLastError());
+    return DRT_OK;
+}
+
+int drt_render_paths_ray_loss_fused(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir,
+                                    const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays, double ior_int, double ior_ext,
+                                    int max_bounces, int reflect, double* d_loss, double* d_grad_verts, int64_t* d_n_valid, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+    if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
+    if (n_rays == 0) return DRT_OK;
+    if (!d_verts || !d_origin || !d_dir || !d_screen_pixel || !d_valid || !d_loss || !d_grad_verts) return fail(DRT_E_INVALID, "null pointer argument");
+    hipStream_t st = (hipStream_t)stream;
+    { int rc = ensure_paths_ws(s, n_rays, st, "drt_render_paths_ray_loss_fused"); if (rc) return rc; }
+    { int rc = ensure_paths_fused_ws(s, n_rays, st); if (rc) return rc; }
+    { int rc = wait_build(s, st); if (rc) return rc; }
+    const PathsWs& w = *ws_of(s);
+    PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
+    pc.tc.slow_stack = w.slow_stack;
+    const unsigned n = (unsigned)n_rays;
+    const int gs = grid_for(n_rays, kPathBlock, 8 * s->n_cu);
+    double* const park_ori = w.park;
+    double* const park_dir = w.park + 3 * w.fused_cap;
+    HIP_TRY(hipMemsetAsync(w.cnt, 0, sizeof(unsigned) * kCntWords, st));
+    const RayList l0{w.idx[0], w.ray[0], w.face[0]};
+    k_paths_start_fused<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, d_origin, d_dir, d_valid, n, park_ori, park_dir, w.state, l0, w.cnt + kCntList);
+    trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, park_ori, park_dir, w.hits, w.tape);
+    int32_t* const done = w.idx[0];          // (both ping-pong lists are free once the loop has ended)
+    k_paths_collect<<<gs, kPathBlock, 0, st>>>(n, w.state, done, w.cnt + kCntValid);
+    DET_LAUNCH(k_paths_loss_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_screen_pixel, n_rays, max_bounces, park_ori, park_dir, w.tape, w.hits,
+               done, w.cnt + kCntValid, d_loss, d_grad_verts, reinterpret_cast<unsigned long long*>(d_n_valid));
     HIP_TRY(hipGetLastError());
     return DRT_OK;
 }

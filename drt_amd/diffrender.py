@@ -40,7 +40,8 @@ def cache_report(reset=False):
     calls that read and verified every ray, `grid_off` calls without whole-image hints / with GRID_CACHE off, `grid_unattachable` ray tensors
     that take no attributes), output recycling (`recycle_take` calls that rendered into pooled buffers; `recycle_miss_held` the pool had an
     entry of that size but the caller still holds, or wrote, its outputs; `recycle_miss_empty` nothing pooled yet; `recycle_off_capture` inside
-    a graph capture; `recycle_off_small` below RECYCLE_MIN_RAYS), hit seeds (`seed_armed`), and the switches in force."""
+    a graph capture; `recycle_off_small` below RECYCLE_MIN_RAYS), hit seeds (`seed_armed`), the one-pass K-interaction term (`paths_fused_calls`), and the
+    switches in force."""
     out = dict(_stats)
     out["switches"] = {"GRID_CACHE": GRID_CACHE, "RECYCLE_OUTPUTS": RECYCLE_OUTPUTS, "storage_use_count_available": hasattr(torch._C, "_storage_Use_Count"),
                        "RECYCLE_MIN_RAYS": RECYCLE_MIN_RAYS, "PREFILL_NEXT": PREFILL_NEXT, "HIT_SEED": HIT_SEED, "GRID_CANARY": GRID_CANARY}
@@ -759,6 +760,37 @@ class _RenderRayLossFused(torch.autograd.Function):
         return grad_v * g_loss, None, None, None, None, None, None, None, None
 
 
+class _PathsRayLossFused(torch.autograd.Function):
+    """render_paths + ray_loss + d/d vertices of one view in ONE call (drt_render_paths_ray_loss_fused: nothing dense written)."""
+
+    @staticmethod
+    def forward(ctx, vertices, origin, ray_dir, screen_pixel, valid, scene, ior, max_bounces, reflect):
+        v = _f64c(vertices.detach(), "vertices")
+        o = _f64c(origin, "origin")
+        d = _f64c(ray_dir, "ray_dir")
+        sp = _f64c(screen_pixel, "screen_pixel")
+        va = _flag_bytes(valid, "valid", o.shape[0])
+        loss = det.scalar(o.device)
+        grad_v = det.acc(v)
+        count = torch.zeros((), dtype=torch.int64, device=o.device)
+        with _on(o.device):
+            _lib.check(_lib.lib().drt_render_paths_ray_loss_fused(
+                scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), o.shape[0],
+                ior[0], ior[1], max_bounces, int(reflect), loss.data_ptr(), grad_v.data_ptr(), count.data_ptr(), _stream()))
+        scene.last_path_count = count
+        ctx.wide = grad_v if grad_v.dtype == torch.int64 else None
+        ctx.save_for_backward(det.value(grad_v, v))
+        return det.value(loss)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        (grad_v,) = ctx.saved_tensors
+        if det.SINK is not None and ctx.wide is not None:
+            det.SINK.append((ctx.wide, g_loss))
+            return None, None, None, None, None, None, None, None, None
+        return grad_v * g_loss, None, None, None, None, None, None, None, None
+
+
 def ray_loss(out_ori, out_dir, mask, screen_pixel, valid):
     """sum over valid & mask rays of |out_dir - normalize(screen_pixel - out_ori.detach())|^2."""
     link = getattr(out_dir, "_drt_link", None) if SPARSE_LOSS_GRAD else None
@@ -943,15 +975,33 @@ class Scene(StepwiseMixin):
         ``ray_dir`` or a tensor IOR raises NotImplementedError.  Afterwards ``self.last_path_hits`` (uint8 [N]: interactions of each valid
         path, 0 elsewhere) and ``self.last_path_faces`` (int32 [K, N]: face per interaction, -1 past the end) describe the call.  Works
         with ``ray_loss`` through its dense gradient route."""
+        ior = self._check_paths_call("render_paths", origin, ray_dir, max_bounces, tir)
+        return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), tir == "reflect")
+
+    @staticmethod
+    def _check_paths_call(who, origin, ray_dir, max_bounces, tir):
+        """The argument checks of the K-interaction calls; returns the (intIOR, extIOR) floats."""
         if isinstance(max_bounces, bool) or int(max_bounces) != max_bounces or not 2 <= int(max_bounces) <= 8:
             raise ValueError(f"max_bounces must be an integer in 2..8, got {max_bounces!r}")
         if tir not in ("drop", "reflect"):
             raise ValueError(f"tir must be 'drop' or 'reflect', got {tir!r}")
         if _wants_input_grads(origin, ray_dir, intIOR, extIOR):
-            raise NotImplementedError("render_paths differentiates the vertices only: origin, ray_dir and the IORs must not require grad "
+            raise NotImplementedError(f"{who} differentiates the vertices only: origin, ray_dir and the IORs must not require grad "
                                       "(render_transparent has those gradients for the two-bounce path)")
-        ior = (_ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR"))
-        return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), tir == "reflect")
+        return _ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR")
+
+    def paths_ray_loss_fused(self, origin, ray_dir, screen_pixel, valid, max_bounces=4, tir="reflect"):
+        """ray_loss of this view under the law of ``render_paths`` -- ``ray_loss(*render_paths(origin, ray_dir, max_bounces, tir),
+        screen_pixel, valid)`` -- in one call that writes no dense output (drt_render_paths_ray_loss_fused): the loss as a scalar, its
+        vertex gradient computed alongside with a unit seed and scaled in the backward pass.  Differentiable w.r.t. ``self.vertices``
+        only, like ``render_paths``.  ``origin`` may be a RayBinding: its rays are used, nothing else of it (no grid verdicts, seeds or
+        recycled outputs exist for this law).  Afterwards ``self.last_path_count`` is the number of contributing rays (0-dim int64 tensor
+        on the device; reading it synchronises, producing it does not)."""
+        if isinstance(origin, RayBinding):
+            origin, ray_dir = origin.origin, origin.ray_dir
+        ior = self._check_paths_call("paths_ray_loss_fused", origin, ray_dir, max_bounces, tir)
+        _stats["paths_fused_calls"] += 1
+        return _PathsRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, int(max_bounces), tir == "reflect")
 
     def ray_loss_fused(self, origin, ray_dir, screen_pixel, valid):
         """ray_loss of this view without materialising out_ori/out_dir/mask.  The fused kernel differentiates the vertices only: when

@@ -48,10 +48,36 @@ def path_law(hp):
     return None if (int(k) == 2 and tir == "drop") else (int(k), tir)
 
 
+_law_of = path_law          # (the loops take a keyword of that name)
+
+
 def _refuse_path_law(hp, who):
     if path_law(hp) is not None:
         raise NotImplementedError(f"HyperParams['max_bounces'] / ['tir'] other than 2 / 'drop' are not supported by {who}: use the drop-in "
                                   "loop optimize(..., fused=False)")
+
+
+def path_law_keyword(law, hp, who):
+    """The ``path_law=(max_bounces, tir)`` keyword of the loops, normalised by the rules of ``path_law``: None when absent or (2, "drop")
+    -- today's kernels -- else (int K, tir); bad values raise ValueError.  The keyword selects the ONE-PASS form of the law
+    (``Scene.paths_ray_loss_fused`` / drt_render_paths_ray_loss_fused) where the caller runs the one-pass terms; the ``HyperParams``
+    keys keep meaning the drop-in route.  Like ``Scene.render_paths`` the law differentiates the vertices only: not with ``ior_lr > 0``.
+    Looks at nothing but its arguments."""
+    if law is None:
+        return None
+    try:
+        k, tir = law
+    except (TypeError, ValueError):
+        raise ValueError(f"path_law must be None or (max_bounces, tir), got {law!r}") from None
+    law = path_law({"max_bounces": k, "tir": tir})
+    if law is None:
+        return None
+    if float(hp.get("ior_lr", 0) or 0) > 0:
+        raise NotImplementedError(f"path_law cannot be combined with HyperParams['ior_lr'] > 0 in {who}: the K-interaction law "
+                                  "differentiates the vertices only")
+    if path_law(hp) is not None:
+        raise ValueError("the path law was given twice: HyperParams['max_bounces'] / ['tir'] and the path_law keyword")
+    return law
 
 
 def loss_weights(hp, resy, mean_len):
@@ -67,7 +93,8 @@ class Loss_calculator:
 
     N_SILHOUETTE_VIEWS = 8          # the reference loops over np.arange(0, 72, 9)
 
-    def __init__(self, scene, data, HyperParams, fused=False):
+    def __init__(self, scene, data, HyperParams, fused=False, path_law=None):
+        self.law = path_law_keyword(path_law, HyperParams, "Loss_calculator")       # (first: bad values raise before anything is touched)
         self.scene, self.data, self.HyperParams, self.fused = scene, data, HyperParams, fused
         self.ray_view = data.ray_view_generator()
         self.silh_view = data.silh_view_generator()
@@ -115,6 +142,13 @@ class Loss_calculator:
             if ray_dir is None:
                 origin, ray_dir = origin.origin, origin.ray_dir
             exit_o, exit_d, exit_mask = self.scene.render_paths(origin, ray_dir, *law)
+            return Render.ray_loss(exit_o, exit_d, exit_mask, target, valid)
+        if self.law is not None:            # the path_law keyword: the one-pass form with the one-pass terms, else the route above
+            if self.fused:
+                return self.scene.paths_ray_loss_fused(origin, ray_dir, target, valid, *self.law)
+            if ray_dir is None:
+                origin, ray_dir = origin.origin, origin.ray_dir
+            exit_o, exit_d, exit_mask = self.scene.render_paths(origin, ray_dir, *self.law)
             return Render.ray_loss(exit_o, exit_d, exit_mask, target, valid)
         if self.fused:
             return self.scene.ray_loss_fused(origin, ray_dir, target, valid)
@@ -225,13 +259,15 @@ class FusedIteration:
     (0.7 ms) exceeds the GPU time of the whole iteration at the reference's size (one 960x1280 refraction view, 8 silhouette views).
     Here the three entry points write into one [3, V, 3] buffer, the weighted sum is one matrix product and the update is the
     one-kernel limit_hook + SGD(nesterov): the same kernels, inputs and arithmetic, ~10 host calls.  The silhouette and smoothness
-    terms run on a side stream beside the refraction term.  Same view schedule generators as Loss_calculator."""
+    terms run on a side stream beside the refraction term.  Same view schedule generators as Loss_calculator.
+    ``path_law=(K, tir)``: the refraction term is drt_render_paths_ray_loss_fused (paths of up to K interactions, one pass)."""
 
     N_SILHOUETTE_VIEWS = 8
 
-    def __init__(self, scene, data, HyperParams, lr, concurrent=True):
+    def __init__(self, scene, data, HyperParams, lr, concurrent=True, path_law=None):
         from . import _lib
         _refuse_path_law(HyperParams, "FusedIteration")
+        self.law = path_law_keyword(path_law, HyperParams, "FusedIteration")
         self._lib = _lib
         self.scene, self.data, self.hp = scene, data, HyperParams
         self.ray_view = data.ray_view_generator()
@@ -295,11 +331,16 @@ class FusedIteration:
                 n = origin.shape[0]
                 o, d, sp = R._f64c(origin, "origin"), R._f64c(ray_dir, "ray_dir"), R._f64c(target, "screen_pixel")
                 va = R._flag_bytes(valid, "valid", n)
-                grid = R._grid_cache(origin, ray_dir, n, *R._tile_hint(n)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
-                R._arm_seed(h, grid, n)
-                check(lib.drt_render_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n,
-                                                    float(R.intIOR), float(R.extIOR), l_ptr[0], g_ptr[0], None,
-                                                    *R._tile_hint(n), grid[0], ptr(grid[1]), _stream()))
+                if self.law is not None:
+                    check(lib.drt_render_paths_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n,
+                                                              float(R.intIOR), float(R.extIOR), self.law[0], int(self.law[1] == "reflect"),
+                                                              l_ptr[0], g_ptr[0], None, _stream()))
+                else:
+                    grid = R._grid_cache(origin, ray_dir, n, *R._tile_hint(n)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
+                    R._arm_seed(h, grid, n)
+                    check(lib.drt_render_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n,
+                                                        float(R.intIOR), float(R.extIOR), l_ptr[0], g_ptr[0], None,
+                                                        *R._tile_hint(n), grid[0], ptr(grid[1]), _stream()))
             ctx = torch.cuda.stream(self.side) if self.side is not None else torch.no_grad()
             with ctx:
                 if hp["sm_w"] != 0:        # (first: it needs no tree, so it runs while the build finishes; the silhouette probes wait for the tree)
@@ -354,14 +395,16 @@ class ShardedIteration:
     parameters stay bit-identical across ranks without a broadcast.  A rank that owns nothing in an iteration still joins the exchange.
     With one rank and ``views_per_step = 1`` this is FusedIteration: same schedule, kernels, weights and update (in deterministic mode the
     same bits).  ``n_allreduce`` counts the collectives issued; ``collective_events`` holds (start, end) CUDA events around each of them
-    until the caller reads them."""
+    until the caller reads them.  ``path_law=(K, tir)``: every owned refraction view goes through drt_render_paths_ray_loss_fused
+    into the same accumulators; the exchange and the step kernels are the same."""
 
     N_SILHOUETTE_VIEWS = 8
 
-    def __init__(self, scene, data, HyperParams, lr, views_per_step=1, concurrent=True):
+    def __init__(self, scene, data, HyperParams, lr, views_per_step=1, concurrent=True, path_law=None):
         from . import _lib, det
         self._lib = _lib
         _refuse_path_law(HyperParams, "ShardedIteration")
+        self.law = path_law_keyword(path_law, HyperParams, "ShardedIteration")
         self.scene, self.data, self.hp = scene, data, HyperParams
         self.k = int(views_per_step)
         if self.k < 1:
@@ -446,6 +489,11 @@ class ShardedIteration:
                 o, d, sp = R._f64c(origin, "origin"), R._f64c(ray_dir, "ray_dir"), R._f64c(target, "screen_pixel")
                 va = R._flag_bytes(valid, "valid", nr)
                 keep += [o, d, sp, va]
+                if self.law is not None:
+                    check(lib.drt_render_paths_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), nr,
+                                                              float(R.intIOR), float(R.extIOR), self.law[0], int(self.law[1] == "reflect"),
+                                                              l_ptr[0], g_ptr[0], None, _stream()))
+                    continue
                 grid = R._grid_cache(origin, ray_dir, nr, *R._tile_hint(nr)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
                 R._arm_seed(h, grid, nr)
                 check(lib.drt_render_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), nr,
@@ -509,14 +557,14 @@ class ShardedIteration:
         return s
 
 
-def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotropic", output=True):
+def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotropic", output=True, path_law=None):
     """``optimize(..., fused=True)`` on every rank of the default process group (one process without one): the pass / iteration loop with
     ShardedIteration steps, ONE all-reduce per iteration, and before every pass the remesh on rank 0 with its result broadcast to the
     others (drt_amd.dist.broadcast_mesh_: the remesher need not give the same mesh in two processes).  ``remesh`` as in optimize (run on
     rank 0 only).  Returns (scene, history, stats): history = the weighted loss every 100 iterations; stats counts the collectives
     (``allreduces`` and ``allreduces_per_iteration``, mesh ``broadcasts`` and ``broadcasts_per_pass``) and times the steps
     (``step_seconds``: the iterations without the remesh, device-synchronised at the end of each pass; ``collective_seconds``: CUDA-event
-    time between the start and the end of the all-reduces)."""
+    time between the start and the end of the all-reduces).  ``path_law=(K, tir)``: as in ShardedIteration."""
     rank, world = ddist.rank_world()
     if remesh == "isotropic":
         from .remesh_gpu import GpuMeshlabserver
@@ -528,6 +576,7 @@ def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotrop
         raise NotImplementedError("HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by optimize_sharded: use the drop-in loop "
                                   "optimize(..., fused=False)")
     _refuse_path_law(HyperParams, "optimize_sharded")
+    law_kw = path_law_keyword(path_law, HyperParams, "optimize_sharded")
     say = output and rank == 0
     Render.intIOR = HyperParams["IOR"]
     Render.resy, Render.resx = data.resy, data.resx
@@ -548,7 +597,7 @@ def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotrop
             if rank == 0:
                 remesh(scene, remesh_len)
             stats["broadcasts"] += int(ddist.broadcast_mesh_(scene, src=0))
-        stepper = ShardedIteration(scene, data, HyperParams, lr, views_per_step)
+        stepper = ShardedIteration(scene, data, HyperParams, lr, views_per_step, path_law=law_kw)
         stepper.ray_view, stepper.silh_view = ray_view, silh_view
         torch.cuda.synchronize(scene.vertices.device)
         t0 = time.perf_counter()
@@ -586,7 +635,7 @@ def setup_opt(scene, lr, HyperParams, hook=True, fused=False):
     return init_vertices, parameter, opt
 
 
-def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=False):
+def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=False, path_law=None):
     """The reference's pass / iteration loop (optim.py:190-215) for an existing scene and data object.
     ``remesh``: "isotropic" (default) re-tessellates to ``remesh_len`` before every pass like the reference's
     ``meshlabserver.remesh`` (optim.py:195), with the device remesher of drt_amd.remesh_gpu ("isotropic-host": the sequential
@@ -599,17 +648,22 @@ def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=Fa
 
     ``HyperParams["max_bounces"]`` (absent or 2) and ``HyperParams["tir"]`` (absent or "drop"): with any other value the refraction term
     traces paths of up to that many interactions (``Scene.render_paths`` + ``Render.ray_loss``); the drop-in loop only, and not together
-    with ``ior_lr``."""
+    with ``ior_lr``.
+
+    ``path_law=(max_bounces, tir)`` (keyword; None or (2, "drop"): today's kernels) selects the same law explicitly and works with both
+    loops: with ``fused=True`` the refraction term is the one-pass ``Scene.paths_ray_loss_fused``, with ``fused=False`` it takes the
+    ``render_paths`` + ``ray_loss`` route of the ``HyperParams`` keys.  Not together with ``ior_lr``."""
     ior_lr = float(HyperParams.get("ior_lr", 0) or 0)
     if ior_lr > 0 and fused:
         raise NotImplementedError("HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by the fused loop: use the drop-in loop "
                                   "optimize(..., fused=False)")
-    law = path_law(HyperParams)
+    law = _law_of(HyperParams)
     if law is not None and fused:
         _refuse_path_law(HyperParams, "the fused loop")
     if law is not None and ior_lr > 0:
         raise NotImplementedError("HyperParams['max_bounces'] / ['tir'] cannot be combined with ior_lr > 0: Scene.render_paths differentiates "
                                   "the vertices only")
+    law_kw = path_law_keyword(path_law, HyperParams, "optimize")
     if remesh == "isotropic":               # on the device (drt_amd.remesh_gpu); "isotropic-host": the sequential host version, its checker
         from .remesh_gpu import GpuMeshlabserver
         remesh = GpuMeshlabserver().remesh
@@ -621,7 +675,7 @@ def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=Fa
         ior = torch.tensor(float(HyperParams["IOR"]), dtype=Float, device=scene.vertices.device, requires_grad=True)
     Render.intIOR = HyperParams["IOR"] if ior is None else ior
     Render.resy, Render.resx = data.resy, data.resx
-    loss_calculator = Loss_calculator(scene, data, HyperParams, fused=fused)
+    loss_calculator = Loss_calculator(scene, data, HyperParams, fused=fused, path_law=law_kw)
     start_time = time.time()
     history = []
     for i_pass in range(HyperParams["Pass"]):
@@ -635,7 +689,7 @@ def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=Fa
         if remesh is not None:
             remesh(scene, remesh_len)
         if fused:      # the one-pass terms without the autograd graph around them (same arithmetic, a third of the host work)
-            stepper = FusedIteration(scene, data, HyperParams, lr)
+            stepper = FusedIteration(scene, data, HyperParams, lr, path_law=law_kw)
             stepper.ray_view, stepper.silh_view = loss_calculator.ray_view, loss_calculator.silh_view      # one view schedule across passes
             for it in range(HyperParams["Iters"]):
                 total, parts = stepper.step()

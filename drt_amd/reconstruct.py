@@ -2,6 +2,7 @@
 
     python -m drt_amd.reconstruct --name horse [--capture horse.npz] [--res 512] [--passes 20] [--iters 200]
     python -m torch.distributed.run --nproc-per-node 8 -m drt_amd.reconstruct --name monkey --views 144 --res 1024 --views-per-step all
+    python -m drt_amd.reconstruct --name horse --max-bounces 6 --tir reflect --fused-paths
 
 ``optimize(HyperParams)`` of the reference builds the scene from ``<data>/<name>_vh.ply``, loads the capture,
 runs Pass x Iters iterations with a remesh before every pass and writes ``<result>/<name>_recons.ply``
@@ -26,16 +27,20 @@ from . import captured_data, diffrender as Render, mesh_io, metrics, optim, view
 
 
 def run(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, fused=True, output=True, device=0, n_views=72,
-        views_per_step=None, ior_start=None):
+        views_per_step=None, ior_start=None, path_law=None):
     """``views_per_step=None``: the single-process loop (optim.optimize).  An int, or "all" (one epoch of the refraction schedule per
     iteration), goes through optim.optimize_sharded on every rank of the default process group (one process without one).
     ``HyperParams["ior_lr"] > 0``: the IOR is fitted too (the drop-in loop, optim.optimize), starting at ``ior_start`` (default
     ``HyperParams["IOR"]``, which is also the IOR the synthetic capture is traced with); the report gains ``ior``, the fitted value.
     ``HyperParams["max_bounces"]`` / ``["tir"]`` other than 2 / "drop" (optim.path_law): the synthetic capture AND the fit trace paths of up
-    to that many interactions (the drop-in loop); the report echoes both."""
-    law = optim.path_law(HyperParams)
+    to that many interactions (the drop-in loop); the report echoes both.
+    ``path_law=(K, tir)`` (the keyword of optim.optimize / optimize_sharded; the ``HyperParams`` keys stay at their defaults): the same
+    law for the capture, and the fit runs it in the ONE-PASS loop (unless ``fused=False``).  ``report["path_route"]`` says which route the
+    refraction term took: "fused" (one-pass kernels) or "dropin"."""
+    law_kw = optim.path_law_keyword(path_law, HyperParams, "reconstruct")
+    law = optim.path_law(HyperParams) or law_kw
     if views_per_step is not None or torch.distributed.is_available() and torch.distributed.is_initialized():
-        return run_sharded(HyperParams, data_path, result_path, capture, res, output, device, n_views, views_per_step or 1)
+        return run_sharded(HyperParams, data_path, result_path, capture, res, output, device, n_views, views_per_step or 1, path_law=law_kw)
     name = HyperParams["name"]
     hull_path = os.path.join(data_path, f"{name}_vh.ply")
     scan_path = os.path.join(data_path, f"{name}_scan.ply")
@@ -59,9 +64,12 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
     if float(HyperParams.get("ior_lr", 0) or 0) > 0:
         start = HyperParams["IOR"] if ior_start is None else float(ior_start)
         report["ior_start"] = start
+        report["path_route"] = "dropin"
         scene, history, report["ior"] = optim.optimize(scene, data, dict(HyperParams, IOR=start), output=output, fused=False)
     else:
-        scene, history = optim.optimize(scene, data, HyperParams, output=output, fused=fused and law is None)
+        one_pass = fused and (law is None or law_kw is not None)
+        report["path_route"] = "fused" if one_pass else "dropin"
+        scene, history = optim.optimize(scene, data, HyperParams, output=output, fused=one_pass, path_law=law_kw)
     torch.cuda.synchronize()
     report["optimize_seconds"] = time.time() - t0
     report["iterations"] = HyperParams["Pass"] * HyperParams["Iters"]
@@ -76,11 +84,12 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
 
 
 def run_sharded(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, output=True, device=0, n_views=72,
-                views_per_step=1):
+                views_per_step=1, path_law=None):
     """The reconstruction on every rank (optim.optimize_sharded): each rank renders only the views it owns of the synthetic capture; rank 0
     alone prints, measures and writes ``<name>_recons.ply`` and ``<name>_report.json``.  Returns (scene, report) -- the report on rank 0,
-    None elsewhere."""
+    None elsewhere.  ``path_law=(K, tir)``: capture and fit trace paths of up to K interactions (the one-pass form)."""
     from . import dist as ddist
+    law = optim.path_law_keyword(path_law, HyperParams, "reconstruct")
     rank, world = ddist.rank_world()
     name = HyperParams["name"]
     hull_path = os.path.join(data_path, f"{name}_vh.ply")
@@ -98,14 +107,15 @@ def run_sharded(HyperParams, data_path="./data/", result_path="./result/", captu
         mine = sorted(set(ddist.owned_views(ray_ids, rank, world)) | set(ddist.owned_views(captured_data.silh_view_ids(n_views), rank, world)))
         gt = scan_scene if scan_scene is not None else Render.Scene(views.displaced_ground_truth(scene.mesh, 0.5, 0), device)
         center, extent = views.mesh_frame(gt.mesh.vertices)
-        data = captured_data.SyntheticData(gt, center, extent, resx, resy, num_view=num_view, n_total=n_views, name=name, view_ids=mine)
+        data = captured_data.SyntheticData(gt, center, extent, resx, resy, num_view=num_view, n_total=n_views, name=name, view_ids=mine,
+                                           path_law=law)
     k = len(data.ray_view_ids()) if views_per_step == "all" else int(views_per_step)
     report = {"name": name, "resx": data.resx, "resy": data.resy, "views": data.n_total, "hull_faces": int(scene.faces.shape[0]),
-              "world": world, "views_per_step": k}
+              "world": world, "views_per_step": k, "max_bounces": law[0] if law else 2, "tir": law[1] if law else "drop", "path_route": "fused"}
     if scan_scene is not None and rank == 0:
         report["hull_to_scan"] = metrics.hausdorff(scene, scan_scene)
     t0 = time.time()
-    scene, history, stats = optim.optimize_sharded(scene, data, HyperParams, views_per_step=k, output=output)
+    scene, history, stats = optim.optimize_sharded(scene, data, HyperParams, views_per_step=k, output=output, path_law=law)
     torch.cuda.synchronize()
     report["optimize_seconds"] = time.time() - t0
     report["iterations"] = stats["iterations"]
@@ -155,6 +165,8 @@ def main(argv=None):
     ap.add_argument("--max-bounces", type=int, default=2, metavar="K", help="surface interactions per light path, 2..8 (other than 2 / drop: "
                     "Scene.render_paths for the synthetic capture and the fit; implies --dropin)")
     ap.add_argument("--tir", choices=("drop", "reflect"), default="drop", help="what a hit with total internal reflection does to a path")
+    ap.add_argument("--fused-paths", action="store_true", help="with --max-bounces / --tir: fit with the one-pass form of the law "
+                    "(Scene.paths_ray_loss_fused) in the one-pass loop, which also runs under torch.distributed.run")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--views-per-step", type=_views_per_step, default=None, metavar="N|all",
                     help="refraction views per iteration (all: every view of the schedule once) on the multi-rank loop; "
@@ -165,12 +177,16 @@ def main(argv=None):
     hp = dict(optim.HyperParams, name=a.name, Pass=a.passes, Iters=a.iters, num_view=a.num_view, IOR=a.ior)
     if a.fit_ior > 0:
         hp["ior_lr"] = a.fit_ior
-    hp["max_bounces"], hp["tir"] = a.max_bounces, a.tir
+    law_kw = None
+    if a.fused_paths:         # the law as the explicit keyword: the HyperParams keys keep their defaults, the one-pass loop runs it
+        law_kw = optim.path_law_keyword((a.max_bounces, a.tir), hp, "reconstruct")
+    else:
+        hp["max_bounces"], hp["tir"] = a.max_bounces, a.tir
     law = optim.path_law(hp)
     from . import dist as ddist
     if a.views_per_step is None and ddist.env_world()[2] == 1:
         _, report = run(hp, a.data_path, a.result_path, a.capture, a.res, fused=not (a.dropin or a.fit_ior > 0), n_views=a.views,
-                        ior_start=a.ior_start)
+                        ior_start=a.ior_start, path_law=law_kw)
         print(json.dumps(report))
         return
     if a.dropin or a.fit_ior > 0 or law is not None:
@@ -180,7 +196,7 @@ def main(argv=None):
     torch.cuda.set_device(device)
     try:
         _, report = run_sharded(hp, a.data_path, a.result_path, a.capture, a.res, output=True, device=device, n_views=a.views,
-                                views_per_step=a.views_per_step or 1)
+                                views_per_step=a.views_per_step or 1, path_law=law_kw)
         if report is not None:
             print(json.dumps(report))
     finally:

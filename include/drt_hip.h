@@ -32,7 +32,7 @@ extern "C" {
 typedef struct drt_scene drt_scene_t;
 
 const char* drt_last_error(void);
-int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward */
+int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -211,6 +211,21 @@ int drt_render_paths_backward(drt_scene_t* s, const double* d_verts, const doubl
                               const int32_t* d_valid_idx, const int64_t* d_n_valid,
                               const double* d_grad_out_ori, const double* d_grad_out_dir,
                               double* d_grad_verts, void* stream);
+
+/* The one-pass form of the K-interaction law for a loss loop: ray_loss of this view and its vertex gradient, nothing dense written
+ * (what drt_render_ray_loss_fused is to drt_render_forward).  *d_loss += sum over the rays with a target (d_valid) whose path completes
+ * of |out_dir - normalize(screen_pixel - out_ori)|^2; d_grad_verts float64 [V,3] += d loss / d vertices with a UNIT seed; *d_n_valid
+ * (int64, device; may be NULL) += the number of contributing rays.  In deterministic mode d_loss and d_grad_verts are accumulator cells,
+ * as for drt_render_ray_loss_fused.  Several calls (the views of a step) may accumulate into the same targets.  The law and its checks
+ * are drt_render_paths_forward's; n_rays = 0, a view that misses the mesh and a view without targets leave the accumulators alone.
+ * No caller tensor is written: the float64 ray in flight, the face tape and the hit counts live in the scene's workspace (81 B per ray
+ * of the largest call so far, next to the ray lists), a ray without a target is never traced, and origin / dir / valid are read once
+ * per camera ray.  All launches go to `stream` and every list size stays on the device: capturable once an eager call of at least this
+ * many rays has grown the workspace (a call that would have to grow it inside a capture is DRT_E_INVALID). */
+int drt_render_paths_ray_loss_fused(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir,
+                                    const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays,
+                                    double ior_int, double ior_ext, int max_bounces, int reflect,
+                                    double* d_loss, double* d_grad_verts, int64_t* d_n_valid, void* stream);
 
 /* ---- Loss_calculator.ray_loss, optim.py:91-108 ------------------------------------------
  * loss = sum over rays with valid & mask of |out_dir - normalize(screen_pixel - out_ori)|^2.
