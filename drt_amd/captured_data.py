@@ -209,7 +209,8 @@ class SyntheticData(Data):
     """Turntable views of a ground-truth mesh traced through the same path, with the tuple layout of
     Data.get_view; built on the device and resident there (stands in for the undistributed captures).
     ``path_law``: None (the default: the reference's two-bounce path, so pixels whose true light path has three or more surface
-    interactions carry no target), or (max_bounces, tir) to trace the ground truth with ``Scene.render_paths``."""
+    interactions carry no target), or (max_bounces, tir) / (max_bounces, tir, refraction) to trace the ground truth with ``Scene.render_paths``
+    -- (2, "drop", "snell") is the two-bounce path as real glass bends it."""
 
     def __init__(self, scene_gt, center, extent, resx, resy, num_view=72, device="cuda", n_total=72, view_ids=None, seed=0, name="synthetic",
                  path_law=None):

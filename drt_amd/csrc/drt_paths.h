@@ -10,6 +10,9 @@
 //             TIR, tir = reflect -> continues mirrored (bounce_reflect), no refraction counted
 //   hit     with K interactions used up: invalid
 // K = 2 with tir = drop is trace_path (drt_path.h): the same rule through the same device functions, the same bits.
+// The third element of the law, the refraction formula (template parameter SNELL of everything below): false, the
+// default, is the reference's Refract through bounce_forward / bounce_backward -- today's functions; true bends a refracting hit by
+// Snell's law (bounce_forward_snell / bounce_backward_snell).  The TIR flag and the mirror continuation are the same under both.
 //
 //   trace_path_k              forward; records the face of every interaction and their number
 //   path_recompute_backward_k recomputes the path from the camera ray and that face tape, reverses it
@@ -25,13 +28,26 @@ constexpr int kMaxBounces = 8;
 // A miss ends the path: valid iff an even, non-zero number of refractions was made.
 DRT_HD bool path_exit_valid(int n_refr) { return n_refr > 0 && (n_refr & 1) == 0; }
 
+// The bounce pair of the law.
+template <bool SNELL>
+DRT_HD void law_forward(d3 o, d3 d, d3 v0, d3 v1, d3 v2, double ior_ext, double ior_int, Bounce& b) {
+    if constexpr (SNELL) bounce_forward_snell(o, d, v0, v1, v2, ior_ext, ior_int, b);
+    else bounce_forward(o, d, v0, v1, v2, ior_ext, ior_int, b);
+}
+template <bool SNELL>
+DRT_HD void law_backward(const Bounce& b, d3 g_new_o, d3 g_wt, d3& gv0, d3& gv1, d3& gv2, d3& g_o, d3& g_d) {
+    if constexpr (SNELL) bounce_backward_snell(b, g_new_o, g_wt, gv0, gv1, gv2, g_o, g_d);
+    else bounce_backward(b, g_new_o, g_wt, gv0, gv1, gv2, g_o, g_d);
+}
+
 // One interaction of the law on face `face`: the continuing ray in (o, d), the refraction count bumped.  False: the path dies (TIR, drop).
+template <bool SNELL = false>
 DRT_HD bool path_interact(const PathCtx& c, int32_t face, bool reflect, d3& o, d3& d, int& n_refr) {
     d3 v0, v1, v2;
     int32_t vid[3];
     Bounce b;
     load_tri64(c, face, v0, v1, v2, vid);
-    bounce_forward(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b);
+    law_forward<SNELL>(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b);
     if (!b.tir) {
         o = b.new_o; d = b.wt;
         ++n_refr;
@@ -46,6 +62,7 @@ DRT_HD bool path_interact(const PathCtx& c, int32_t face, bool reflect, d3& o, d
 
 // Returns true when the path completes; out_o / out_d are then the exit ray.  faces[0 .. n_hits) are the faces of the interactions that
 // took place (also on a path that ends invalid: the caller decides what it reports for those), faces[n_hits .. K) are left alone.
+template <bool SNELL = false>
 DRT_HD bool trace_path_k(const PathCtx& c, Stack& st, d3 o, d3 d, int max_bounces, bool reflect, int32_t* faces, int& n_hits, d3& out_o, d3& out_d) {
     int n_refr = 0;
     n_hits = 0;
@@ -60,7 +77,7 @@ DRT_HD bool trace_path_k(const PathCtx& c, Stack& st, d3 o, d3 d, int max_bounce
         if (k == max_bounces) return false;
         faces[k] = h.face;
         n_hits = k + 1;
-        if (!path_interact(c, h.face, reflect, o, d, n_refr)) return false;
+        if (!path_interact<SNELL>(c, h.face, reflect, o, d, n_refr)) return false;
     }
     return false;
 }
@@ -69,7 +86,7 @@ DRT_HD bool trace_path_k(const PathCtx& c, Stack& st, d3 o, d3 d, int max_bounce
 // at faces[k * face_stride]; the TIR flags are recomputed, the same bits as in the forward: a set flag on a completed path means the ray
 // was mirrored), reverse them, hand the vertex gradients to `add(vertex_id, d3)`.  Only the incoming ray of every interaction is kept
 // (6 doubles each); its Bounce (about 45 doubles) is rebuilt right before it is reversed.
-template <typename Add>
+template <bool SNELL = false, typename Add>
 DRT_HD void path_recompute_backward_k(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 g_ori, d3 g_dir, Add add) {
     d3 ro[kMaxBounces], rd[kMaxBounces];
     d3 v0, v1, v2;
@@ -80,7 +97,7 @@ DRT_HD void path_recompute_backward_k(const PathCtx& c, d3 o, d3 d, const int32_
         ro[k] = o; rd[k] = d;
         if (k + 1 == n_hits) break;              // (the last interaction is rebuilt by the reverse loop)
         load_tri64(c, faces[k * face_stride], v0, v1, v2, vid);
-        bounce_forward(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b);
+        law_forward<SNELL>(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b);
         if (b.tir) { d3 no, wr; bounce_reflect(b, o, no, wr); o = no; d = wr; }
         else { o = b.new_o; d = b.wt; }
     }
@@ -88,10 +105,10 @@ DRT_HD void path_recompute_backward_k(const PathCtx& c, d3 o, d3 d, const int32_
     d3 g_o = g_ori, g_d = g_dir;
     for (int k = n_hits - 1; k >= 0; --k) {
         load_tri64(c, faces[k * face_stride], v0, v1, v2, vid);
-        bounce_forward(ro[k], rd[k], v0, v1, v2, c.ior_ext, c.ior_int, b);
+        law_forward<SNELL>(ro[k], rd[k], v0, v1, v2, c.ior_ext, c.ior_int, b);
         d3 ga = z, gb = z, gc = z, g_o_in, g_d_in;
         if (b.tir) bounce_reflect_backward(b, g_o, g_d, ga, gb, gc, g_o_in, g_d_in);
-        else bounce_backward(b, g_o, g_d, ga, gb, gc, g_o_in, g_d_in);
+        else law_backward<SNELL>(b, g_o, g_d, ga, gb, gc, g_o_in, g_d_in);
         add(vid[0], ga); add(vid[1], gb); add(vid[2], gc);
         g_o = g_o_in; g_d = g_d_in;
     }
@@ -99,12 +116,12 @@ DRT_HD void path_recompute_backward_k(const PathCtx& c, d3 o, d3 d, const int32_
 
 // The one-pass form of a completed path: its ray_loss term (ray_loss_term, drt_shade.h) on the exit ray the forward left behind, and the
 // adjoint of that term w.r.t. the vertices with a unit seed (no gradient reaches the exit origin: the loss detaches it).  Returns the term.
-template <typename Add>
+template <bool SNELL = false, typename Add>
 DRT_HD double path_loss_backward_k(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 exit_o, d3 exit_d,
                                    d3 screen_pixel, Add add) {
     d3 g_dir;
     const double term = ray_loss_term(exit_o, exit_d, screen_pixel, g_dir);
-    path_recompute_backward_k(c, o, d, faces, face_stride, n_hits, d3{0.0, 0.0, 0.0}, g_dir, add);
+    path_recompute_backward_k<SNELL>(c, o, d, faces, face_stride, n_hits, d3{0.0, 0.0, 0.0}, g_dir, add);
     return term;
 }
 

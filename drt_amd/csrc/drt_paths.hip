@@ -109,6 +109,8 @@ __global__ void __launch_bounds__(kPathBlock) k_paths_start_fused(const Node4Q* 
 }
 
 // list k -> list k + 1.  k == max_bounces: every interaction is used up, the list was traced in the any-hit form and nothing continues.
+// SNELL (here and in the two backward kernels): the refraction formula of the law (drt_paths.h), chosen on the host per launch.
+template <bool SNELL>
 __global__ void __launch_bounds__(kPathBlock) k_paths_shade(PathCtx c, int64_t n_rays, int k, int max_bounces, bool reflect, RayList in,
                                                              const unsigned* __restrict__ n_in, RayList out, unsigned* n_out,
                                                              double* __restrict__ out_ori, double* __restrict__ out_dir,
@@ -135,7 +137,7 @@ __global__ void __launch_bounds__(kPathBlock) k_paths_shade(PathCtx c, int64_t n
                     tape[(int64_t)k * n_rays + i] = f;
                     hits[i] = (uint8_t)(k + 1);
                     d3 o = load_d3(out_ori, i), d = load_d3(out_dir, i);
-                    go = path_interact(c, f, reflect, o, d, n_refr);
+                    go = path_interact<SNELL>(c, f, reflect, o, d, n_refr);
                     if (go) {
                         store_d3(out_ori, i, o); store_d3(out_dir, i, d);
                         state[i] = (uint8_t)n_refr;
@@ -185,7 +187,7 @@ __global__ void k_paths_count(const unsigned* __restrict__ count, int64_t* __res
 // gradients through the LDS hash sink.  A ray brings up to 3 * K vertex references (24 at K = 8, against 6 of the two-bounce path), so a
 // table fill takes a quarter of k_render_bwd's rays; neighbouring rays still share most of their vertices.
 constexpr int kPathsBwdBatch = 256;
-template <bool DET>
+template <bool DET, bool SNELL>
 __global__ void __launch_bounds__(256) k_paths_bwd(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir, int64_t n_rays,
                                                    int max_bounces, const int32_t* __restrict__ tape, const uint8_t* __restrict__ hits,
                                                    const double* __restrict__ g_out_ori, const double* __restrict__ g_out_dir, double* grad_verts,
@@ -204,7 +206,7 @@ __global__ void __launch_bounds__(256) k_paths_bwd(PathCtx c, const double* __re
             const d3 z{0.0, 0.0, 0.0};
             const d3 g_ori = g_out_ori ? load_d3(g_out_ori, i) : z;
             const d3 g_dir = g_out_dir ? load_d3(g_out_dir, i) : z;
-            path_recompute_backward_k(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces), g_ori, g_dir, add);
+            path_recompute_backward_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces), g_ori, g_dir, add);
         }
         add.flush();
     }
@@ -228,7 +230,7 @@ __global__ void __launch_bounds__(kPathBlock) k_paths_collect(unsigned n, const 
 // Loss AND vertex gradient (unit seed) over the list of completed paths: the ray_loss term on the exit ray the forward parked -- the bits a
 // recompute would give -- then recompute, reverse, scatter as k_paths_bwd does (same table fill).  Every listed ray has a target:
 // k_paths_start_fused admits no other.
-template <bool DET>
+template <bool DET, bool SNELL>
 __global__ void __launch_bounds__(256) k_paths_loss_bwd(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir,
                                                         const double* __restrict__ screen_pixel, int64_t n_rays, int max_bounces,
                                                         const double* __restrict__ park_ori, const double* __restrict__ park_dir,
@@ -248,7 +250,7 @@ __global__ void __launch_bounds__(256) k_paths_loss_bwd(PathCtx c, const double*
         for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
             const int64_t i = list[k];
             if (i < 0 || i >= n_rays) continue;
-            acc.add(path_loss_backward_k(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
+            acc.add(path_loss_backward_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
                                          load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), add));
             ++cnt;
         }
@@ -314,6 +316,28 @@ static int check_law(int max_bounces, int reflect) {
     return DRT_OK;
 }
 
+// law_flags of the drt_render_paths_law_* entry points (include/drt_hip.h: DRT_LAW_REFLECT | DRT_LAW_SNELL)
+static int check_law_flags(int max_bounces, int law_flags) {
+    if (max_bounces < 2 || max_bounces > kMaxBounces) return fail(DRT_E_INVALID, "max_bounces = %d: must be 2 .. %d", max_bounces, kMaxBounces);
+    if (law_flags & ~(DRT_LAW_REFLECT | DRT_LAW_SNELL))
+        return fail(DRT_E_INVALID, "law_flags = %d: must be a combination of DRT_LAW_REFLECT (%d) and DRT_LAW_SNELL (%d)", law_flags,
+                    DRT_LAW_REFLECT, DRT_LAW_SNELL);
+    return DRT_OK;
+}
+
+// DET_LAUNCH for the kernels whose second template parameter is the refraction formula of the law
+#define DET_LAW_LAUNCH(kern, snell, grid, block, st, ...)                                 \
+    do {                                                                                  \
+        const bool det_ = det_mode();                                                     \
+        if (snell) {                                                                      \
+            if (det_) kern<true, true><<<grid, block, 0, st>>>(__VA_ARGS__);              \
+            else kern<false, true><<<grid, block, 0, st>>>(__VA_ARGS__);                  \
+        } else {                                                                          \
+            if (det_) kern<true, false><<<grid, block, 0, st>>>(__VA_ARGS__);             \
+            else kern<false, false><<<grid, block, 0, st>>>(__VA_ARGS__);                 \
+        }                                                                                 \
+    } while (0)
+
 void paths_free(drt_scene* s) {
     PathsWs* w = ws_of(s);
     if (!w) return;
@@ -326,27 +350,28 @@ void paths_free(drt_scene* s) {
 
 // The wavefront loop behind list 0: trace list k, shade it into list k + 1 (the other ping-pong buffer), K + 1 times.  ray_ori / ray_dir
 // [N,3]: the rows the float64 ray in flight parks in; hits [N], tape [K,N]: written per list item.
-static void trace_lists(drt_scene* s, const PathsWs& w, const PathCtx& pc, hipStream_t st, int gs, int64_t n_rays, int max_bounces, int reflect,
-                        double* ray_ori, double* ray_dir, uint8_t* hits, int32_t* tape) {
+static void trace_lists(drt_scene* s, const PathsWs& w, const PathCtx& pc, hipStream_t st, int gs, int64_t n_rays, int max_bounces, bool reflect,
+                        bool snell, double* ray_ori, double* ray_dir, uint8_t* hits, int32_t* tape) {
     const RayList l0{w.idx[0], w.ray[0], w.face[0]}, l1{w.idx[1], w.ray[1], w.face[1]};
     for (int k = 0; k <= max_bounces; ++k) {
         const RayList& in = (k & 1) ? l1 : l0;
         const RayList& out = (k & 1) ? l0 : l1;
         launch_trace_list(k < max_bounces ? kTraceClosest : kTraceAny, s->grid_path, st, pc.tc, in.ray, w.cnt + kCntList + k,
                           TraceOut{in.face, nullptr, nullptr, nullptr}, w.redo, w.cnt + kCntRedo + k, w.cnt + kCntDone, s->refill_min, s->inner_min, nullptr);
-        k_paths_shade<<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect != 0, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1,
-                                                 ray_ori, ray_dir, w.state, hits, tape);
+        if (snell)
+            k_paths_shade<true><<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1,
+                                                           ray_ori, ray_dir, w.state, hits, tape);
+        else
+            k_paths_shade<false><<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1,
+                                                            ray_ori, ray_dir, w.state, hits, tape);
     }
 }
 
-extern "C" {
-
-int drt_render_paths_forward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
-                             double ior_int, double ior_ext, int max_bounces, int reflect,
-                             double* d_out_ori, double* d_out_dir, uint8_t* d_mask, int32_t* d_tape, uint8_t* d_hits,
-                             int32_t* d_valid_idx, int64_t* d_n_valid, void* stream) {
-    CHECK_BUILT(s);
-    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+// The bodies behind the entry points; the law has been checked.  `who`: the entry point, for messages.
+static int paths_forward(drt_scene* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                         double ior_int, double ior_ext, int max_bounces, bool reflect, bool snell,
+                         double* d_out_ori, double* d_out_dir, uint8_t* d_mask, int32_t* d_tape, uint8_t* d_hits,
+                         int32_t* d_valid_idx, int64_t* d_n_valid, void* stream, const char* who) {
     if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
     hipStream_t st = (hipStream_t)stream;
     if (n_rays == 0) {
@@ -355,7 +380,7 @@ int drt_render_paths_forward(drt_scene_t* s, const double* d_verts, const double
     }
     if (!d_verts || !d_origin || !d_dir || !d_out_ori || !d_out_dir || !d_mask || !d_tape || !d_hits || !d_valid_idx || !d_n_valid)
         return fail(DRT_E_INVALID, "null pointer argument");
-    { int rc = ensure_paths_ws(s, n_rays, st, "drt_render_paths_forward"); if (rc) return rc; }
+    { int rc = ensure_paths_ws(s, n_rays, st, who); if (rc) return rc; }
     { int rc = wait_build(s, st); if (rc) return rc; }
     const PathsWs& w = *ws_of(s);
     PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
@@ -366,40 +391,37 @@ int drt_render_paths_forward(drt_scene_t* s, const double* d_verts, const double
     HIP_TRY(hipMemsetAsync(d_tape, 0xFF, sizeof(int32_t) * (size_t)max_bounces * (size_t)n_rays, st));
     const RayList l0{w.idx[0], w.ray[0], w.face[0]};
     k_paths_start<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, d_origin, d_dir, n, d_out_ori, d_out_dir, w.state, d_hits, l0, w.cnt + kCntList);
-    trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, d_out_ori, d_out_dir, d_hits, d_tape);
+    trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, snell, d_out_ori, d_out_dir, d_hits, d_tape);
     k_paths_finish<<<gs, kPathBlock, 0, st>>>(n, d_out_ori, d_out_dir, d_mask, w.state, d_hits, d_valid_idx, w.cnt + kCntValid);
     k_paths_count<<<1, 64, 0, st>>>(w.cnt + kCntValid, d_n_valid);
     HIP_TRY(hipGetLastError());
     return DRT_OK;
 }
 
-int drt_render_paths_backward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
-                              double ior_int, double ior_ext, int max_bounces, int reflect,
-                              const int32_t* d_tape, const uint8_t* d_hits, const int32_t* d_valid_idx, const int64_t* d_n_valid,
-                              const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts, void* stream) {
-    CHECK_BUILT(s);
-    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+static int paths_backward(drt_scene* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                          double ior_int, double ior_ext, int max_bounces, bool snell,
+                          const int32_t* d_tape, const uint8_t* d_hits, const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                          const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts, void* stream) {
     if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
     if (n_rays == 0 || (!d_grad_out_ori && !d_grad_out_dir)) return DRT_OK;
     if (!d_verts || !d_origin || !d_dir || !d_tape || !d_hits || !d_valid_idx || !d_n_valid || !d_grad_verts) return fail(DRT_E_INVALID, "null pointer argument");
     hipStream_t st = (hipStream_t)stream;
     const PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
-    DET_LAUNCH(k_paths_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, n_rays, max_bounces, d_tape, d_hits, d_grad_out_ori, d_grad_out_dir, d_grad_verts,
+    DET_LAW_LAUNCH(k_paths_bwd, snell, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, n_rays, max_bounces, d_tape, d_hits, d_grad_out_ori, d_grad_out_dir, d_grad_verts,
                d_valid_idx, d_n_valid);
     HIP_TRY(hipGetLastError());
     return DRT_OK;
 }
 
-int drt_render_paths_ray_loss_fused(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir,
-                                    const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays, double ior_int, double ior_ext,
-                                    int max_bounces, int reflect, double* d_loss, double* d_grad_verts, int64_t* d_n_valid, void* stream) {
-    CHECK_BUILT(s);
-    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+static int paths_ray_loss_fused(drt_scene* s, const double* d_verts, const double* d_origin, const double* d_dir,
+                                const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays, double ior_int, double ior_ext,
+                                int max_bounces, bool reflect, bool snell, double* d_loss, double* d_grad_verts, int64_t* d_n_valid,
+                                void* stream, const char* who) {
     if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
     if (n_rays == 0) return DRT_OK;
     if (!d_verts || !d_origin || !d_dir || !d_screen_pixel || !d_valid || !d_loss || !d_grad_verts) return fail(DRT_E_INVALID, "null pointer argument");
     hipStream_t st = (hipStream_t)stream;
-    { int rc = ensure_paths_ws(s, n_rays, st, "drt_render_paths_ray_loss_fused"); if (rc) return rc; }
+    { int rc = ensure_paths_ws(s, n_rays, st, who); if (rc) return rc; }
     { int rc = ensure_paths_fused_ws(s, n_rays, st); if (rc) return rc; }
     { int rc = wait_build(s, st); if (rc) return rc; }
     const PathsWs& w = *ws_of(s);
@@ -412,13 +434,75 @@ int drt_render_paths_ray_loss_fused(drt_scene_t* s, const double* d_verts, const
     HIP_TRY(hipMemsetAsync(w.cnt, 0, sizeof(unsigned) * kCntWords, st));
     const RayList l0{w.idx[0], w.ray[0], w.face[0]};
     k_paths_start_fused<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, d_origin, d_dir, d_valid, n, park_ori, park_dir, w.state, l0, w.cnt + kCntList);
-    trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, park_ori, park_dir, w.hits, w.tape);
+    trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, snell, park_ori, park_dir, w.hits, w.tape);
     int32_t* const done = w.idx[0];          // (both ping-pong lists are free once the loop has ended)
     k_paths_collect<<<gs, kPathBlock, 0, st>>>(n, w.state, done, w.cnt + kCntValid);
-    DET_LAUNCH(k_paths_loss_bwd, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_screen_pixel, n_rays, max_bounces, park_ori, park_dir, w.tape, w.hits,
+    DET_LAW_LAUNCH(k_paths_loss_bwd, snell, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_screen_pixel, n_rays, max_bounces, park_ori, park_dir, w.tape, w.hits,
                done, w.cnt + kCntValid, d_loss, d_grad_verts, reinterpret_cast<unsigned long long*>(d_n_valid));
     HIP_TRY(hipGetLastError());
     return DRT_OK;
+}
+
+extern "C" {
+
+int drt_render_paths_forward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                             double ior_int, double ior_ext, int max_bounces, int reflect,
+                             double* d_out_ori, double* d_out_dir, uint8_t* d_mask, int32_t* d_tape, uint8_t* d_hits,
+                             int32_t* d_valid_idx, int64_t* d_n_valid, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+    return paths_forward(s, d_verts, d_origin, d_dir, n_rays, ior_int, ior_ext, max_bounces, reflect != 0, false, d_out_ori, d_out_dir, d_mask,
+                         d_tape, d_hits, d_valid_idx, d_n_valid, stream, "drt_render_paths_forward");
+}
+
+int drt_render_paths_backward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                              double ior_int, double ior_ext, int max_bounces, int reflect,
+                              const int32_t* d_tape, const uint8_t* d_hits, const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                              const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+    return paths_backward(s, d_verts, d_origin, d_dir, n_rays, ior_int, ior_ext, max_bounces, false, d_tape, d_hits, d_valid_idx, d_n_valid,
+                          d_grad_out_ori, d_grad_out_dir, d_grad_verts, stream);
+}
+
+int drt_render_paths_ray_loss_fused(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir,
+                                    const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays, double ior_int, double ior_ext,
+                                    int max_bounces, int reflect, double* d_loss, double* d_grad_verts, int64_t* d_n_valid, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
+    return paths_ray_loss_fused(s, d_verts, d_origin, d_dir, d_screen_pixel, d_valid, n_rays, ior_int, ior_ext, max_bounces, reflect != 0, false,
+                                d_loss, d_grad_verts, d_n_valid, stream, "drt_render_paths_ray_loss_fused");
+}
+
+int drt_render_paths_law_forward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                                 double ior_int, double ior_ext, int max_bounces, int law_flags,
+                                 double* d_out_ori, double* d_out_dir, uint8_t* d_mask, int32_t* d_tape, uint8_t* d_hits,
+                                 int32_t* d_valid_idx, int64_t* d_n_valid, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law_flags(max_bounces, law_flags); if (rc) return rc; }
+    return paths_forward(s, d_verts, d_origin, d_dir, n_rays, ior_int, ior_ext, max_bounces, (law_flags & DRT_LAW_REFLECT) != 0,
+                         (law_flags & DRT_LAW_SNELL) != 0, d_out_ori, d_out_dir, d_mask, d_tape, d_hits, d_valid_idx, d_n_valid, stream,
+                         "drt_render_paths_law_forward");
+}
+
+int drt_render_paths_law_backward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
+                                  double ior_int, double ior_ext, int max_bounces, int law_flags,
+                                  const int32_t* d_tape, const uint8_t* d_hits, const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                                  const double* d_grad_out_ori, const double* d_grad_out_dir, double* d_grad_verts, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law_flags(max_bounces, law_flags); if (rc) return rc; }
+    return paths_backward(s, d_verts, d_origin, d_dir, n_rays, ior_int, ior_ext, max_bounces, (law_flags & DRT_LAW_SNELL) != 0, d_tape, d_hits,
+                          d_valid_idx, d_n_valid, d_grad_out_ori, d_grad_out_dir, d_grad_verts, stream);
+}
+
+int drt_render_paths_law_ray_loss_fused(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir,
+                                        const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays, double ior_int, double ior_ext,
+                                        int max_bounces, int law_flags, double* d_loss, double* d_grad_verts, int64_t* d_n_valid, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law_flags(max_bounces, law_flags); if (rc) return rc; }
+    return paths_ray_loss_fused(s, d_verts, d_origin, d_dir, d_screen_pixel, d_valid, n_rays, ior_int, ior_ext, max_bounces,
+                                (law_flags & DRT_LAW_REFLECT) != 0, (law_flags & DRT_LAW_SNELL) != 0, d_loss, d_grad_verts, d_n_valid, stream,
+                                "drt_render_paths_law_ray_loss_fused");
 }
 
 }  // extern "C"

@@ -122,6 +122,72 @@ DRT_HD void bounce_backward(const Bounce& b, d3 g_new_o, d3 g_wt, d3& gv0, d3& g
     gv0 -= (g_s + g_e1) + g_e2;
 }
 
+// The refracting bounce under Snell's law (opt-in, paths of up to K interactions only: drt_paths.h).  One statement of
+// bounce_forward differs -- cosThetaT comes from sin2ThetaT = eta^2 * sin2ThetaI, so sin(theta_t) = eta * sin(theta_i) --
+//   ct = sqrt(max(1 - (eta * eta) * s2, 0))
+// and what follows it (k, w, wl, wt, new_o) is restated with bounce_forward's own statements; everything before it (the tape, the
+// `entering` branch, the TIR flag) is bounce_forward's, bit for bit.  The flag is mathematically the same condition (eta^2 * s2 >= 1), so
+// bounce_reflect / bounce_reflect_backward, which never read ct, continue a flagged bounce unchanged.
+DRT_HD void bounce_forward_snell(d3 o, d3 d, d3 v0, d3 v1, d3 v2, double ior_ext, double ior_int, Bounce& b) {
+    bounce_forward(o, d, v0, v1, v2, ior_ext, ior_int, b);
+    const double arg = 1.0 - (b.eta * b.eta) * b.s2;
+    b.ct = sqrt(arg < 0.0 ? 0.0 : arg);
+    b.k = b.eta * b.ci - b.ct;
+    b.w = b.eta * d + b.k * b.n;
+    b.wl = sqrt((b.w.x * b.w.x + b.w.y * b.w.y) + b.w.z * b.w.z);
+    b.wt = b.w / b.wl;
+    b.new_o = (o + b.t * d) + 1e-5 * b.wt;
+}
+
+// Adjoint of bounce_forward_snell: bounce_backward statement for statement, except the chain k = eta*ci - ct.  ct > 0 guards the
+// division: a bounce whose flag says "refracts" but whose 1 - eta^2 * s2 rounds to <= 0 gets no gradient through ct (the clamp's
+// convention) instead of NaN.  Near the critical angle the gradient grows like 1 / ct: that is the physics.
+DRT_HD void bounce_backward_snell(const Bounce& b, d3 g_new_o, d3 g_wt, d3& gv0, d3& gv1, d3& gv2, d3& g_o, d3& g_d) {
+    // new_o = o + t*d + 1e-5*wt
+    g_o = g_new_o;
+    const double g_t = dot(g_new_o, b.d);
+    g_d = b.t * g_new_o;
+    const d3 G = g_wt + 1e-5 * g_new_o;
+    // wt = w / |w|
+    const d3 g_w = (G - dot(b.wt, G) * b.wt) / b.wl;
+    // w = eta*d + k*n
+    g_d += b.eta * g_w;
+    const double g_k = dot(g_w, b.n);
+    d3 g_n = b.k * g_w;
+    // k = eta*ci - ct ; ct = sqrt(max(1 - eta^2 * s2, 0)) ; s2 = max(1 - ci^2, 0)
+    double g_ci = b.eta * g_k;
+    const double g_ct = -g_k;
+    const double g_s2 = (b.ct > 0.0) ? -(b.eta * b.eta) * (g_ct / (2.0 * b.ct)) : 0.0;
+    const double g_in = (b.one_m_ci2 >= 0.0) ? g_s2 : 0.0;
+    g_ci += -2.0 * b.ci * g_in;
+    // ci = n . wo = -(n . d)
+    g_n += (-g_ci) * b.d;
+    g_d += (-g_ci) * b.n;
+    // n = sg*n0 ; n0 = m/|m| ; m = e1 x e2
+    const d3 g_n0 = b.sg * g_n;
+    const d3 g_m = (g_n0 - dot(b.n0, g_n0) * b.n0) / b.len;
+    d3 g_e1 = cross(b.e2, g_m);
+    d3 g_e2 = cross(g_m, b.e1);
+    // t = (e2 . q) * inv
+    g_e2 += (g_t * b.inv) * b.q;
+    const d3 g_q = (g_t * b.inv) * b.e2;
+    const double g_inv = g_t * b.e2q;
+    // q = s x e1
+    const d3 g_s = cross(b.e1, g_q);
+    g_e1 += cross(g_q, b.s);
+    // s = o - v0
+    g_o += g_s;
+    // inv = 1/det ; det = e1 . p ; p = d x e2
+    const double g_det = -g_inv * b.inv * b.inv;
+    g_e1 += g_det * b.p;
+    const d3 g_p = g_det * b.e1;
+    g_d += cross(b.e2, g_p);
+    g_e2 += cross(g_p, b.d);
+    gv1 += g_e1;
+    gv2 += g_e2;
+    gv0 -= (g_s + g_e1) + g_e2;
+}
+
 // bounce_backward plus the adjoint of eta (g_eta; set).  eta enters only through w = eta*d + k*n and k = eta*ci - ct, so
 // g_eta = dot(g_w, d) + g_k*ci; g_w and g_k are recomputed with bounce_backward's own statements (the same bits, which the
 // compiler shares).  bounce_backward itself is left alone: the kernels that do not need g_eta keep their code.

@@ -597,11 +597,23 @@ class _RenderTransparent(torch.autograd.Function):
         return grad_v, g_in[0], g_in[1], None, g_ior[0], g_ior[1], None, None, None
 
 
+def _law_flags(tir, refraction):
+    """law_flags of the drt_render_paths_law_* entry points (DRT_LAW_REFLECT = 1, DRT_LAW_SNELL = 2)."""
+    return int(tir == "reflect") | (2 if refraction == "snell" else 0)
+
+
+def _paths_entry(name, law_flags):
+    """The entry point of a K-interaction call: without the Snell bit the one that takes ``reflect`` -- today's call -- else its
+    ``_law`` namesake, which takes the flags in the same place."""
+    return getattr(_lib.lib(), name.replace("drt_render_paths_", "drt_render_paths_law_") if law_flags & 2 else name)
+
+
 class _RenderPaths(torch.autograd.Function):
-    """render_paths (paths of up to K interactions, drt_render_paths_forward) as a function of the vertices."""
+    """render_paths (paths of up to K interactions, drt_render_paths_forward / drt_render_paths_law_forward) as a function of the
+    vertices.  ``law_flags`` (``_law_flags``) goes to the backward with the tape."""
 
     @staticmethod
-    def forward(ctx, vertices, origin, ray_dir, scene, ior, max_bounces, reflect):
+    def forward(ctx, vertices, origin, ray_dir, scene, ior, max_bounces, law_flags):
         v = _f64c(vertices.detach(), "vertices")
         o = _f64c(origin.detach(), "origin")
         d = _f64c(ray_dir.detach(), "ray_dir")
@@ -617,11 +629,11 @@ class _RenderPaths(torch.autograd.Function):
         n_valid = torch.zeros(1, dtype=torch.int64, device=dev)
         if n:
             with _on(dev):
-                _lib.check(_lib.lib().drt_render_paths_forward(
-                    scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), n, ior[0], ior[1], max_bounces, int(reflect),
+                _lib.check(_paths_entry("drt_render_paths_forward", law_flags)(
+                    scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), n, ior[0], ior[1], max_bounces, law_flags,
                     out_ori.data_ptr(), out_dir.data_ptr(), mask.data_ptr(), tape.data_ptr(), hits.data_ptr(),
                     valid_idx.data_ptr(), n_valid.data_ptr(), _stream()))
-        ctx.scene, ctx.ior, ctx.law = scene, ior, (max_bounces, int(reflect))
+        ctx.scene, ctx.ior, ctx.law = scene, ior, (max_bounces, law_flags)
         ctx.save_for_backward(v, o, d, tape, hits, valid_idx, n_valid)
         ctx.set_materialize_grads(False)
         mask_b = mask.view(torch.bool)
@@ -638,7 +650,7 @@ class _RenderPaths(torch.autograd.Function):
         g_ori = None if g_ori is None else _f64c(g_ori, "grad_out_ori")
         g_dir = None if g_dir is None else _f64c(g_dir, "grad_out_dir")
         with _on(o.device):
-            _lib.check(_lib.lib().drt_render_paths_backward(
+            _lib.check(_paths_entry("drt_render_paths_backward", ctx.law[1])(
                 ctx.scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), o.shape[0], ctx.ior[0], ctx.ior[1], *ctx.law,
                 tape.data_ptr(), hits.data_ptr(), valid_idx.data_ptr(), n_valid.data_ptr(), _lib.ptr(g_ori), _lib.ptr(g_dir),
                 grad_v.data_ptr(), _stream()))
@@ -761,10 +773,11 @@ class _RenderRayLossFused(torch.autograd.Function):
 
 
 class _PathsRayLossFused(torch.autograd.Function):
-    """render_paths + ray_loss + d/d vertices of one view in ONE call (drt_render_paths_ray_loss_fused: nothing dense written)."""
+    """render_paths + ray_loss + d/d vertices of one view in ONE call (drt_render_paths_ray_loss_fused or, under Snell, its ``_law``
+    namesake: nothing dense written).  The gradient is computed here, under ``law_flags``; the backward only scales it."""
 
     @staticmethod
-    def forward(ctx, vertices, origin, ray_dir, screen_pixel, valid, scene, ior, max_bounces, reflect):
+    def forward(ctx, vertices, origin, ray_dir, screen_pixel, valid, scene, ior, max_bounces, law_flags):
         v = _f64c(vertices.detach(), "vertices")
         o = _f64c(origin, "origin")
         d = _f64c(ray_dir, "ray_dir")
@@ -774,10 +787,11 @@ class _PathsRayLossFused(torch.autograd.Function):
         grad_v = det.acc(v)
         count = torch.zeros((), dtype=torch.int64, device=o.device)
         with _on(o.device):
-            _lib.check(_lib.lib().drt_render_paths_ray_loss_fused(
+            _lib.check(_paths_entry("drt_render_paths_ray_loss_fused", law_flags)(
                 scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), o.shape[0],
-                ior[0], ior[1], max_bounces, int(reflect), loss.data_ptr(), grad_v.data_ptr(), count.data_ptr(), _stream()))
+                ior[0], ior[1], max_bounces, law_flags, loss.data_ptr(), grad_v.data_ptr(), count.data_ptr(), _stream()))
         scene.last_path_count = count
+        ctx.law_flags = law_flags
         ctx.wide = grad_v if grad_v.dtype == torch.int64 else None
         ctx.save_for_backward(det.value(grad_v, v))
         return det.value(loss)
@@ -966,7 +980,7 @@ class Scene(StepwiseMixin):
         link.out_ori = weakref.ref(out_ori)
         return out_ori, out_dir, mask
 
-    def render_paths(self, origin, ray_dir, max_bounces=4, tir="reflect"):
+    def render_paths(self, origin, ray_dir, max_bounces=4, tir="reflect", refraction="reference"):
         """Refraction paths of up to ``max_bounces`` (2..8) surface interactions: (out_ori, out_dir, mask) as render_transparent.
         ``tir``: what a hit with total internal reflection does -- "drop" ends the path (the reference's rule), "reflect" mirrors the
         ray (the reference's Reflect with refract_ray's flipped normal) and goes on.  A path is valid when it leaves the object after an
@@ -974,34 +988,40 @@ class Scene(StepwiseMixin):
         ``render_transparent(o, d)`` bit for bit.  Differentiable w.r.t. ``self.vertices`` only: a gradient requested for ``origin``,
         ``ray_dir`` or a tensor IOR raises NotImplementedError.  Afterwards ``self.last_path_hits`` (uint8 [N]: interactions of each valid
         path, 0 elsewhere) and ``self.last_path_faces`` (int32 [K, N]: face per interaction, -1 past the end) describe the call.  Works
-        with ``ray_loss`` through its dense gradient route."""
-        ior = self._check_paths_call("render_paths", origin, ray_dir, max_bounces, tir)
-        return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), tir == "reflect")
+        with ``ray_loss`` through its dense gradient route.
+        ``refraction``: how a refracting hit bends the ray -- "reference" (the default: the reference's Refract, which obeys
+        tan(theta_t) = eta tan(theta_i); every route of this package) or "snell" (sin(theta_t) = eta sin(theta_i): what real glass
+        does; these K-interaction calls only).  ``render_paths(o, d, 2, "drop", "snell")`` is the two-bounce path under
+        Snell's law."""
+        ior = self._check_paths_call("render_paths", origin, ray_dir, max_bounces, tir, refraction)
+        return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), _law_flags(tir, refraction))
 
     @staticmethod
-    def _check_paths_call(who, origin, ray_dir, max_bounces, tir):
+    def _check_paths_call(who, origin, ray_dir, max_bounces, tir, refraction="reference"):
         """The argument checks of the K-interaction calls; returns the (intIOR, extIOR) floats."""
         if isinstance(max_bounces, bool) or int(max_bounces) != max_bounces or not 2 <= int(max_bounces) <= 8:
             raise ValueError(f"max_bounces must be an integer in 2..8, got {max_bounces!r}")
         if tir not in ("drop", "reflect"):
             raise ValueError(f"tir must be 'drop' or 'reflect', got {tir!r}")
+        if not isinstance(refraction, str) or refraction not in ("reference", "snell"):
+            raise ValueError(f"refraction must be 'reference' or 'snell', got {refraction!r}")
         if _wants_input_grads(origin, ray_dir, intIOR, extIOR):
             raise NotImplementedError(f"{who} differentiates the vertices only: origin, ray_dir and the IORs must not require grad "
                                       "(render_transparent has those gradients for the two-bounce path)")
         return _ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR")
 
-    def paths_ray_loss_fused(self, origin, ray_dir, screen_pixel, valid, max_bounces=4, tir="reflect"):
-        """ray_loss of this view under the law of ``render_paths`` -- ``ray_loss(*render_paths(origin, ray_dir, max_bounces, tir),
-        screen_pixel, valid)`` -- in one call that writes no dense output (drt_render_paths_ray_loss_fused): the loss as a scalar, its
+    def paths_ray_loss_fused(self, origin, ray_dir, screen_pixel, valid, max_bounces=4, tir="reflect", refraction="reference"):
+        """ray_loss of this view under the law of ``render_paths`` -- ``ray_loss(*render_paths(origin, ray_dir, max_bounces, tir,
+        refraction), screen_pixel, valid)`` -- in one call that writes no dense output (drt_render_paths_ray_loss_fused): the loss as a scalar, its
         vertex gradient computed alongside with a unit seed and scaled in the backward pass.  Differentiable w.r.t. ``self.vertices``
         only, like ``render_paths``.  ``origin`` may be a RayBinding: its rays are used, nothing else of it (no grid verdicts, seeds or
         recycled outputs exist for this law).  Afterwards ``self.last_path_count`` is the number of contributing rays (0-dim int64 tensor
         on the device; reading it synchronises, producing it does not)."""
         if isinstance(origin, RayBinding):
             origin, ray_dir = origin.origin, origin.ray_dir
-        ior = self._check_paths_call("paths_ray_loss_fused", origin, ray_dir, max_bounces, tir)
+        ior = self._check_paths_call("paths_ray_loss_fused", origin, ray_dir, max_bounces, tir, refraction)
         _stats["paths_fused_calls"] += 1
-        return _PathsRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, int(max_bounces), tir == "reflect")
+        return _PathsRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, int(max_bounces), _law_flags(tir, refraction))
 
     def ray_loss_fused(self, origin, ray_dir, screen_pixel, valid):
         """ray_loss of this view without materialising out_ori/out_dir/mask.  The fused kernel differentiates the vertices only: when

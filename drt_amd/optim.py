@@ -37,15 +37,28 @@ HyperParams = {          # reference config.py:18-39
 
 def path_law(hp):
     """(max_bounces, tir) of ``HyperParams``, or None for the reference's path (both absent, or 2 and "drop"): what selects
-    ``Scene.render_paths`` instead of ``render_transparent`` in the drop-in loop.  Bad values raise ValueError here, before a pass starts."""
-    k, tir = hp.get("max_bounces", 2), hp.get("tir", "drop")
+    ``Scene.render_paths`` instead of ``render_transparent`` in the drop-in loop.  Bad values raise ValueError here, before a pass starts.
+    A third key, ``HyperParams["refraction"]`` (absent, None or "reference": the reference's formula, the results above), adds the
+    refraction formula: with "snell" the result is (max_bounces, tir, "snell"), and 2 / "drop" is a law too -- the two-bounce path bent
+    by Snell's law.  The tuple is what ``Scene.render_paths`` / ``paths_ray_loss_fused`` take after the rays."""
+    k, tir, refraction = hp.get("max_bounces", 2), hp.get("tir", "drop"), hp.get("refraction", "reference")
     k = 2 if k is None else k
     tir = "drop" if tir is None else tir
+    refraction = "reference" if refraction is None else refraction
     if isinstance(k, bool) or int(k) != k or not 2 <= int(k) <= 8:
         raise ValueError(f"HyperParams['max_bounces'] must be an integer in 2..8, got {k!r}")
     if tir not in ("drop", "reflect"):
         raise ValueError(f"HyperParams['tir'] must be 'drop' or 'reflect', got {tir!r}")
+    if not isinstance(refraction, str) or refraction not in ("reference", "snell"):
+        raise ValueError(f"HyperParams['refraction'] must be 'reference' or 'snell', got {refraction!r}")
+    if refraction == "snell":
+        return (int(k), tir, "snell")
     return None if (int(k) == 2 and tir == "drop") else (int(k), tir)
+
+
+def law_flags(law):
+    """``law_flags`` of the drt_render_paths_law_* entry points for a normalised law."""
+    return Render._law_flags(law[1], law[2] if len(law) > 2 else "reference")
 
 
 _law_of = path_law          # (the loops take a keyword of that name)
@@ -58,18 +71,23 @@ def _refuse_path_law(hp, who):
 
 
 def path_law_keyword(law, hp, who):
-    """The ``path_law=(max_bounces, tir)`` keyword of the loops, normalised by the rules of ``path_law``: None when absent or (2, "drop")
-    -- today's kernels -- else (int K, tir); bad values raise ValueError.  The keyword selects the ONE-PASS form of the law
+    """The ``path_law=(max_bounces, tir)`` or ``(max_bounces, tir, refraction)`` keyword of the loops, normalised by the rules of
+    ``path_law``: None when absent or (2, "drop") -- today's kernels -- else (int K, tir), or (int K, tir, "snell") under Snell's law
+    (a "reference" third element is dropped); bad values raise ValueError.  The keyword selects the ONE-PASS form of the law
     (``Scene.paths_ray_loss_fused`` / drt_render_paths_ray_loss_fused) where the caller runs the one-pass terms; the ``HyperParams``
     keys keep meaning the drop-in route.  Like ``Scene.render_paths`` the law differentiates the vertices only: not with ``ior_lr > 0``.
     Looks at nothing but its arguments."""
     if law is None:
         return None
     try:
-        k, tir = law
+        k, tir, *rest = law
+        (refraction,) = rest or ("reference",)
     except (TypeError, ValueError):
-        raise ValueError(f"path_law must be None or (max_bounces, tir), got {law!r}") from None
-    law = path_law({"max_bounces": k, "tir": tir})
+        raise ValueError(f"path_law must be None or (max_bounces, tir) or (max_bounces, tir, refraction), got {law!r}") from None
+    refraction = "reference" if refraction is None else refraction
+    if not isinstance(refraction, str) or refraction not in ("reference", "snell"):
+        raise ValueError(f"path_law's refraction must be 'reference' or 'snell', got {refraction!r}")
+    law = path_law({"max_bounces": k, "tir": tir, "refraction": refraction})
     if law is None:
         return None
     if float(hp.get("ior_lr", 0) or 0) > 0:
@@ -332,8 +350,8 @@ class FusedIteration:
                 o, d, sp = R._f64c(origin, "origin"), R._f64c(ray_dir, "ray_dir"), R._f64c(target, "screen_pixel")
                 va = R._flag_bytes(valid, "valid", n)
                 if self.law is not None:
-                    check(lib.drt_render_paths_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n,
-                                                              float(R.intIOR), float(R.extIOR), self.law[0], int(self.law[1] == "reflect"),
+                    check(R._paths_entry("drt_render_paths_ray_loss_fused", law_flags(self.law))(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n,
+                                                              float(R.intIOR), float(R.extIOR), self.law[0], law_flags(self.law),
                                                               l_ptr[0], g_ptr[0], None, _stream()))
                 else:
                     grid = R._grid_cache(origin, ray_dir, n, *R._tile_hint(n)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
@@ -490,8 +508,8 @@ class ShardedIteration:
                 va = R._flag_bytes(valid, "valid", nr)
                 keep += [o, d, sp, va]
                 if self.law is not None:
-                    check(lib.drt_render_paths_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), nr,
-                                                              float(R.intIOR), float(R.extIOR), self.law[0], int(self.law[1] == "reflect"),
+                    check(R._paths_entry("drt_render_paths_ray_loss_fused", law_flags(self.law))(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), nr,
+                                                              float(R.intIOR), float(R.extIOR), self.law[0], law_flags(self.law),
                                                               l_ptr[0], g_ptr[0], None, _stream()))
                     continue
                 grid = R._grid_cache(origin, ray_dir, nr, *R._tile_hint(nr)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)

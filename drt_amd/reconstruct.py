@@ -26,6 +26,10 @@ import torch
 from . import captured_data, diffrender as Render, mesh_io, metrics, optim, views
 
 
+def _refraction_of(law):
+    return law[2] if law is not None and len(law) > 2 else "reference"
+
+
 def run(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, fused=True, output=True, device=0, n_views=72,
         views_per_step=None, ior_start=None, path_law=None):
     """``views_per_step=None``: the single-process loop (optim.optimize).  An int, or "all" (one epoch of the refraction schedule per
@@ -35,7 +39,8 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
     ``HyperParams["max_bounces"]`` / ``["tir"]`` other than 2 / "drop" (optim.path_law): the synthetic capture AND the fit trace paths of up
     to that many interactions (the drop-in loop); the report echoes both.
     ``path_law=(K, tir)`` (the keyword of optim.optimize / optimize_sharded; the ``HyperParams`` keys stay at their defaults): the same
-    law for the capture, and the fit runs it in the ONE-PASS loop (unless ``fused=False``).  ``report["path_route"]`` says which route the
+    law for the capture, and the fit runs it in the ONE-PASS loop (unless ``fused=False``).  Either spelling may carry the refraction
+    formula (``HyperParams["refraction"]``, or a third element of the keyword: "reference" / "snell"); the report echoes it.  ``report["path_route"]`` says which route the
     refraction term took: "fused" (one-pass kernels) or "dropin"."""
     law_kw = optim.path_law_keyword(path_law, HyperParams, "reconstruct")
     law = optim.path_law(HyperParams) or law_kw
@@ -57,7 +62,7 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
         data = captured_data.SyntheticData(gt, center, extent, resx, resy, num_view=min(HyperParams["num_view"], n_views), n_total=n_views, name=name,
                                            path_law=law)
     report = {"name": name, "resx": data.resx, "resy": data.resy, "views": data.n_total, "hull_faces": int(scene.faces.shape[0]),
-              "max_bounces": law[0] if law else 2, "tir": law[1] if law else "drop"}
+              "max_bounces": law[0] if law else 2, "tir": law[1] if law else "drop", "refraction": _refraction_of(law)}
     if scan_scene is not None:
         report["hull_to_scan"] = metrics.hausdorff(scene, scan_scene)
     t0 = time.time()
@@ -111,7 +116,7 @@ def run_sharded(HyperParams, data_path="./data/", result_path="./result/", captu
                                            path_law=law)
     k = len(data.ray_view_ids()) if views_per_step == "all" else int(views_per_step)
     report = {"name": name, "resx": data.resx, "resy": data.resy, "views": data.n_total, "hull_faces": int(scene.faces.shape[0]),
-              "world": world, "views_per_step": k, "max_bounces": law[0] if law else 2, "tir": law[1] if law else "drop", "path_route": "fused"}
+              "world": world, "views_per_step": k, "max_bounces": law[0] if law else 2, "tir": law[1] if law else "drop", "refraction": _refraction_of(law), "path_route": "fused"}
     if scan_scene is not None and rank == 0:
         report["hull_to_scan"] = metrics.hausdorff(scene, scan_scene)
     t0 = time.time()
@@ -165,7 +170,9 @@ def main(argv=None):
     ap.add_argument("--max-bounces", type=int, default=2, metavar="K", help="surface interactions per light path, 2..8 (other than 2 / drop: "
                     "Scene.render_paths for the synthetic capture and the fit; implies --dropin)")
     ap.add_argument("--tir", choices=("drop", "reflect"), default="drop", help="what a hit with total internal reflection does to a path")
-    ap.add_argument("--fused-paths", action="store_true", help="with --max-bounces / --tir: fit with the one-pass form of the law "
+    ap.add_argument("--refraction", choices=("reference", "snell"), default="reference", help="how a refracting hit bends the ray: the "
+                    "reference's formula, or Snell's law (alone: the two-bounce path under Snell's law through Scene.render_paths, drop-in)")
+    ap.add_argument("--fused-paths", action="store_true", help="with --max-bounces / --tir / --refraction: fit with the one-pass form of the law "
                     "(Scene.paths_ray_loss_fused) in the one-pass loop, which also runs under torch.distributed.run")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--views-per-step", type=_views_per_step, default=None, metavar="N|all",
@@ -179,9 +186,9 @@ def main(argv=None):
         hp["ior_lr"] = a.fit_ior
     law_kw = None
     if a.fused_paths:         # the law as the explicit keyword: the HyperParams keys keep their defaults, the one-pass loop runs it
-        law_kw = optim.path_law_keyword((a.max_bounces, a.tir), hp, "reconstruct")
+        law_kw = optim.path_law_keyword((a.max_bounces, a.tir, a.refraction), hp, "reconstruct")
     else:
-        hp["max_bounces"], hp["tir"] = a.max_bounces, a.tir
+        hp["max_bounces"], hp["tir"], hp["refraction"] = a.max_bounces, a.tir, a.refraction
     law = optim.path_law(hp)
     from . import dist as ddist
     if a.views_per_step is None and ddist.env_world()[2] == 1:

@@ -32,7 +32,8 @@ extern "C" {
 typedef struct drt_scene drt_scene_t;
 
 const char* drt_last_error(void);
-int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused */
+int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
+                            * 5: drt_render_paths_law_* (law_flags: Snell refraction) */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -226,6 +227,37 @@ int drt_render_paths_ray_loss_fused(drt_scene_t* s, const double* d_verts, const
                                     const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays,
                                     double ior_int, double ior_ext, int max_bounces, int reflect,
                                     double* d_loss, double* d_grad_verts, int64_t* d_n_valid, void* stream);
+
+/* The three calls above with the whole law in one argument: `law_flags` (a combination of the bits below; any other bit is
+ * DRT_E_INVALID) stands where `reflect` stands, every other argument, output and rule is the namesake's.
+ *   DRT_LAW_REFLECT  a hit with total internal reflection mirrors the ray (reflect = 1); unset: it ends the path (reflect = 0).
+ *   DRT_LAW_SNELL    a refracting hit is bent by Snell's law, sin(theta_t) = eta sin(theta_i): cosThetaT =
+ *                    sqrt(max(1 - eta^2 sin2ThetaI, 0)) in place of the reference's sqrt(1 - sin2ThetaI) (Refract, DiffRender.py:42,
+ *                    which gives tan(theta_t) = eta tan(theta_i)); everything else of the bounce -- the hit, the flipped normal, the
+ *                    total-internal-reflection flag, w = eta d + k n, its normalisation, the 1e-5 origin offset -- is unchanged.
+ *                    The adjoint passes no gradient through cosThetaT where it is 0 (instead of NaN); close to the critical angle it
+ *                    grows like 1 / cosThetaT.  Unset: the reference's formula, i.e. the namesake's bits.
+ * drt_render_paths_law_backward must be given the law_flags of the forward whose tape it reverses (DRT_LAW_REFLECT does not change
+ * what it computes: the flags of a completed path are recomputed).  Without DRT_LAW_SNELL the calls run the namesakes' kernels. */
+#define DRT_LAW_REFLECT 1
+#define DRT_LAW_SNELL 2
+int drt_render_paths_law_forward(drt_scene_t* s, const double* d_verts, const double* d_origin,
+                                 const double* d_dir, int64_t n_rays, double ior_int, double ior_ext,
+                                 int max_bounces, int law_flags,
+                                 double* d_out_ori, double* d_out_dir, uint8_t* d_mask,
+                                 int32_t* d_tape, uint8_t* d_hits,
+                                 int32_t* d_valid_idx, int64_t* d_n_valid, void* stream);
+int drt_render_paths_law_backward(drt_scene_t* s, const double* d_verts, const double* d_origin,
+                                  const double* d_dir, int64_t n_rays, double ior_int, double ior_ext,
+                                  int max_bounces, int law_flags,
+                                  const int32_t* d_tape, const uint8_t* d_hits,
+                                  const int32_t* d_valid_idx, const int64_t* d_n_valid,
+                                  const double* d_grad_out_ori, const double* d_grad_out_dir,
+                                  double* d_grad_verts, void* stream);
+int drt_render_paths_law_ray_loss_fused(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir,
+                                        const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays,
+                                        double ior_int, double ior_ext, int max_bounces, int law_flags,
+                                        double* d_loss, double* d_grad_verts, int64_t* d_n_valid, void* stream);
 
 /* ---- Loss_calculator.ray_loss, optim.py:91-108 ------------------------------------------
  * loss = sum over rays with valid & mask of |out_dir - normalize(screen_pixel - out_ori)|^2.

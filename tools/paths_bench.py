@@ -5,10 +5,11 @@
     (b) one-pass Scene.paths_ray_loss_fused + backward()                 (drt_render_paths_ray_loss_fused: nothing dense)
     (c) two-bounce one-pass kernel Scene.ray_loss_fused + backward()     at (2, drop) only: the pipeline the fast loops use today
 
-    python tools/paths_bench.py [--mesh horse] [--res 1024] [--views 0,18,36,54] [--reps 15] [--warmup 3]
+    python tools/paths_bench.py [--mesh horse] [--res 1024] [--views 0,18,36,54] [--reps 15] [--warmup 3] [--refraction reference|snell]
 
 Input as bench.py's: <mesh>_vh x4 (one midpoint subdivision), targets from <mesh>_scan traced with the law under test, 72-camera
-turntable, at the bench camera (2.5 extents) and at 1.1 extents (the object fills the image).  Laws (2, drop), (4, reflect), (8, reflect).
+turntable, at the bench camera (2.5 extents) and at 1.1 extents (the object fills the image).  Laws (2, drop), (4, reflect), (8, reflect),
+each under the refraction formula of --refraction (targets and fit alike; route (c) is always the reference's formula).
 The routes are alternated inside one process on the same tensors, after a warm-up of every route; each timed window is one view through
 one route and ends in a device synchronise; the figure is the median over views x repetitions (min and max alongside).  Prints a table
 and one JSON line."""
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--views", default="0,18,36,54")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--refraction", choices=("reference", "snell"), default="reference")
     a = ap.parse_args()
     view_ids = [int(v) for v in a.views.split(",")]
     res = a.res
@@ -64,7 +66,7 @@ def main():
           "ms per view, forward + loss + backward: median [min .. max]")
     for factor in (2.5, 1.1):
         cams = views.turntable_cameras(center, extent, 72, res, res, distance_factor=factor)
-        for law in LAWS:
+        for law in [l + (a.refraction,) for l in LAWS]:
             data = []
             with torch.no_grad():
                 for k in view_ids:
@@ -72,7 +74,7 @@ def main():
                     oo, od, mk = gt.render_paths(o, d, *law)
                     sp = views.screen_targets(oo, od, mk, cams[k], center, extent).contiguous()
                     data.append((o, d, sp, (sp[:, 0] != 0).contiguous()))
-            routes = [("dense", dense), ("one_pass", one_pass)] + ([("two_bounce_one_pass", two_bounce)] if law == (2, "drop") else [])
+            routes = [("dense", dense), ("one_pass", one_pass)] + ([("two_bounce_one_pass", two_bounce)] if law[:2] == (2, "drop") else [])
             times = {name: [] for name, _ in routes}
             contributing = []
             for rep in range(a.warmup + a.reps):
@@ -87,7 +89,7 @@ def main():
                             times[name].append((time.perf_counter() - t0) * 1e3)
                         if rep == 0 and name == "one_pass":
                             contributing.append(int(scene.last_path_count))
-            row = {"distance_factor": factor, "max_bounces": law[0], "tir": law[1], "contributing_rays_per_view": contributing}
+            row = {"distance_factor": factor, "max_bounces": law[0], "tir": law[1], "refraction": law[2], "contributing_rays_per_view": contributing}
             for name, ts in times.items():
                 row[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "windows": len(ts)}
             results.append(row)
