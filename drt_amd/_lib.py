@@ -46,6 +46,7 @@ SIGNATURES = {
     "drt_render_paths_law_forward": (_c.c_int, [_P, _P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drt_render_paths_law_backward": (_c.c_int, [_P, _P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drt_render_paths_law_ray_loss_fused": (_c.c_int, [_P, _P, _P, _P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _P, _P, _P, _P]),
+    "drt_render_paths_law_ray_loss_ior_fused": (_c.c_int, [_P, _P, _P, _P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _P, _P, _P, _P, _P]),
     "drt_ray_loss": (_c.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "drt_ray_loss_listed": (_c.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "drt_prefill_zero": (_c.c_int, [_P, _P, _I64, _P]),

@@ -1,5 +1,5 @@
 // drt_paths.h -- one camera ray through a refraction path of up to K surface interactions, with optional internal reflection,
-// and its adjoint w.r.t. the vertices.
+// and its adjoint w.r.t. the vertices (and, as functions of their own, the two indices of refraction).
 //
 // The path law (opt-in: Scene.render_paths; DESIGN.md "Paths of up to K interactions").  A camera ray repeats:
 //   trace   closest hit under the tracer contract (float32 cast of the float64 ray); once K interactions are used up the any-hit form
@@ -17,6 +17,7 @@
 //   trace_path_k              forward; records the face of every interaction and their number
 //   path_recompute_backward_k recomputes the path from the camera ray and that face tape, reverses it
 //   path_loss_backward_k      the ray_loss term of a completed path and its adjoint in one go (the one-pass form)
+//   path_recompute_backward_ior_k / path_loss_backward_ior_k   the same two, also w.r.t. the indices of refraction
 // Plain C++ (also compiled by tests/hostsim); the gradient sink is a functor as in drt_path.h.
 #pragma once
 #include "drt_path.h"
@@ -122,6 +123,62 @@ DRT_HD double path_loss_backward_k(const PathCtx& c, d3 o, d3 d, const int32_t* 
     d3 g_dir;
     const double term = ray_loss_term(exit_o, exit_d, screen_pixel, g_dir);
     path_recompute_backward_k<SNELL>(c, o, d, faces, face_stride, n_hits, d3{0.0, 0.0, 0.0}, g_dir, add);
+    return term;
+}
+
+// ---- the same adjoint, also w.r.t. the two indices of refraction --------------------------------------------------------
+// law_backward plus the adjoint of eta of a refracting bounce (bounce_backward_eta / bounce_backward_snell_eta).
+template <bool SNELL>
+DRT_HD void law_backward_eta(const Bounce& b, d3 g_new_o, d3 g_wt, d3& gv0, d3& gv1, d3& gv2, d3& g_o, d3& g_d, double& g_eta) {
+    if constexpr (SNELL) bounce_backward_snell_eta(b, g_new_o, g_wt, gv0, gv1, gv2, g_o, g_d, g_eta);
+    else bounce_backward_eta(b, g_new_o, g_wt, gv0, gv1, gv2, g_o, g_d, g_eta);
+}
+
+// path_recompute_backward_k -- the same recompute from the face tape, the same vertex gradients handed to `add` in the same order -- that
+// also returns d / d (ior_int, ior_ext) (g_int, g_ext; set): every refracting interaction adds its g_eta through eta_to_ior.  A mirrored
+// interaction adds nothing: bounce_reflect never reads eta, and the TIR flag and the `entering` branch carry no gradient, as in torch.
+template <bool SNELL = false, typename Add>
+DRT_HD void path_recompute_backward_ior_k(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 g_ori, d3 g_dir,
+                                          Add add, double& g_int, double& g_ext) {
+    d3 ro[kMaxBounces], rd[kMaxBounces];
+    d3 v0, v1, v2;
+    int32_t vid[3];
+    Bounce b;
+    g_int = 0.0; g_ext = 0.0;
+    if (n_hits > kMaxBounces) n_hits = kMaxBounces;
+    for (int k = 0; k < n_hits; ++k) {
+        ro[k] = o; rd[k] = d;
+        if (k + 1 == n_hits) break;              // (the last interaction is rebuilt by the reverse loop)
+        load_tri64(c, faces[k * face_stride], v0, v1, v2, vid);
+        law_forward<SNELL>(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b);
+        if (b.tir) { d3 no, wr; bounce_reflect(b, o, no, wr); o = no; d = wr; }
+        else { o = b.new_o; d = b.wt; }
+    }
+    const d3 z{0.0, 0.0, 0.0};
+    d3 g_o = g_ori, g_d = g_dir;
+    for (int k = n_hits - 1; k >= 0; --k) {
+        load_tri64(c, faces[k * face_stride], v0, v1, v2, vid);
+        law_forward<SNELL>(ro[k], rd[k], v0, v1, v2, c.ior_ext, c.ior_int, b);
+        d3 ga = z, gb = z, gc = z, g_o_in, g_d_in;
+        if (b.tir) {
+            bounce_reflect_backward(b, g_o, g_d, ga, gb, gc, g_o_in, g_d_in);
+        } else {
+            double g_eta;
+            law_backward_eta<SNELL>(b, g_o, g_d, ga, gb, gc, g_o_in, g_d_in, g_eta);
+            eta_to_ior(b, c.ior_int, c.ior_ext, g_eta, g_int, g_ext);
+        }
+        add(vid[0], ga); add(vid[1], gb); add(vid[2], gc);
+        g_o = g_o_in; g_d = g_d_in;
+    }
+}
+
+// path_loss_backward_k that also returns the IOR partials of the term (unit seed; set).
+template <bool SNELL = false, typename Add>
+DRT_HD double path_loss_backward_ior_k(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 exit_o, d3 exit_d,
+                                       d3 screen_pixel, Add add, double& g_int, double& g_ext) {
+    d3 g_dir;
+    const double term = ray_loss_term(exit_o, exit_d, screen_pixel, g_dir);
+    path_recompute_backward_ior_k<SNELL>(c, o, d, faces, face_stride, n_hits, d3{0.0, 0.0, 0.0}, g_dir, add, g_int, g_ext);
     return term;
 }
 

@@ -18,6 +18,8 @@
 //   k_trace / k_paths_shade      : unchanged (they are handed the workspace rows)
 //   k_paths_collect     all rays : reads the state byte, completed paths -> index list
 //   k_paths_loss_bwd    that list: ray_loss term on the parked exit ray + adjoint (path_loss_backward_k), LossAcc / PathSink
+//   k_paths_loss_bwd_ior that list: in place of k_paths_loss_bwd when the IOR partials are asked for (drt_render_paths_law_ray_loss_ior_fused);
+//                                 VERTS = false: no vertex gradient, no table in LDS
 // The tape needs no -1 preset there: hits[i], written with the last face of a path, bounds what the last kernel reads.
 #include "drt_device.h"
 #include "drt_trace_kernel.h"
@@ -260,6 +262,63 @@ __global__ void __launch_bounds__(256) k_paths_loss_bwd(PathCtx c, const double*
     if (n_valid && cnt) atomicAdd(n_valid, (unsigned long long)cnt);
 }
 
+// k_paths_loss_bwd that also sums d loss / d (ior_int, ior_ext) (path_loss_backward_ior_k): two more LossAcc, summed per
+// thread and per wave and flushed with one atomic per wave into grad_ior[0] / [1] -- float64, or, deterministic, two FxCells (exact, as the
+// loss).  VERTS = false is the calibration mode of a fixed mesh: no vertex gradient is wanted, `add` discards, the kernel has no table in
+// LDS and the compiler drops the vertex chains of the adjoints.
+struct DiscardAdd3 {
+    __device__ __forceinline__ void operator()(int32_t, d3) const {}
+};
+template <bool DET>
+__device__ __forceinline__ double* paths_ior_slot(double* ior, int k) {
+    return DET ? reinterpret_cast<double*>(reinterpret_cast<FxCell*>(ior) + k) : ior + k;
+}
+template <bool DET, bool SNELL, bool VERTS>
+__global__ void __launch_bounds__(256) k_paths_loss_bwd_ior(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir,
+                                                            const double* __restrict__ screen_pixel, int64_t n_rays, int max_bounces,
+                                                            const double* __restrict__ park_ori, const double* __restrict__ park_dir,
+                                                            const int32_t* __restrict__ tape, const uint8_t* __restrict__ hits,
+                                                            const int32_t* __restrict__ list, const unsigned* __restrict__ n_list, double* loss,
+                                                            double* grad_verts, double* grad_ior, unsigned long long* n_valid) {
+    int64_t n = *n_list;
+    if (n > n_rays) n = n_rays;
+    LossAcc<DET> acc, acc_int, acc_ext;
+    unsigned cnt = 0;
+    if constexpr (VERTS) {
+        __shared__ int32_t hkeys[kHashSize];
+        __shared__ double hsums[3 * kHashSize];
+        const PathSink<DET> add{hkeys, hsums, grad_verts};
+        for (int64_t base = blockIdx.x * (int64_t)kPathsBwdBatch; base < n; base += (int64_t)gridDim.x * kPathsBwdBatch) {
+            add.clear();
+            const int64_t end = base + kPathsBwdBatch < n ? base + kPathsBwdBatch : n;
+            for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
+                const int64_t i = list[k];
+                if (i < 0 || i >= n_rays) continue;
+                double gi, ge;
+                acc.add(path_loss_backward_ior_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
+                                                        load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), add, gi, ge));
+                acc_int.add(gi); acc_ext.add(ge);
+                ++cnt;
+            }
+            add.flush();
+        }
+    } else {
+        for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t i = list[k];
+            if (i < 0 || i >= n_rays) continue;
+            double gi, ge;
+            acc.add(path_loss_backward_ior_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
+                                                    load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), DiscardAdd3{}, gi, ge));
+            acc_int.add(gi); acc_ext.add(ge);
+            ++cnt;
+        }
+    }
+    acc.flush(loss);
+    acc_int.flush(paths_ior_slot<DET>(grad_ior, 0));
+    acc_ext.flush(paths_ior_slot<DET>(grad_ior, 1));
+    if (n_valid && cnt) atomicAdd(n_valid, (unsigned long long)cnt);
+}
+
 static PathsWs* ws_of(drt_scene* s) { return static_cast<PathsWs*>(s->paths_ws); }
 
 static int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st, const char* who) {
@@ -335,6 +394,25 @@ static int check_law_flags(int max_bounces, int law_flags) {
         } else {                                                                          \
             if (det_) kern<true, false><<<grid, block, 0, st>>>(__VA_ARGS__);             \
             else kern<false, false><<<grid, block, 0, st>>>(__VA_ARGS__);                 \
+        }                                                                                 \
+    } while (0)
+
+// ... and for k_paths_loss_bwd_ior, whose third is whether the vertex gradient is computed.  Without the table the calibration mode is
+// limited by its registers: kPathsIorBpc blocks per CU fill the waves the compiler's report allows.
+constexpr int kPathsIorBpc = 4;
+#define DET_LAW_VERTS_LAUNCH(kern, snell, verts, grid, block, st, ...)                    \
+    do {                                                                                  \
+        const bool det_ = det_mode();                                                     \
+        const int sel_ = (det_ ? 4 : 0) | ((snell) ? 2 : 0) | ((verts) ? 1 : 0);          \
+        switch (sel_) {                                                                   \
+        case 0: kern<false, false, false><<<grid, block, 0, st>>>(__VA_ARGS__); break;    \
+        case 1: kern<false, false, true><<<grid, block, 0, st>>>(__VA_ARGS__); break;     \
+        case 2: kern<false, true, false><<<grid, block, 0, st>>>(__VA_ARGS__); break;     \
+        case 3: kern<false, true, true><<<grid, block, 0, st>>>(__VA_ARGS__); break;      \
+        case 4: kern<true, false, false><<<grid, block, 0, st>>>(__VA_ARGS__); break;     \
+        case 5: kern<true, false, true><<<grid, block, 0, st>>>(__VA_ARGS__); break;      \
+        case 6: kern<true, true, false><<<grid, block, 0, st>>>(__VA_ARGS__); break;      \
+        default: kern<true, true, true><<<grid, block, 0, st>>>(__VA_ARGS__); break;      \
         }                                                                                 \
     } while (0)
 
@@ -415,11 +493,12 @@ static int paths_backward(drt_scene* s, const double* d_verts, const double* d_o
 
 static int paths_ray_loss_fused(drt_scene* s, const double* d_verts, const double* d_origin, const double* d_dir,
                                 const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays, double ior_int, double ior_ext,
-                                int max_bounces, bool reflect, bool snell, double* d_loss, double* d_grad_verts, int64_t* d_n_valid,
-                                void* stream, const char* who) {
+                                int max_bounces, bool reflect, bool snell, double* d_loss, double* d_grad_verts, double* d_grad_ior,
+                                int64_t* d_n_valid, void* stream, const char* who) {
     if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
     if (n_rays == 0) return DRT_OK;
-    if (!d_verts || !d_origin || !d_dir || !d_screen_pixel || !d_valid || !d_loss || !d_grad_verts) return fail(DRT_E_INVALID, "null pointer argument");
+    // (d_grad_ior: the call that also differentiates the IORs, k_paths_loss_bwd_ior; only there may the vertex gradient be left out)
+    if (!d_verts || !d_origin || !d_dir || !d_screen_pixel || !d_valid || !d_loss || (!d_grad_verts && !d_grad_ior)) return fail(DRT_E_INVALID, "null pointer argument");
     hipStream_t st = (hipStream_t)stream;
     { int rc = ensure_paths_ws(s, n_rays, st, who); if (rc) return rc; }
     { int rc = ensure_paths_fused_ws(s, n_rays, st); if (rc) return rc; }
@@ -437,8 +516,13 @@ static int paths_ray_loss_fused(drt_scene* s, const double* d_verts, const doubl
     trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, snell, park_ori, park_dir, w.hits, w.tape);
     int32_t* const done = w.idx[0];          // (both ping-pong lists are free once the loop has ended)
     k_paths_collect<<<gs, kPathBlock, 0, st>>>(n, w.state, done, w.cnt + kCntValid);
-    DET_LAW_LAUNCH(k_paths_loss_bwd, snell, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_screen_pixel, n_rays, max_bounces, park_ori, park_dir, w.tape, w.hits,
-               done, w.cnt + kCntValid, d_loss, d_grad_verts, reinterpret_cast<unsigned long long*>(d_n_valid));
+    if (d_grad_ior)
+        DET_LAW_VERTS_LAUNCH(k_paths_loss_bwd_ior, snell, d_grad_verts != nullptr, (d_grad_verts ? DRT_BWD_BPC : kPathsIorBpc) * s->n_cu, 256, st, pc, d_origin, d_dir,
+                             d_screen_pixel, n_rays, max_bounces, park_ori, park_dir, w.tape, w.hits, done, w.cnt + kCntValid, d_loss, d_grad_verts, d_grad_ior,
+                             reinterpret_cast<unsigned long long*>(d_n_valid));
+    else
+        DET_LAW_LAUNCH(k_paths_loss_bwd, snell, DRT_BWD_BPC * s->n_cu, 256, st, pc, d_origin, d_dir, d_screen_pixel, n_rays, max_bounces, park_ori, park_dir, w.tape, w.hits,
+                       done, w.cnt + kCntValid, d_loss, d_grad_verts, reinterpret_cast<unsigned long long*>(d_n_valid));
     HIP_TRY(hipGetLastError());
     return DRT_OK;
 }
@@ -471,7 +555,7 @@ int drt_render_paths_ray_loss_fused(drt_scene_t* s, const double* d_verts, const
     CHECK_BUILT(s);
     { int rc = check_law(max_bounces, reflect); if (rc) return rc; }
     return paths_ray_loss_fused(s, d_verts, d_origin, d_dir, d_screen_pixel, d_valid, n_rays, ior_int, ior_ext, max_bounces, reflect != 0, false,
-                                d_loss, d_grad_verts, d_n_valid, stream, "drt_render_paths_ray_loss_fused");
+                                d_loss, d_grad_verts, nullptr, d_n_valid, stream, "drt_render_paths_ray_loss_fused");
 }
 
 int drt_render_paths_law_forward(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir, int64_t n_rays,
@@ -501,8 +585,20 @@ int drt_render_paths_law_ray_loss_fused(drt_scene_t* s, const double* d_verts, c
     CHECK_BUILT(s);
     { int rc = check_law_flags(max_bounces, law_flags); if (rc) return rc; }
     return paths_ray_loss_fused(s, d_verts, d_origin, d_dir, d_screen_pixel, d_valid, n_rays, ior_int, ior_ext, max_bounces,
-                                (law_flags & DRT_LAW_REFLECT) != 0, (law_flags & DRT_LAW_SNELL) != 0, d_loss, d_grad_verts, d_n_valid, stream,
+                                (law_flags & DRT_LAW_REFLECT) != 0, (law_flags & DRT_LAW_SNELL) != 0, d_loss, d_grad_verts, nullptr, d_n_valid, stream,
                                 "drt_render_paths_law_ray_loss_fused");
+}
+
+int drt_render_paths_law_ray_loss_ior_fused(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir,
+                                            const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays, double ior_int, double ior_ext,
+                                            int max_bounces, int law_flags, double* d_loss, double* d_grad_verts, double* d_grad_ior,
+                                            int64_t* d_n_valid, void* stream) {
+    CHECK_BUILT(s);
+    { int rc = check_law_flags(max_bounces, law_flags); if (rc) return rc; }
+    if (!d_grad_ior) return fail(DRT_E_INVALID, "d_grad_ior is NULL: this call differentiates the IORs (drt_render_paths_law_ray_loss_fused does not)");
+    return paths_ray_loss_fused(s, d_verts, d_origin, d_dir, d_screen_pixel, d_valid, n_rays, ior_int, ior_ext, max_bounces,
+                                (law_flags & DRT_LAW_REFLECT) != 0, (law_flags & DRT_LAW_SNELL) != 0, d_loss, d_grad_verts, d_grad_ior, d_n_valid, stream,
+                                "drt_render_paths_law_ray_loss_ior_fused");
 }
 
 }  // extern "C"

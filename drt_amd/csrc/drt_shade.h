@@ -199,6 +199,20 @@ DRT_HD void bounce_backward_eta(const Bounce& b, d3 g_new_o, d3 g_wt, d3& gv0, d
     g_eta = dot(g_w, b.d) + g_k * b.ci;
 }
 
+// bounce_backward_snell plus the adjoint of eta (g_eta; set).  Under Snell eta enters three times: w = eta*d + k*n, k = eta*ci - ct and
+// ct = sqrt(max(1 - (eta*eta)*s2, 0)).  The last chain, as torch reverses it: g_arg = g_ct / (2*ct), g_(eta*eta) = -s2 * g_arg,
+// g_eta += 2*eta * g_(eta*eta) = -g_ct * eta*s2/ct = g_k * eta*s2/ct -- behind bounce_backward_snell's own guard: a refracting bounce whose
+// argument rounds to <= 0 gets nothing through ct instead of NaN.  g_w and g_k are recomputed with bounce_backward_snell's own statements
+// (the same bits, which the compiler shares); bounce_backward_snell itself is left alone.
+DRT_HD void bounce_backward_snell_eta(const Bounce& b, d3 g_new_o, d3 g_wt, d3& gv0, d3& gv1, d3& gv2, d3& g_o, d3& g_d, double& g_eta) {
+    bounce_backward_snell(b, g_new_o, g_wt, gv0, gv1, gv2, g_o, g_d);
+    const d3 G = g_wt + 1e-5 * g_new_o;
+    const d3 g_w = (G - dot(b.wt, G) * b.wt) / b.wl;
+    const double g_k = dot(g_w, b.n);
+    g_eta = dot(g_w, b.d) + g_k * b.ci;
+    if (b.ct > 0.0) g_eta += g_k * ((b.eta * b.s2) / b.ct);
+}
+
 // eta -> (ior_int, ior_ext) through bounce_forward's `entering` branch (sg = 1: eta = ext / int; sg = -1: eta = int / ext); the
 // branch and the TIR flag carry no gradient, as in torch.  Torch's quotient rule: d/d num = g / den, d/d den = -g * ((num / den) / den).
 // Accumulates into g_int / g_ext.

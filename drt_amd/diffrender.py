@@ -40,7 +40,7 @@ def cache_report(reset=False):
     calls that read and verified every ray, `grid_off` calls without whole-image hints / with GRID_CACHE off, `grid_unattachable` ray tensors
     that take no attributes), output recycling (`recycle_take` calls that rendered into pooled buffers; `recycle_miss_held` the pool had an
     entry of that size but the caller still holds, or wrote, its outputs; `recycle_miss_empty` nothing pooled yet; `recycle_off_capture` inside
-    a graph capture; `recycle_off_small` below RECYCLE_MIN_RAYS), hit seeds (`seed_armed`), the one-pass K-interaction term (`paths_fused_calls`), and the
+    a graph capture; `recycle_off_small` below RECYCLE_MIN_RAYS), hit seeds (`seed_armed`), the one-pass K-interaction term (`paths_fused_calls`; with the IOR gradient `paths_ior_fused_calls`), and the
     switches in force."""
     out = dict(_stats)
     out["switches"] = {"GRID_CACHE": GRID_CACHE, "RECYCLE_OUTPUTS": RECYCLE_OUTPUTS, "storage_use_count_available": hasattr(torch._C, "_storage_Use_Count"),
@@ -805,6 +805,51 @@ class _PathsRayLossFused(torch.autograd.Function):
         return grad_v * g_loss, None, None, None, None, None, None, None, None
 
 
+class _PathsRayLossIorFused(torch.autograd.Function):
+    """_PathsRayLossFused that also differentiates the indices of refraction (drt_render_paths_law_ray_loss_ior_fused):
+    the vertex gradient -- unless ``want_verts`` is off: no array is handed over and the library runs its kernel without the gradient
+    table -- and the two IOR partials are computed here with a unit seed; the backward only scales them.  ``ior_int`` / ``ior_ext``
+    stand for the tensors autograd tracks (or None); ``ior`` carries their float values."""
+
+    @staticmethod
+    def forward(ctx, vertices, ior_int, ior_ext, origin, ray_dir, screen_pixel, valid, scene, ior, max_bounces, law_flags, want_verts):
+        v = _f64c(vertices.detach(), "vertices")
+        o = _f64c(origin, "origin")
+        d = _f64c(ray_dir, "ray_dir")
+        sp = _f64c(screen_pixel, "screen_pixel")
+        va = _flag_bytes(valid, "valid", o.shape[0])
+        loss = det.scalar(o.device)
+        grad_v = det.acc(v) if want_verts else None
+        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=o.device))
+        count = torch.zeros((), dtype=torch.int64, device=o.device)
+        with _on(o.device):
+            _lib.check(_lib.lib().drt_render_paths_law_ray_loss_ior_fused(
+                scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), o.shape[0],
+                ior[0], ior[1], max_bounces, law_flags, loss.data_ptr(), _lib.ptr(grad_v), grad_ior.data_ptr(), count.data_ptr(), _stream()))
+        scene.last_path_count = count
+        ctx.ior_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
+        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
+        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v), det.value(grad_ior, torch.empty(2, dtype=torch.float64)))
+        return det.value(loss)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        grad_v, both = ctx.saved_tensors
+        g_ior = [None, None]
+        for k in (0, 1):
+            if ctx.needs_input_grad[1 + k]:
+                shape, dtype, dev = ctx.ior_like[k]
+                g_ior[k] = (both[k] * g_loss).reshape(shape).to(dtype=dtype, device=dev)
+        if grad_v is None or not ctx.needs_input_grad[0]:
+            g_v = None
+        elif det.SINK is not None and ctx.wide is not None:
+            det.SINK.append((ctx.wide, g_loss))
+            g_v = None
+        else:
+            g_v = grad_v * g_loss
+        return g_v, g_ior[0], g_ior[1], None, None, None, None, None, None, None, None, None
+
+
 def ray_loss(out_ori, out_dir, mask, screen_pixel, valid):
     """sum over valid & mask rays of |out_dir - normalize(screen_pixel - out_ori.detach())|^2."""
     link = getattr(out_dir, "_drt_link", None) if SPARSE_LOSS_GRAD else None
@@ -997,14 +1042,19 @@ class Scene(StepwiseMixin):
         return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), _law_flags(tir, refraction))
 
     @staticmethod
-    def _check_paths_call(who, origin, ray_dir, max_bounces, tir, refraction="reference"):
-        """The argument checks of the K-interaction calls; returns the (intIOR, extIOR) floats."""
+    def _check_law(max_bounces, tir, refraction):
+        """The checks of the law itself, shared by every K-interaction call."""
         if isinstance(max_bounces, bool) or int(max_bounces) != max_bounces or not 2 <= int(max_bounces) <= 8:
             raise ValueError(f"max_bounces must be an integer in 2..8, got {max_bounces!r}")
         if tir not in ("drop", "reflect"):
             raise ValueError(f"tir must be 'drop' or 'reflect', got {tir!r}")
         if not isinstance(refraction, str) or refraction not in ("reference", "snell"):
             raise ValueError(f"refraction must be 'reference' or 'snell', got {refraction!r}")
+
+    @staticmethod
+    def _check_paths_call(who, origin, ray_dir, max_bounces, tir, refraction="reference"):
+        """The argument checks of the K-interaction calls; returns the (intIOR, extIOR) floats."""
+        Scene._check_law(max_bounces, tir, refraction)
         if _wants_input_grads(origin, ray_dir, intIOR, extIOR):
             raise NotImplementedError(f"{who} differentiates the vertices only: origin, ray_dir and the IORs must not require grad "
                                       "(render_transparent has those gradients for the two-bounce path)")
@@ -1022,6 +1072,31 @@ class Scene(StepwiseMixin):
         ior = self._check_paths_call("paths_ray_loss_fused", origin, ray_dir, max_bounces, tir, refraction)
         _stats["paths_fused_calls"] += 1
         return _PathsRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, int(max_bounces), _law_flags(tir, refraction))
+
+    def paths_ray_loss_ior_fused(self, origin, ray_dir, screen_pixel, valid, ior_int, ior_ext=None, max_bounces=4, tir="reflect",
+                                 refraction="reference", vertices=True):
+        """``paths_ray_loss_fused`` that is also differentiable w.r.t. the indices of refraction: the loss as a scalar,
+        its vertex gradient AND d loss / d (ior_int, ior_ext) computed alongside with a unit seed and scaled in the backward pass.
+        The IORs are ARGUMENTS here: ``ior_int`` / ``ior_ext`` are floats or 0-dim float64 tensors (CPU or GPU; each is read to the
+        host once per call, so a call with a tensor IOR cannot be captured), ``ior_ext=None`` is the module's ``extIOR`` read as a
+        float; the module globals are not consulted otherwise.  Differentiable w.r.t. ``self.vertices`` when ``vertices=True`` and
+        w.r.t. whichever IOR tensors require grad.  ``vertices=False`` is the calibration of a fixed mesh: no vertex gradient is
+        computed (the kernel runs without its gradient table) and ``self.vertices`` receives none.  Rays that require grad raise
+        NotImplementedError.  ``origin`` may be a RayBinding: its rays are used, nothing else.  The law and its checks are those of
+        ``paths_ray_loss_fused``; afterwards ``self.last_path_count`` is the number of contributing rays."""
+        if isinstance(origin, RayBinding):
+            origin, ray_dir = origin.origin, origin.ray_dir
+        Scene._check_law(max_bounces, tir, refraction)
+        if _wants_input_grads(origin, ray_dir):
+            raise NotImplementedError("paths_ray_loss_ior_fused differentiates the vertices and the IORs: origin and ray_dir must not require "
+                                      "grad (render_transparent has those gradients for the two-bounce path)")
+        if ior_ext is None:
+            ior_ext = _ior_host(extIOR, "extIOR")
+        ior = (_ior_host(ior_int, "ior_int"), _ior_host(ior_ext, "ior_ext"))
+        tracked = tuple(x if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
+        _stats["paths_ior_fused_calls"] += 1
+        return _PathsRayLossIorFused.apply(self.vertices if vertices else self.vertices.detach(), *tracked, origin, ray_dir, screen_pixel, valid,
+                                           self, ior, int(max_bounces), _law_flags(tir, refraction), bool(vertices))
 
     def ray_loss_fused(self, origin, ray_dir, screen_pixel, valid):
         """ray_loss of this view without materialising out_ori/out_dir/mask.  The fused kernel differentiates the vertices only: when

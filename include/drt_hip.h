@@ -33,7 +33,7 @@ typedef struct drt_scene drt_scene_t;
 
 const char* drt_last_error(void);
 int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
-                            * 5: drt_render_paths_law_* (law_flags: Snell refraction) */
+                            * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -258,6 +258,18 @@ int drt_render_paths_law_ray_loss_fused(drt_scene_t* s, const double* d_verts, c
                                         const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays,
                                         double ior_int, double ior_ext, int max_bounces, int law_flags,
                                         double* d_loss, double* d_grad_verts, int64_t* d_n_valid, void* stream);
+
+/* drt_render_paths_law_ray_loss_fused that also differentiates the two indices of refraction: d_grad_ior, two accumulators -- d loss /
+ * d ior_int, then d loss / d ior_ext, unit seed -- that are ADDED to: two float64, or, in deterministic mode, two accumulator cells laid
+ * out as those of drt_render_backward_ray_loss_inputs.  Every refracting interaction of a completed path contributes through
+ * eta = ior_i / ior_t (under either refraction formula); a mirrored one contributes nothing, and the total-internal-reflection flag and
+ * the entering / leaving branch carry no gradient.  d_grad_verts may be NULL: no vertex gradient is computed then (the calibration of a
+ * fixed mesh: a kernel without the gradient table); otherwise it receives what the namesake writes.  d_grad_ior = NULL, a bad law_flags
+ * or a bad max_bounces is DRT_E_INVALID; n_rays = 0 is DRT_OK and touches nothing.  Stream, workspace and capture rules: the namesake's. */
+int drt_render_paths_law_ray_loss_ior_fused(drt_scene_t* s, const double* d_verts, const double* d_origin, const double* d_dir,
+                                            const double* d_screen_pixel, const uint8_t* d_valid, int64_t n_rays,
+                                            double ior_int, double ior_ext, int max_bounces, int law_flags,
+                                            double* d_loss, double* d_grad_verts, double* d_grad_ior, int64_t* d_n_valid, void* stream);
 
 /* ---- Loss_calculator.ray_loss, optim.py:91-108 ------------------------------------------
  * loss = sum over rays with valid & mask of |out_dir - normalize(screen_pixel - out_ori)|^2.
