@@ -23,7 +23,7 @@ import time
 
 import torch
 
-from . import captured_data, diffrender as Render, mesh_io, metrics, optim, views
+from . import captured_data, diffrender as Render, mesh_io, metrics, optim, views, visual_hull
 
 
 def _refraction_of(law):
@@ -31,7 +31,7 @@ def _refraction_of(law):
 
 
 def run(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, fused=True, output=True, device=0, n_views=72,
-        views_per_step=None, ior_start=None, path_law=None):
+        views_per_step=None, ior_start=None, path_law=None, hull_from_capture=None):
     """``views_per_step=None``: the single-process loop (optim.optimize).  An int, or "all" (one epoch of the refraction schedule per
     iteration), goes through optim.optimize_sharded on every rank of the default process group (one process without one).
     ``HyperParams["ior_lr"] > 0``: the IOR is fitted too (the drop-in loop, optim.optimize), starting at ``ior_start`` (default
@@ -41,28 +41,38 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
     ``path_law=(K, tir)`` (the keyword of optim.optimize / optimize_sharded; the ``HyperParams`` keys stay at their defaults): the same
     law for the capture, and the fit runs it in the ONE-PASS loop (unless ``fused=False``).  Either spelling may carry the refraction
     formula (``HyperParams["refraction"]``, or a third element of the keyword: "reference" / "snell"); the report echoes it.  ``report["path_route"]`` says which route the
-    refraction term took: "fused" (one-pass kernels) or "dropin"."""
+    refraction term took: "fused" (one-pass kernels) or "dropin".
+    ``hull_from_capture=N``: do not read ``<name>_vh.ply`` as the start; build the visual hull of the run's own capture on an N-corner grid
+    (drt_amd.visual_hull) and start from that; ``report["hull"]`` describes it.  Single process only (a rank holds only its own views)."""
     law_kw = optim.path_law_keyword(path_law, HyperParams, "reconstruct")
     law = optim.path_law(HyperParams) or law_kw
     if views_per_step is not None or torch.distributed.is_available() and torch.distributed.is_initialized():
+        if hull_from_capture:
+            raise ValueError(HULL_NEEDS_ONE_PROCESS)
         return run_sharded(HyperParams, data_path, result_path, capture, res, output, device, n_views, views_per_step or 1, path_law=law_kw)
     name = HyperParams["name"]
     hull_path = os.path.join(data_path, f"{name}_vh.ply")
     scan_path = os.path.join(data_path, f"{name}_scan.ply")
     Render.intIOR = HyperParams["IOR"]
-    scene = Render.Scene(hull_path, device)
+    scene = None if hull_from_capture else Render.Scene(hull_path, device)
     scan_scene = Render.Scene(scan_path, device) if os.path.exists(scan_path) else None
     if capture is not None:
         data = captured_data.get_data(HyperParams, path=capture)
     else:
         resx = resy = int(res or 512)
         Render.resx, Render.resy = resx, resy
-        gt = scan_scene if scan_scene is not None else Render.Scene(views.displaced_ground_truth(scene.mesh, 0.5, 0), device)
+        gt = scan_scene if scan_scene is not None else Render.Scene(
+            views.displaced_ground_truth(scene.mesh if scene is not None else mesh_io.load(hull_path), 0.5, 0), device)
         center, extent = views.mesh_frame(gt.mesh.vertices)
         data = captured_data.SyntheticData(gt, center, extent, resx, resy, num_view=min(HyperParams["num_view"], n_views), n_total=n_views, name=name,
                                            path_law=law)
+    hull = {}
+    if hull_from_capture:
+        scene = Render.Scene(visual_hull.visual_hull(data, resolution=int(hull_from_capture), report=hull), device)
     report = {"name": name, "resx": data.resx, "resy": data.resy, "views": data.n_total, "hull_faces": int(scene.faces.shape[0]),
               "max_bounces": law[0] if law else 2, "tir": law[1] if law else "drop", "refraction": _refraction_of(law)}
+    if hull_from_capture:
+        report.update(hull_source="capture", hull=hull)
     if scan_scene is not None:
         report["hull_to_scan"] = metrics.hausdorff(scene, scan_scene)
     t0 = time.time()
@@ -86,6 +96,10 @@ def run(HyperParams, data_path="./data/", result_path="./result/", capture=None,
     scene.mesh.export(out)
     report["result"] = out
     return scene, report
+
+
+HULL_NEEDS_ONE_PROCESS = ("--hull-from-capture builds the hull from ALL views of the capture and a rank holds only its own: write the hull first with "
+                          "`python -m drt_amd.visual_hull --name NAME -o DATA/NAME_vh.ply` (one process), then run the ranks without the flag")
 
 
 def run_sharded(HyperParams, data_path="./data/", result_path="./result/", capture=None, res=None, output=True, device=0, n_views=72,
@@ -178,6 +192,9 @@ def main(argv=None):
     ap.add_argument("--views-per-step", type=_views_per_step, default=None, metavar="N|all",
                     help="refraction views per iteration (all: every view of the schedule once) on the multi-rank loop; "
                          "under torch.distributed.run the default is 1")
+    ap.add_argument("--hull-from-capture", type=int, nargs="?", const=256, default=None, metavar="N",
+                    help="start from the visual hull of the run's own capture, built on an N-corner grid (default 256), instead of reading "
+                         "<name>_vh.ply; single process only")
     a = ap.parse_args(argv)
     import numpy as np
     np.random.seed(a.seed)
@@ -191,9 +208,11 @@ def main(argv=None):
         hp["max_bounces"], hp["tir"], hp["refraction"] = a.max_bounces, a.tir, a.refraction
     law = optim.path_law(hp)
     from . import dist as ddist
+    if a.hull_from_capture is not None and (a.views_per_step is not None or ddist.env_world()[2] > 1):
+        raise SystemExit(HULL_NEEDS_ONE_PROCESS)
     if a.views_per_step is None and ddist.env_world()[2] == 1:
         _, report = run(hp, a.data_path, a.result_path, a.capture, a.res, fused=not (a.dropin or a.fit_ior > 0), n_views=a.views,
-                        ior_start=a.ior_start, path_law=law_kw)
+                        ior_start=a.ior_start, path_law=law_kw, hull_from_capture=a.hull_from_capture)
         print(json.dumps(report))
         return
     if a.dropin or a.fit_ior > 0 or law is not None:

@@ -33,7 +33,8 @@ typedef struct drt_scene drt_scene_t;
 
 const char* drt_last_error(void);
 int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
-                            * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused */
+                            * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused;
+                            * 7: drt_hull_field / drt_hull_mark / drt_hull_emit */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -609,6 +610,27 @@ int drt_edge_tables(const int64_t* d_faces, int64_t n_faces, const double* d_ver
 int drt_subdivide_midpoint(const int64_t* d_faces, int64_t n_faces, const double* d_verts, int64_t n_verts,
                            const int64_t* d_edges, int64_t n_edges, const int32_t* d_row2edge, int round_f32,
                            int64_t* d_faces_out, double* d_verts_out, void* stream);
+
+/* ---- the visual hull of a capture's silhouette masks (csrc/drt_hull.h states the law) ----------------------
+ * A dense grid of nx x ny x nz corners (each count in [3, 1024]); corner (i, j, k) lies at lo + cell * (i, j, k) and has the linear index
+ * (i * ny + j) * nz + k.  All pointers are device pointers; everything is enqueued on `stream`, nothing synchronises; a bad argument
+ * gives DRT_E_INVALID with a message that names it.
+ * drt_hull_field: d_masks uint8 [n_views, height, width] (nonzero = object), d_proj float64 [n_views, 3, 4] = K R[:3, :] per view ->
+ * d_field float32 [nx, ny, nz]: the minimum over the views of the bilinear mask sample at the corner's projection; a view that does not
+ * see the corner counts as 0 (keep_outside = 0, "carve") or is skipped (1, "keep"); corners on the six boundary planes are 0.
+ * drt_hull_mark: per corner, d_edge_mask uint8 (bit c - 1: the lattice edge to the corner at offset code c = 4 dx + 2 dy + dz crosses
+ * `level`, inside <=> field > (float)level), d_n_vert uint8 (its set bits) and d_n_tri uint8 (triangles of the cell that starts there).
+ * drt_hull_emit: d_v_inc / d_t_inc int32 = INCLUSIVE prefix sums of d_n_vert / d_n_tri over the linear index, n_verts / n_faces their
+ * totals -> d_verts float64 [n_verts, 3], d_faces int32 [n_faces, 3]: marching tetrahedra on the Kuhn subdivision, a closed oriented
+ * manifold with outward normals, vertices ordered by (corner, code), triangles by (cell, tetrahedron).  Nothing is written beyond the
+ * two totals. */
+int drt_hull_field(const uint8_t* d_masks, int n_views, int height, int width, const double* d_proj, double lo_x, double lo_y, double lo_z,
+                   double cell, int nx, int ny, int nz, int keep_outside, float* d_field, void* stream);
+int drt_hull_mark(const float* d_field, int nx, int ny, int nz, double level, uint8_t* d_edge_mask, uint8_t* d_n_vert, uint8_t* d_n_tri,
+                  void* stream);
+int drt_hull_emit(const float* d_field, int nx, int ny, int nz, double lo_x, double lo_y, double lo_z, double cell, double level,
+                  const uint8_t* d_edge_mask, const int32_t* d_v_inc, const int32_t* d_t_inc, int64_t n_verts, int64_t n_faces,
+                  double* d_verts, int32_t* d_faces, void* stream);
 
 /* ---- measurement (bench.py's live per-kernel timing) --------------------------------------------
  * When enabled (on = 1; on = 2 additionally collects the traversal statistics below, which perturbs
