@@ -9,6 +9,8 @@ from fractions import Fraction
 
 import numpy as np
 
+import fx_cases as fx
+
 
 def _from(hs, x):
     hi, lo, fl = ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_uint32()
@@ -59,3 +61,37 @@ def test_any_order_gives_the_same_bits_and_the_correctly_rounded_sum(hostsim):
     exact = sum((Fraction(int(Fraction(float(v)) * 2 ** 80), 2 ** 80) for v in x), Fraction(0))
     assert ref == float(exact)
     assert abs(ref - math.fsum(x)) <= 20000 * 2.0 ** -80 + abs(ref) * 2.0 ** -52
+
+
+def test_conversion_edges_against_python_integers(hostsim):
+    """tests/fx_cases.py: the thresholds, the unit, the low word's carry pattern, subnormals, zeros, infinities and NaNs of either sign
+    and payload -- the list the device is held to as well (test_gpu_fixed_device.py)."""
+    for x in fx.CONVERSION_EDGES:
+        f = fx.flags_of(x)
+        assert _from(hostsim, x) == (0 if f else fx.q(x), f), x.hex() if x == x else x
+    assert _from(hostsim, fx.HUGE) == (0, 2) and _from(hostsim, math.nextafter(fx.HUGE, 0.0)) == ((2 ** 53 - 1) << 73, 0)
+    assert _from(hostsim, -1.5 * 2.0 ** -80) == (-1, 0) and _from(hostsim, math.nextafter(2.0 ** -80, 0.0)) == (0, 0)
+    rnd = random.Random(4)
+    for _ in range(20000):                                              # q() is the frexp-and-shift form of the definition
+        x = rnd.choice([-1, 1]) * rnd.random() * 2.0 ** rnd.uniform(-120, 46)
+        if abs(x) < fx.HUGE:
+            assert fx.q(x) == int(Fraction(x) * 2 ** 80)
+
+
+def test_rounding_edges_against_python_integers(hostsim):
+    """Ties at every leading-one position with an even and an odd kept bit, round-ups that carry out of an all-ones field, the exact range,
+    -2^127, +-(2^127 - 1), +-1 and every flag combination: bit for bit."""
+    cases = fx.finalize_edges()
+    assert len(cases) > 380
+    for v, f in cases:
+        assert fx.bits_of(_to(hostsim, v, f)) == fx.value_bits(v, f), (v, f)
+    assert fx.value_bits(-(1 << 127)) == fx.bits_of(-2.0 ** 47) and fx.value_bits(((1 << 54) - 1) << 60) == fx.bits_of(2.0 ** 34)
+
+
+def test_the_device_harness_compiles_for_gfx950():
+    """tests/devsim/fx_device.hip instantiates the production structs (GradAdd3, PathSink, LossAcc) on their own: a change of their
+    interfaces shows here, without a GPU."""
+    so = fx.build_devsim(force=True)
+    lib = ctypes.CDLL(so)
+    for name in ("dv_direct", "dv_sink_det", "dv_sink_f64", "dv_loss"):
+        assert hasattr(lib, name)
