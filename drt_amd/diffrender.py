@@ -33,7 +33,7 @@ from ._util import _f64c, _flag_bytes, _stats, _warn_once, _warned  # noqa: F401
 from .optix_mesh import optix_mesh, _stream, _on
 from .stepwise import Intersection, StepwiseMixin  # noqa: F401  (Dintersect / refract_ray / trace2 / project_vert)
 from .silhouette import (LazyColumn, LazyDiff, LazyGather, LazyIndex, LazyOutput, LazySum, LazyTerm, SampleSet, SilhouetteEdges,  # noqa: F401
-                         _Dihedral, _EdgeSample, _SmLossFused, _VhLossFused, _VhTermLazy, force, pack_camera)
+                         _Dihedral, _EdgeSample, _SmLossFused, _VhLossFused, _VhTermLazy, enqueue_sm_term, enqueue_vh_term, force, pack_camera)
 
 def cache_report(reset=False):
     """Counters of the transparent caches of this module: grid verdict cache (`grid_trust` calls that relied on a verdict, `grid_establish`
@@ -741,57 +741,50 @@ class _RayLoss(torch.autograd.Function):
         return None, g, None, None, None, None
 
 
+def enqueue_ray_term(scene, vertices, origin, ray_dir, target, valid, law, loss_ptr, grad_ptr, count_ptr=None, ior=None, grid=None):
+    """Enqueues ONE view's refraction term -- loss and d loss / d vertices (unit seed), nothing dense written -- on the current stream;
+    the one place that packs the arguments of drt_render_ray_loss_fused and drt_render_paths_ray_loss_fused.  ``law=None``: the two-bounce
+    kernel with the grid verdict of the ray tensors (``grid``: a verdict the caller already has, a RayBinding's), seed arming and tile
+    hint; a normalised law tuple (K, tir[, refraction]): the K-interaction kernel under ``_law_flags``.  ``loss_ptr`` / ``grad_ptr`` /
+    ``count_ptr`` are raw device addresses the kernels ADD into (float64, or fixed-point cells in deterministic mode; int64 count, may
+    be None); ``ior``: (interior, exterior) floats, the module's IORs without it.  The caller is inside ``_on(device)``.  Returns the
+    tensors whose memory the enqueued kernels read: the caller keeps them alive until the work is done."""
+    o, d, sp = _f64c(origin, "origin"), _f64c(ray_dir, "ray_dir"), _f64c(target, "screen_pixel")
+    n = o.shape[0]
+    va = _flag_bytes(valid, "valid", n)
+    h = scene.optix_mesh._h
+    if ior is None:
+        ior = _ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR")
+    if law is not None:
+        flags = _law_flags(law[1], law[2] if len(law) > 2 else "reference")
+        _lib.check(_paths_entry("drt_render_paths_ray_loss_fused", flags)(
+            h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n, ior[0], ior[1], law[0], flags,
+            loss_ptr, grad_ptr, count_ptr, _stream()))
+        return [o, d, sp, va]
+    if grid is None:
+        grid = _grid_cache(origin, ray_dir, n, *_tile_hint(n)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
+    _arm_seed(h, grid, n)
+    _lib.check(_lib.lib().drt_render_ray_loss_fused(
+        h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n, ior[0], ior[1],
+        loss_ptr, grad_ptr, count_ptr, *_tile_hint(n), grid[0], _lib.ptr(grid[1]), _stream()))
+    return [o, d, sp, va]
+
+
 class _RenderRayLossFused(torch.autograd.Function):
-    """render_transparent + ray_loss + d/d vertices in ONE kernel pass (nothing dense written)."""
+    """render_transparent + ray_loss + d/d vertices in ONE kernel pass (nothing dense written): ``enqueue_ray_term`` into accumulators of
+    its own -- with ``law`` (a normalised law tuple) under the K-interaction law of ``render_paths``, and ``scene.last_path_count`` is
+    then the call's number of contributing rays.  The gradient is computed in the forward pass; the backward only scales it."""
 
     @staticmethod
-    def forward(ctx, vertices, origin, ray_dir, screen_pixel, valid, scene, ior_int, ior_ext, grid=(0, None)):
+    def forward(ctx, vertices, origin, ray_dir, screen_pixel, valid, scene, ior, law, grid):
         v = _f64c(vertices.detach(), "vertices")
-        o = _f64c(origin, "origin")
-        d = _f64c(ray_dir, "ray_dir")
-        sp = _f64c(screen_pixel, "screen_pixel")
-        va = _flag_bytes(valid, "valid", o.shape[0])
-        loss = det.scalar(o.device)
+        loss = det.scalar(v.device)
         grad_v = det.acc(v)
-        ior = (_ior_host(ior_int, "intIOR"), _ior_host(ior_ext, "extIOR"))
-        with _on(o.device):
-            _arm_seed(scene.optix_mesh._h, grid, o.shape[0])
-            _lib.check(_lib.lib().drt_render_ray_loss_fused(
-                scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), o.shape[0],
-                ior[0], ior[1], loss.data_ptr(), grad_v.data_ptr(), None, *_tile_hint(o.shape[0]), grid[0], _lib.ptr(grid[1]), _stream()))
-        ctx.wide = grad_v if grad_v.dtype == torch.int64 else None
-        ctx.save_for_backward(det.value(grad_v, v))
-        return det.value(loss)
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        (grad_v,) = ctx.saved_tensors
-        if det.SINK is not None and ctx.wide is not None:
-            det.SINK.append((ctx.wide, g_loss))
-            return None, None, None, None, None, None, None, None, None
-        return grad_v * g_loss, None, None, None, None, None, None, None, None
-
-
-class _PathsRayLossFused(torch.autograd.Function):
-    """render_paths + ray_loss + d/d vertices of one view in ONE call (drt_render_paths_ray_loss_fused or, under Snell, its ``_law``
-    namesake: nothing dense written).  The gradient is computed here, under ``law_flags``; the backward only scales it."""
-
-    @staticmethod
-    def forward(ctx, vertices, origin, ray_dir, screen_pixel, valid, scene, ior, max_bounces, law_flags):
-        v = _f64c(vertices.detach(), "vertices")
-        o = _f64c(origin, "origin")
-        d = _f64c(ray_dir, "ray_dir")
-        sp = _f64c(screen_pixel, "screen_pixel")
-        va = _flag_bytes(valid, "valid", o.shape[0])
-        loss = det.scalar(o.device)
-        grad_v = det.acc(v)
-        count = torch.zeros((), dtype=torch.int64, device=o.device)
-        with _on(o.device):
-            _lib.check(_paths_entry("drt_render_paths_ray_loss_fused", law_flags)(
-                scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), o.shape[0],
-                ior[0], ior[1], max_bounces, law_flags, loss.data_ptr(), grad_v.data_ptr(), count.data_ptr(), _stream()))
-        scene.last_path_count = count
-        ctx.law_flags = law_flags
+        count = torch.zeros((), dtype=torch.int64, device=v.device) if law is not None else None
+        with _on(v.device):
+            enqueue_ray_term(scene, v, origin, ray_dir, screen_pixel, valid, law, loss.data_ptr(), grad_v.data_ptr(), _lib.ptr(count), ior, grid)
+        if law is not None:
+            scene.last_path_count = count
         ctx.wide = grad_v if grad_v.dtype == torch.int64 else None
         ctx.save_for_backward(det.value(grad_v, v))
         return det.value(loss)
@@ -806,7 +799,7 @@ class _PathsRayLossFused(torch.autograd.Function):
 
 
 class _PathsRayLossIorFused(torch.autograd.Function):
-    """_PathsRayLossFused that also differentiates the indices of refraction (drt_render_paths_law_ray_loss_ior_fused):
+    """_RenderRayLossFused under a law that also differentiates the indices of refraction (drt_render_paths_law_ray_loss_ior_fused):
     the vertex gradient -- unless ``want_verts`` is off: no array is handed over and the library runs its kernel without the gradient
     table -- and the two IOR partials are computed here with a unit seed; the backward only scales them.  ``ior_int`` / ``ior_ext``
     stand for the tensors autograd tracks (or None); ``ior`` carries their float values."""
@@ -1071,7 +1064,7 @@ class Scene(StepwiseMixin):
             origin, ray_dir = origin.origin, origin.ray_dir
         ior = self._check_paths_call("paths_ray_loss_fused", origin, ray_dir, max_bounces, tir, refraction)
         _stats["paths_fused_calls"] += 1
-        return _PathsRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, int(max_bounces), _law_flags(tir, refraction))
+        return _RenderRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, (int(max_bounces), tir, refraction), None)
 
     def paths_ray_loss_ior_fused(self, origin, ray_dir, screen_pixel, valid, ior_int, ior_ext=None, max_bounces=4, tir="reflect",
                                  refraction="reference", vertices=True):
@@ -1106,11 +1099,11 @@ class Scene(StepwiseMixin):
             _stats["fused_fallback_inputs"] += 1
             out_ori, out_dir, mask = self.render_transparent(origin, ray_dir)
             return ray_loss(out_ori, out_dir, mask, screen_pixel, valid)
+        ior = _ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR")
         if isinstance(origin, RayBinding):
             b = origin
-            return _RenderRayLossFused.apply(self.vertices, b.origin, b.ray_dir, screen_pixel, valid, self, intIOR, extIOR, b._grid())
-        grid = _grid_cache(origin, ray_dir, origin.shape[0], *_tile_hint(origin.shape[0])) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
-        return _RenderRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, intIOR, extIOR, grid)
+            return _RenderRayLossFused.apply(self.vertices, b.origin, b.ray_dir, screen_pixel, valid, self, ior, None, b._grid())
+        return _RenderRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, None, None)
 
     # ------------------------------------------------------------------ smoothness branch
     def dihedral_angle(self):
@@ -1119,7 +1112,7 @@ class Scene(StepwiseMixin):
 
     def sm_loss_fused(self):
         """sum -log(1 + cos dihedral) (reference optim.py:82-89) with its gradient in one kernel pass."""
-        return _SmLossFused.apply(self.vertices, self.E2F)
+        return _SmLossFused.apply(self.vertices, self)
 
     # ------------------------------------------------------------------ silhouette branch
     def silhouette_edge(self, origin: torch.Tensor):

@@ -13,6 +13,10 @@ Differences from the reference, all outside the per-view math:
   * multi-GPU: ``full_batch_step`` shards views over ranks and all-reduces the vertex gradient
     once per step (drt_amd.dist); the reference is single-GPU and one view per step.  ``optimize_sharded`` is the whole
     loop on N ranks (ShardedIteration: all three terms, one exchange per iteration; the remesh on rank 0, broadcast).
+
+The loops share their parts: ``check_loop_config`` (every refusal), ``pass_schedule`` / ``resolve_remesh`` / ``run_steps`` (the pass loop)
+and ONE iteration class (FusedIteration; ShardedIteration is its form with an exchange), whose terms go through the enqueue functions the
+autograd Functions use (diffrender.enqueue_ray_term, silhouette.enqueue_vh_term / enqueue_sm_term).
 """
 from __future__ import annotations
 
@@ -61,15 +65,6 @@ def law_flags(law):
     return Render._law_flags(law[1], law[2] if len(law) > 2 else "reference")
 
 
-_law_of = path_law          # (the loops take a keyword of that name)
-
-
-def _refuse_path_law(hp, who):
-    if path_law(hp) is not None:
-        raise NotImplementedError(f"HyperParams['max_bounces'] / ['tir'] other than 2 / 'drop' are not supported by {who}: use the drop-in "
-                                  "loop optimize(..., fused=False)")
-
-
 def path_law_keyword(law, hp, who):
     """The ``path_law=(max_bounces, tir)`` or ``(max_bounces, tir, refraction)`` keyword of the loops, normalised by the rules of
     ``path_law``: None when absent or (2, "drop") -- today's kernels -- else (int K, tir), or (int K, tir, "snell") under Snell's law
@@ -96,6 +91,26 @@ def path_law_keyword(law, hp, who):
     if path_law(hp) is not None:
         raise ValueError("the path law was given twice: HyperParams['max_bounces'] / ['tir'] and the path_law keyword")
     return law
+
+
+def check_loop_config(hp, law, who, one_pass, loop=False):
+    """The one validation of a loop's configuration, before anything touches the scene or the capture; returns the normalised
+    ``path_law`` keyword (``path_law_keyword``).  ``who`` names the caller in the messages.  ``one_pass``: the caller runs the one-pass
+    terms only, for which the ``HyperParams`` spelling of a law -- the drop-in route -- is refused.  ``loop``: the caller is a whole loop
+    (optimize, optimize_sharded), which has ``HyperParams["ior_lr"]`` to honour; the iteration classes never read it.  The
+    ``HyperParams`` refusals fire first, bad values of either spelling raise ValueError."""
+    ior_lr = float(hp.get("ior_lr", 0) or 0)
+    if loop and one_pass and ior_lr > 0:
+        raise NotImplementedError(f"HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by {who}: use the drop-in loop "
+                                  "optimize(..., fused=False)")
+    if path_law(hp) is not None:
+        if one_pass:
+            raise NotImplementedError(f"HyperParams['max_bounces'] / ['tir'] other than 2 / 'drop' are not supported by {who}: use the "
+                                      "drop-in loop optimize(..., fused=False)")
+        if loop and ior_lr > 0:
+            raise NotImplementedError("HyperParams['max_bounces'] / ['tir'] cannot be combined with ior_lr > 0: Scene.render_paths "
+                                      "differentiates the vertices only")
+    return path_law_keyword(law, hp, who)
 
 
 def loss_weights(hp, resy, mean_len):
@@ -154,19 +169,15 @@ class Loss_calculator:
         if bind is not None:
             origin, ray_dir = bind(self.scene, view_id), None
         law = path_law(self.HyperParams)
-        if law is not None:                 # paths of up to K interactions (Scene.render_paths): dense outputs, ray_loss's dense gradient
-            if self.fused:
-                _refuse_path_law(self.HyperParams, "the fused terms")
+        if law is not None and self.fused:       # (the HyperParams keys mean the drop-in route)
+            check_loop_config(self.HyperParams, None, "the fused terms", one_pass=True)
+        law = law or self.law
+        if law is not None:                 # paths of up to K interactions
+            if self.fused:                  # (the path_law keyword: the one-pass form with the one-pass terms)
+                return self.scene.paths_ray_loss_fused(origin, ray_dir, target, valid, *law)
             if ray_dir is None:
                 origin, ray_dir = origin.origin, origin.ray_dir
-            exit_o, exit_d, exit_mask = self.scene.render_paths(origin, ray_dir, *law)
-            return Render.ray_loss(exit_o, exit_d, exit_mask, target, valid)
-        if self.law is not None:            # the path_law keyword: the one-pass form with the one-pass terms, else the route above
-            if self.fused:
-                return self.scene.paths_ray_loss_fused(origin, ray_dir, target, valid, *self.law)
-            if ray_dir is None:
-                origin, ray_dir = origin.origin, origin.ray_dir
-            exit_o, exit_d, exit_mask = self.scene.render_paths(origin, ray_dir, *self.law)
+            exit_o, exit_d, exit_mask = self.scene.render_paths(origin, ray_dir, *law)        # dense outputs, ray_loss's dense gradient
             return Render.ray_loss(exit_o, exit_d, exit_mask, target, valid)
         if self.fused:
             return self.scene.ray_loss_fused(origin, ray_dir, target, valid)
@@ -268,6 +279,13 @@ class FusedLimitSGD:
                                                       int(self.nesterov), int(first), self.max_abs, _stream()))
 
 
+def sharded_loss_weights(hp, resy, mean_len, views_per_step=1):
+    """The weights of an iteration of ``views_per_step`` refraction views: loss_weights with the refraction weight divided by the step's
+    view count (the refraction term is the MEAN over the step's views); ``views_per_step = 1`` gives loss_weights exactly."""
+    w_ray, w_vh, w_sm = loss_weights(hp, resy, mean_len)
+    return (w_ray / views_per_step if views_per_step != 1 else w_ray), w_vh, w_sm
+
+
 class FusedIteration:
     """One iteration of the reference's loop (optim.py:198-215: vertices = init + parameter, update_verticex, all_loss, backward,
     limit_hook, SGD) on the one-pass kernels WITHOUT the autograd graph around them.
@@ -275,31 +293,71 @@ class FusedIteration:
     With ``Loss_calculator(fused=True)`` every term already returns its loss together with d term / d vertices; autograd only
     multiplies those by the weights and adds them up -- ~15 tiny torch ops, three Function nodes and a backward pass whose HOST cost
     (0.7 ms) exceeds the GPU time of the whole iteration at the reference's size (one 960x1280 refraction view, 8 silhouette views).
-    Here the three entry points write into one [3, V, 3] buffer, the weighted sum is one matrix product and the update is the
-    one-kernel limit_hook + SGD(nesterov): the same kernels, inputs and arithmetic, ~10 host calls.  The silhouette and smoothness
-    terms run on a side stream beside the refraction term.  Same view schedule generators as Loss_calculator.
-    ``path_law=(K, tir)``: the refraction term is drt_render_paths_ray_loss_fused (paths of up to K interactions, one pass)."""
+    Here ``step()`` has three parts.  It draws the iteration's views (``draw``: same schedule generators as Loss_calculator, or the
+    ``schedule=(ray_view, silh_view)`` pair a pass loop carries from stepper to stepper).  It enqueues the terms with the functions the
+    autograd Functions use (diffrender.enqueue_ray_term / enqueue_vh_term / enqueue_sm_term) into ONE zeroed accumulator block of
+    3n + 3 values -- term k's gradient element i at k n + i, loss k at 3n + k; float64, or fixed-point cells in deterministic mode
+    (drt_amd/det.py) -- the silhouette and smoothness terms on a side stream beside the refraction term.  And it runs the tail: the
+    weighted sum, limit_hook and SGD(nesterov) in one kernel (drt_limit_sgd_step3; in deterministic mode after the cells' conversion).
+    ``path_law=(K, tir)``: the refraction term is the K-interaction law's one-pass kernel.  What the enqueued kernels read stays
+    referenced (``_vertices``, ``_keep``) until the next step replaces it."""
 
     N_SILHOUETTE_VIEWS = 8
+    sharded = False          # (ShardedIteration: evaluate the owned views only, ONE exchange over the ranks in the tail)
 
-    def __init__(self, scene, data, HyperParams, lr, concurrent=True, path_law=None):
-        from . import _lib
-        _refuse_path_law(HyperParams, "FusedIteration")
-        self.law = path_law_keyword(path_law, HyperParams, "FusedIteration")
+    def __init__(self, scene, data, HyperParams, lr, concurrent=True, path_law=None, schedule=None):
+        self._init(scene, data, HyperParams, lr, 1, concurrent, path_law, schedule)
+
+    def _init(self, scene, data, hp, lr, views_per_step, concurrent, path_law, schedule):
+        from . import _lib, det
+        self.law = check_loop_config(hp, path_law, type(self).__name__, one_pass=True)
         self._lib = _lib
-        self.scene, self.data, self.hp = scene, data, HyperParams
-        self.ray_view = data.ray_view_generator()
-        self.silh_view = data.silh_view_generator()
+        self.scene, self.data, self.hp = scene, data, hp
+        self.k = int(views_per_step)
+        if self.k < 1:
+            raise ValueError("views_per_step must be >= 1")
+        self.rank, self.world = ddist.rank_world() if self.sharded else (0, 1)
+        self.ray_view, self.silh_view = schedule if schedule is not None else (data.ray_view_generator(), data.silh_view_generator())
+        self.own_ray = self.own_silh = None
+        if self.sharded:
+            self.own_ray = set(ddist.owned_views(data.ray_view_ids(), self.rank, self.world))
+            self.own_silh = set(ddist.owned_views(data.silh_view_ids(), self.rank, self.world))
         dev = scene.vertices.device
         self.init_vertices = scene.vertices.detach().clone()
         self.parameter = torch.zeros_like(self.init_vertices)
-        self.grads = torch.zeros((3,) + tuple(self.init_vertices.shape), dtype=Float, device=dev)
-        self.losses = torch.zeros(3, dtype=Float, device=dev)
-        self.total = torch.zeros((), dtype=Float, device=dev)
+        n = self.n = self.init_vertices.numel()
+        shape = tuple(self.init_vertices.shape)
+        self.det = det.on()
+        words = det._CELL_WORDS if self.det else 1
+        acc = self.acc = torch.zeros((3 * n + 3) * words, dtype=torch.int64 if self.det else Float, device=dev)
+        self._fills = [acc]                                                    # what a step zeroes
+        self._g_ptr = [acc.data_ptr() + 8 * words * k * n for k in range(3)]
+        self._l_ptr = [acc.data_ptr() + 8 * words * (3 * n + k) for k in range(3)]
         self.total_grad = torch.empty_like(self.init_vertices)
-        self.buf = torch.empty_like(self.init_vertices) if HyperParams["momentum"] != 0 else None
+        if not self.sharded:
+            # drt_limit_sgd_step3 reads the block's float64 values: the block itself, or (deterministic) what the cells convert to
+            vals = torch.empty(3 * n + 3, dtype=Float, device=dev) if self.det else acc
+            self.grads, self.losses = vals[:3 * n].view((3,) + shape), vals[3 * n:]
+            self._finalize = [(acc[:3 * n * words], vals[:3 * n]), (acc[3 * n * words:], vals[3 * n:])] if self.det else []
+        elif self.det:
+            self.limbs = torch.empty((3 * n + 3) * 4, dtype=torch.int64, device=dev)      # the exchange: ONE drt_fx_to_limbs launch
+            self.losses = torch.zeros(3, dtype=Float, device=dev)
+        else:
+            # the exchange is [weighted partial gradient (n), loss parts (3)]: the terms add their losses straight into its tail (the
+            # block's own three loss values stay unused)
+            self.grads = acc[:3 * n].view((3,) + shape)
+            self.xbuf = torch.zeros(n + 3, dtype=Float, device=dev)
+            self.losses, self.total_grad = self.xbuf[n:], self.xbuf[:n].view(shape)
+            self._l_ptr = [self.xbuf.data_ptr() + 8 * (n + k) for k in range(3)]
+            self._fills.append(self.losses)
+        self.total = torch.zeros((), dtype=Float, device=dev)
+        self.buf = torch.empty_like(self.init_vertices) if hp["momentum"] != 0 else None
         self.first = True
-        self.lr, self.momentum = float(lr), float(HyperParams["momentum"])
+        self.lr, self.momentum = float(lr), float(hp["momentum"])
+        self.n_allreduce = 0
+        self.collective_events = []
+        self.last_owned = (0, 0)
+        self._keep = []
         # The side stream of the silhouette / smoothness terms must not share a hardware queue with the caller's stream: a process gets four
         # queues, further streams are multiplexed onto them, and a stream that lands in the caller's queue sits BEHIND the barrier with
         # which the caller's stream waits for the refraction term -- the terms then run one after the other whatever the streams say
@@ -307,156 +365,6 @@ class FusedIteration:
         # this size and has a queue of its own.
         self.side = None
         if concurrent:
-            import ctypes
-            h = ctypes.c_void_p()
-            rc = _lib.lib().drt_internal_stream(scene.optix_mesh._h, 2, ctypes.byref(h))
-            self.side = torch.cuda.ExternalStream(h.value, device=dev) if rc == 0 and h.value else torch.cuda.Stream(device=dev)
-        self._w = None
-
-    def step(self):
-        """Runs the iteration; returns (weighted total, parts [ray, vh, sm]) as device tensors of THIS iteration (views of
-        buffers that the next call overwrites: read them, or clone them, before stepping again)."""
-        from . import diffrender as R
-        from .optix_mesh import _stream
-        lib, check, ptr = self._lib.lib(), self._lib.check, self._lib.ptr
-        scene, hp, data = self.scene, self.hp, self.data
-        dev = self.init_vertices.device
-        with torch.no_grad(), torch.cuda.device(dev):
-            vertices = self.init_vertices + self.parameter
-            scene.update_verticex(vertices)
-            from . import det
-            if det.on():
-                # deterministic mode: the three terms accumulate into fixed-point cells (drt_amd/det.py), converted once all of them are in
-                if getattr(self, "_g_acc", None) is None:
-                    self._g_acc = torch.zeros(self.grads.numel() * 3, dtype=torch.int64, device=dev)
-                    self._l_acc = torch.zeros(3 * 3, dtype=torch.int64, device=dev)
-                self._g_acc.zero_()
-                self._l_acc.zero_()
-                per = self.grads[0].numel() * 3
-                g_ptr = [self._g_acc[k * per:].data_ptr() for k in range(3)]
-                l_ptr = [self._l_acc[3 * k:].data_ptr() for k in range(3)]
-            else:
-                self.grads.zero_()
-                self.losses.zero_()
-                g_ptr = [self.grads[k].data_ptr() for k in range(3)]
-                l_ptr = [self.losses[k:].data_ptr() for k in range(3)]
-            h = scene.optix_mesh._h
-            main = torch.cuda.current_stream()
-            if self.side is not None:
-                self.side.wait_stream(main)
-            if hp["ray_w"] != 0:
-                target, valid, _, origin, ray_dir, _ = data.get_view(next(self.ray_view))
-                n = origin.shape[0]
-                o, d, sp = R._f64c(origin, "origin"), R._f64c(ray_dir, "ray_dir"), R._f64c(target, "screen_pixel")
-                va = R._flag_bytes(valid, "valid", n)
-                if self.law is not None:
-                    check(R._paths_entry("drt_render_paths_ray_loss_fused", law_flags(self.law))(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n,
-                                                              float(R.intIOR), float(R.extIOR), self.law[0], law_flags(self.law),
-                                                              l_ptr[0], g_ptr[0], None, _stream()))
-                else:
-                    grid = R._grid_cache(origin, ray_dir, n, *R._tile_hint(n)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
-                    R._arm_seed(h, grid, n)
-                    check(lib.drt_render_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), n,
-                                                        float(R.intIOR), float(R.extIOR), l_ptr[0], g_ptr[0], None,
-                                                        *R._tile_hint(n), grid[0], ptr(grid[1]), _stream()))
-            ctx = torch.cuda.stream(self.side) if self.side is not None else torch.no_grad()
-            with ctx:
-                if hp["sm_w"] != 0:        # (first: it needs no tree, so it runs while the build finishes; the silhouette probes wait for the tree)
-                    check(lib.drt_sm_loss_fused(vertices.data_ptr(), scene.E2F.data_ptr(), scene.E2F.shape[0], l_ptr[2], g_ptr[2], _stream()))
-                if hp["vh_w"] != 0:
-                    import ctypes
-                    k = self.N_SILHOUETTE_VIEWS
-                    cams, orgs, softs = (ctypes.c_void_p * k)(), (ctypes.c_void_p * k)(), (ctypes.c_void_p * k)()
-                    keep = []
-                    for j in range(k):
-                        _, _, soft_mask, origin, _, camera_M = data.get_view(next(self.silh_view))
-                        cam, o3, sm_ = R.pack_camera(camera_M), R._f64c(origin[0], "origin"), R._f64c(soft_mask, "soft_mask")
-                        keep += [cam, o3, sm_]
-                        cams[j], orgs[j], softs[j] = cam.data_ptr(), o3.data_ptr(), sm_.data_ptr()
-                    check(lib.drt_vh_loss_fused(h, vertices.data_ptr(), scene.Edges.data_ptr(), scene.E2F.data_ptr(), scene.E2F.shape[0], k,
-                                                cams, orgs, softs, int(data.resx), int(data.resy), 1, l_ptr[1], g_ptr[1], _stream()))
-            if self.side is not None:
-                main.wait_stream(self.side)
-            if det.on():
-                det.value_into(self._g_acc, self.grads)
-                det.value_into(self._l_acc, self.losses)
-            w = loss_weights(hp, data.resy, scene.mean_len)
-            if self._w is None or self._w[0] != w:
-                self._w = (w, torch.tensor(w, dtype=Float, device=dev))
-            wv = self._w[1]
-            # d total / d vertices (= d total / d parameter) = the weighted sum of the three terms' gradients, limit_hook, SGD(nesterov): one kernel
-            check(lib.drt_limit_sgd_step3(self.parameter.data_ptr(), self.total_grad.data_ptr(), ptr(self.buf), self.parameter.numel(), self.lr,
-                                          self.momentum, 1, int(self.first), 1.0, self.grads.data_ptr(), wv.data_ptr(), self.losses.data_ptr(),
-                                          self.total.data_ptr(), _stream()))
-            total = self.total
-            self.first = False
-            self._vertices = vertices          # (alive until the next step: kernels enqueued above read it)
-        return total, self.losses
-
-
-def sharded_loss_weights(hp, resy, mean_len, views_per_step=1):
-    """The weights of a ShardedIteration: loss_weights with the refraction weight divided by the step's view count (the refraction term
-    is the MEAN over the step's views); ``views_per_step = 1`` gives loss_weights exactly."""
-    w_ray, w_vh, w_sm = loss_weights(hp, resy, mean_len)
-    return (w_ray / views_per_step if views_per_step != 1 else w_ray), w_vh, w_sm
-
-
-class ShardedIteration:
-    """The rank-local form of FusedIteration: one iteration of the pass loop on ``world`` ranks with ONE collective.
-
-    Every rank draws the same schedule -- ``views_per_step`` refraction views, then the reference's 8 silhouette views, from the capture's
-    generators (same seed on every rank) -- and evaluates only the views it owns (drt_amd.dist.owner: a view's position in the schedule's
-    sorted id list, modulo world); the smoothness term is rank 0's.  The rank's contribution goes into one contiguous buffer, all-reduced
-    once: in float64 mode the weighted partial gradient and the three loss parts (n + 3 values; drt_weight_terms3), in deterministic mode
-    the exchange words of the three terms' gradient cells and the three loss cells ((3n + 3) x 4 int64; drt_fx_to_limbs).  After it every
-    rank applies the same weighted sum, limit_hook and SGD(nesterov) (drt_limit_sgd_step_total / drt_fx_limbs_limit_sgd_step3), so the
-    parameters stay bit-identical across ranks without a broadcast.  A rank that owns nothing in an iteration still joins the exchange.
-    With one rank and ``views_per_step = 1`` this is FusedIteration: same schedule, kernels, weights and update (in deterministic mode the
-    same bits).  ``n_allreduce`` counts the collectives issued; ``collective_events`` holds (start, end) CUDA events around each of them
-    until the caller reads them.  ``path_law=(K, tir)``: every owned refraction view goes through drt_render_paths_ray_loss_fused
-    into the same accumulators; the exchange and the step kernels are the same."""
-
-    N_SILHOUETTE_VIEWS = 8
-
-    def __init__(self, scene, data, HyperParams, lr, views_per_step=1, concurrent=True, path_law=None):
-        from . import _lib, det
-        self._lib = _lib
-        _refuse_path_law(HyperParams, "ShardedIteration")
-        self.law = path_law_keyword(path_law, HyperParams, "ShardedIteration")
-        self.scene, self.data, self.hp = scene, data, HyperParams
-        self.k = int(views_per_step)
-        if self.k < 1:
-            raise ValueError("views_per_step must be >= 1")
-        self.rank, self.world = ddist.rank_world()
-        self.ray_view = data.ray_view_generator()
-        self.silh_view = data.silh_view_generator()
-        ray_ids, silh_ids = data.ray_view_ids(), data.silh_view_ids()
-        self.own_ray = set(ddist.owned_views(ray_ids, self.rank, self.world))
-        self.own_silh = set(ddist.owned_views(silh_ids, self.rank, self.world))
-        dev = scene.vertices.device
-        self.init_vertices = scene.vertices.detach().clone()
-        self.parameter = torch.zeros_like(self.init_vertices)
-        n = self.n = self.init_vertices.numel()
-        self.det = det.on()
-        if self.det:
-            # one contiguous block of 3n + 3 cells (term k, element i at cell k n + i; loss k at cell 3n + k): ONE drt_fx_to_limbs launch
-            self.cells = torch.zeros((3 * n + 3) * det._CELL_WORDS, dtype=torch.int64, device=dev)
-            self.limbs = torch.empty((3 * n + 3) * 4, dtype=torch.int64, device=dev)
-            self.losses = torch.zeros(3, dtype=Float, device=dev)
-            self.total_grad = torch.empty_like(self.init_vertices)
-        else:
-            self.grads = torch.zeros((3,) + tuple(self.init_vertices.shape), dtype=Float, device=dev)
-            self.xbuf = torch.zeros(n + 3, dtype=Float, device=dev)        # [weighted partial gradient (n), loss parts (3)]: the exchange
-            self.losses = self.xbuf[n:]
-            self.total_grad = self.xbuf[:n].view(self.init_vertices.shape)
-        self.total = torch.zeros((), dtype=Float, device=dev)
-        self.buf = torch.empty_like(self.init_vertices) if HyperParams["momentum"] != 0 else None
-        self.first = True
-        self.lr, self.momentum = float(lr), float(HyperParams["momentum"])
-        self.n_allreduce = 0
-        self.collective_events = []
-        self.side = None
-        if concurrent:          # (the library's idle pipeline stream: a hardware queue of its own, see FusedIteration)
             import ctypes
             h = ctypes.c_void_p()
             rc = _lib.lib().drt_internal_stream(scene.optix_mesh._h, 2, ctypes.byref(h))
@@ -471,94 +379,77 @@ class ShardedIteration:
         return ray, silh
 
     def step(self):
-        """Runs the iteration; returns (weighted total, parts [ray, vh, sm]) of the WHOLE iteration (all ranks) as device tensors that the
-        next call overwrites."""
-        import ctypes
-        from . import det, diffrender as R
+        """Runs the iteration; returns (weighted total, parts [ray, vh, sm]) of the WHOLE iteration (all ranks) as device tensors of
+        THIS iteration (views of buffers that the next call overwrites: read them, or clone them, before stepping again)."""
+        from . import det
         from .optix_mesh import _stream
         lib, check, ptr = self._lib.lib(), self._lib.check, self._lib.ptr
         scene, hp, data, n = self.scene, self.hp, self.data, self.n
         dev = self.init_vertices.device
+        # 1. the iteration's views: everything drawn, or this rank's share of it
         ray_ids, silh_ids = self.draw()
-        ray_ids = [v for v in ray_ids if v in self.own_ray]
-        silh_ids = [v for v in silh_ids if v in self.own_silh]
+        if self.sharded:
+            ray_ids = [v for v in ray_ids if v in self.own_ray]
+            silh_ids = [v for v in silh_ids if v in self.own_silh]
         self.last_owned = (len(ray_ids), len(silh_ids))       # (this rank's share of the iteration: refraction views, silhouette views)
         with torch.no_grad(), torch.cuda.device(dev):
             vertices = self.init_vertices + self.parameter
             scene.update_verticex(vertices)
-            if self.det:
-                self.cells.zero_()
-                words = det._CELL_WORDS
-                g_ptr = [self.cells[k * n * words:].data_ptr() for k in range(3)]
-                l_ptr = [self.cells[(3 * n + k) * words:].data_ptr() for k in range(3)]
-            else:
-                self.grads.zero_()
-                self.xbuf[n:].zero_()
-                g_ptr = [self.grads[k].data_ptr() for k in range(3)]
-                l_ptr = [self.xbuf[n + k:].data_ptr() for k in range(3)]
-            h = scene.optix_mesh._h
+            # 2. the terms, into the zeroed block
+            for t in self._fills:
+                t.zero_()
+            g_ptr, l_ptr = self._g_ptr, self._l_ptr
             main = torch.cuda.current_stream()
             if self.side is not None:
                 self.side.wait_stream(main)
             keep = []
             for v in ray_ids:
                 target, valid, _, origin, ray_dir, _ = data.get_view(v)
-                nr = origin.shape[0]
-                o, d, sp = R._f64c(origin, "origin"), R._f64c(ray_dir, "ray_dir"), R._f64c(target, "screen_pixel")
-                va = R._flag_bytes(valid, "valid", nr)
-                keep += [o, d, sp, va]
-                if self.law is not None:
-                    check(R._paths_entry("drt_render_paths_ray_loss_fused", law_flags(self.law))(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), nr,
-                                                              float(R.intIOR), float(R.extIOR), self.law[0], law_flags(self.law),
-                                                              l_ptr[0], g_ptr[0], None, _stream()))
-                    continue
-                grid = R._grid_cache(origin, ray_dir, nr, *R._tile_hint(nr)) if origin.is_contiguous() and ray_dir.is_contiguous() else (0, None)
-                R._arm_seed(h, grid, nr)
-                check(lib.drt_render_ray_loss_fused(h, vertices.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), nr,
-                                                    float(R.intIOR), float(R.extIOR), l_ptr[0], g_ptr[0], None,
-                                                    *R._tile_hint(nr), grid[0], ptr(grid[1]), _stream()))
-            ctx = torch.cuda.stream(self.side) if self.side is not None else torch.no_grad()
-            with ctx:
-                if hp["sm_w"] != 0 and self.rank == 0:     # one rank only: the sum over ranks is the term itself, not world times it
-                    check(lib.drt_sm_loss_fused(vertices.data_ptr(), scene.E2F.data_ptr(), scene.E2F.shape[0], l_ptr[2], g_ptr[2], _stream()))
+                keep += Render.enqueue_ray_term(scene, vertices, origin, ray_dir, target, valid, self.law, l_ptr[0], g_ptr[0])
+            with torch.cuda.stream(self.side) if self.side is not None else torch.no_grad():
+                # (the smoothness term first: it needs no tree, so it runs while the build finishes; the silhouette probes wait for the tree.
+                # On one rank only: the sum over ranks is the term itself, not world times it)
+                if hp["sm_w"] != 0 and self.rank == 0:
+                    Render.enqueue_sm_term(scene, vertices, l_ptr[2], g_ptr[2])
                 if silh_ids:
-                    m = len(silh_ids)
-                    cams, orgs, softs = (ctypes.c_void_p * m)(), (ctypes.c_void_p * m)(), (ctypes.c_void_p * m)()
-                    for j, v in enumerate(silh_ids):
+                    views_ = []
+                    for v in silh_ids:
                         _, _, soft_mask, origin, _, camera_M = data.get_view(v)
-                        cam, o3, sm_ = R.pack_camera(camera_M), R._f64c(origin[0], "origin"), R._f64c(soft_mask, "soft_mask")
-                        keep += [cam, o3, sm_]
-                        cams[j], orgs[j], softs[j] = cam.data_ptr(), o3.data_ptr(), sm_.data_ptr()
-                    check(lib.drt_vh_loss_fused(h, vertices.data_ptr(), scene.Edges.data_ptr(), scene.E2F.data_ptr(), scene.E2F.shape[0], m,
-                                                cams, orgs, softs, int(data.resx), int(data.resy), 1, l_ptr[1], g_ptr[1], _stream()))
+                        views_.append((camera_M, origin[0], soft_mask))
+                    keep += Render.enqueue_vh_term(scene, vertices, views_, data.resx, data.resy, True, l_ptr[1], g_ptr[1])
             if self.side is not None:
                 main.wait_stream(self.side)
+            # 3. the tail: d total / d vertices (= d total / d parameter) = the weighted sum of the three terms' gradients, limit_hook,
+            # SGD(nesterov) -- one kernel, or two around the exchange
             w = sharded_loss_weights(hp, data.resy, scene.mean_len, self.k)
             if self._w is None or self._w[0] != w:
                 self._w = (w, torch.tensor(w, dtype=Float, device=dev))
             wv = self._w[1]
-            ev = None
-            if ddist.active():
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            if self.det:
-                check(lib.drt_fx_to_limbs(self.cells.data_ptr(), 3 * n + 3, self.limbs.data_ptr(), _stream()))
-                self._exchange(self.limbs, ev)
+            step = (self.lr, self.momentum, 1, int(self.first), 1.0)
+            if not self.sharded:
+                for cells, vals in self._finalize:
+                    det.value_into(cells, vals)
+                check(lib.drt_limit_sgd_step3(self.parameter.data_ptr(), self.total_grad.data_ptr(), ptr(self.buf), n, *step, self.grads.data_ptr(),
+                                              wv.data_ptr(), self.losses.data_ptr(), self.total.data_ptr(), _stream()))
+            elif self.det:
+                check(lib.drt_fx_to_limbs(self.acc.data_ptr(), 3 * n + 3, self.limbs.data_ptr(), _stream()))
+                self._exchange(self.limbs)
                 check(lib.drt_fx_limbs_limit_sgd_step3(self.limbs.data_ptr(), n, self.parameter.data_ptr(), self.total_grad.data_ptr(), ptr(self.buf),
-                                                       self.lr, self.momentum, 1, int(self.first), 1.0, wv.data_ptr(), self.losses.data_ptr(),
-                                                       self.total.data_ptr(), _stream()))
+                                                       *step, wv.data_ptr(), self.losses.data_ptr(), self.total.data_ptr(), _stream()))
             else:
                 check(lib.drt_weight_terms3(self.grads.data_ptr(), wv.data_ptr(), n, self.xbuf.data_ptr(), _stream()))
-                self._exchange(self.xbuf, ev)
-                check(lib.drt_limit_sgd_step_total(self.parameter.data_ptr(), self.xbuf.data_ptr(), ptr(self.buf), n, self.lr, self.momentum, 1,
-                                                   int(self.first), 1.0, wv.data_ptr(), self.xbuf[n:].data_ptr(), self.total.data_ptr(), _stream()))
+                self._exchange(self.xbuf)
+                check(lib.drt_limit_sgd_step_total(self.parameter.data_ptr(), self.xbuf.data_ptr(), ptr(self.buf), n, *step, wv.data_ptr(),
+                                                   self.losses.data_ptr(), self.total.data_ptr(), _stream()))
             self.first = False
             self._vertices, self._keep = vertices, keep      # (alive until the next step: kernels enqueued above read them)
         return self.total, self.losses
 
-    def _exchange(self, t, ev):
+    def _exchange(self, t):
         """The iteration's one collective (a sum over ranks; nothing to do for a single process)."""
         if not ddist.active():
             return
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
         ddist.allreduce_sum_(t)
         ev[1].record()
@@ -575,6 +466,59 @@ class ShardedIteration:
         return s
 
 
+class ShardedIteration(FusedIteration):
+    """The rank-local form of FusedIteration: one iteration of the pass loop on ``world`` ranks with ONE collective.
+
+    Every rank draws the same schedule -- ``views_per_step`` refraction views, then the reference's 8 silhouette views, from the capture's
+    generators (same seed on every rank) -- and evaluates only the views it owns (drt_amd.dist.owner: a view's position in the schedule's
+    sorted id list, modulo world); the smoothness term is rank 0's.  The rank's contribution is all-reduced once: in float64 mode the
+    weighted partial gradient and the three loss parts (n + 3 values; drt_weight_terms3), in deterministic mode the exchange words of
+    the whole accumulator block ((3n + 3) x 4 int64; drt_fx_to_limbs).  After it every rank applies the same weighted sum, limit_hook and
+    SGD(nesterov) (drt_limit_sgd_step_total / drt_fx_limbs_limit_sgd_step3), so the parameters stay bit-identical across ranks without a
+    broadcast.  A rank that owns nothing in an iteration still joins the exchange.  The two-kernel tail runs with one rank too: with one
+    rank and ``views_per_step = 1`` this is FusedIteration with another tail (in deterministic mode the same bits).  ``n_allreduce``
+    counts the collectives issued; ``collective_events`` holds (start, end) CUDA events around each of them until the caller reads them.
+    ``last_owned``: this rank's (refraction, silhouette) view counts of the last step."""
+
+    sharded = True
+
+    def __init__(self, scene, data, HyperParams, lr, views_per_step=1, concurrent=True, path_law=None, schedule=None):
+        self._init(scene, data, HyperParams, lr, views_per_step, concurrent, path_law, schedule)
+
+
+def pass_schedule(hp):
+    """(i_pass, remesh_len, lr) of every pass (reference optim.py:191-193): both interpolated harmonically from their start to their end
+    value over the passes; one pass alone runs at the start values."""
+    n = hp["Pass"]
+    for i_pass in range(n):
+        if n > 1:
+            yield i_pass, interp_R(hp["start_len"], hp["end_len"], i_pass, n), interp_R(hp["start_lr"], hp["lr_decay"] * hp["start_lr"], i_pass, n)
+        else:
+            yield i_pass, hp["start_len"], hp["start_lr"]
+
+
+def resolve_remesh(remesh):
+    """The ``remesh=`` argument of the loops as a callable ``remesh(scene, remesh_len)`` or None: "isotropic" is the device remesher
+    (drt_amd.remesh_gpu), "isotropic-host" the sequential host version, its checker (drt_amd.remesh); anything else is returned as is."""
+    if remesh == "isotropic":
+        from .remesh_gpu import GpuMeshlabserver
+        return GpuMeshlabserver().remesh
+    if remesh == "isotropic-host":
+        from .remesh import Meshlabserver
+        return Meshlabserver().remesh
+    return remesh
+
+
+def run_steps(stepper, iters, history, say):
+    """``iters`` steps of an iteration object; every 100th is reported (``say``) and its weighted loss appended to ``history``."""
+    for it in range(iters):
+        total, parts = stepper.step()
+        if it % 100 == 0:
+            if say:
+                print(f"Iteration {it}: {loss_string(tuple(parts))} maxgrad={stepper.total_grad.abs().max():g}")
+            history.append(float(total))
+
+
 def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotropic", output=True, path_law=None):
     """``optimize(..., fused=True)`` on every rank of the default process group (one process without one): the pass / iteration loop with
     ShardedIteration steps, ONE all-reduce per iteration, and before every pass the remesh on rank 0 with its result broadcast to the
@@ -584,47 +528,27 @@ def optimize_sharded(scene, data, HyperParams, views_per_step=1, remesh="isotrop
     (``step_seconds``: the iterations without the remesh, device-synchronised at the end of each pass; ``collective_seconds``: CUDA-event
     time between the start and the end of the all-reduces).  ``path_law=(K, tir)``: as in ShardedIteration."""
     rank, world = ddist.rank_world()
-    if remesh == "isotropic":
-        from .remesh_gpu import GpuMeshlabserver
-        remesh = GpuMeshlabserver().remesh
-    elif remesh == "isotropic-host":
-        from .remesh import Meshlabserver
-        remesh = Meshlabserver().remesh
-    if float(HyperParams.get("ior_lr", 0) or 0) > 0:
-        raise NotImplementedError("HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by optimize_sharded: use the drop-in loop "
-                                  "optimize(..., fused=False)")
-    _refuse_path_law(HyperParams, "optimize_sharded")
-    law_kw = path_law_keyword(path_law, HyperParams, "optimize_sharded")
+    remesh = resolve_remesh(remesh)
+    law_kw = check_loop_config(HyperParams, path_law, "optimize_sharded", one_pass=True, loop=True)
     say = output and rank == 0
     Render.intIOR = HyperParams["IOR"]
     Render.resy, Render.resx = data.resy, data.resx
-    ray_view, silh_view = data.ray_view_generator(), data.silh_view_generator()      # one view schedule across passes
+    schedule = (data.ray_view_generator(), data.silh_view_generator())      # one view schedule across passes
     stats = {"world": world, "views_per_step": int(views_per_step), "passes": 0, "iterations": 0, "allreduces": 0, "broadcasts": 0,
              "step_seconds": 0.0, "collective_seconds": 0.0}
     start_time = time.time()
     history = []
-    for i_pass in range(HyperParams["Pass"]):
-        if HyperParams["Pass"] > 1:
-            remesh_len = interp_R(HyperParams["start_len"], HyperParams["end_len"], i_pass, HyperParams["Pass"])
-            lr = interp_R(HyperParams["start_lr"], HyperParams["lr_decay"] * HyperParams["start_lr"], i_pass, HyperParams["Pass"])
-        else:
-            remesh_len, lr = HyperParams["start_len"], HyperParams["start_lr"]
+    for i_pass, remesh_len, lr in pass_schedule(HyperParams):
         if say:
             print(f"remesh_len {remesh_len:g} lr {lr:g}")
         if remesh is not None:
             if rank == 0:
                 remesh(scene, remesh_len)
             stats["broadcasts"] += int(ddist.broadcast_mesh_(scene, src=0))
-        stepper = ShardedIteration(scene, data, HyperParams, lr, views_per_step, path_law=law_kw)
-        stepper.ray_view, stepper.silh_view = ray_view, silh_view
+        stepper = ShardedIteration(scene, data, HyperParams, lr, views_per_step, path_law=law_kw, schedule=schedule)
         torch.cuda.synchronize(scene.vertices.device)
         t0 = time.perf_counter()
-        for it in range(HyperParams["Iters"]):
-            total, parts = stepper.step()
-            if it % 100 == 0:
-                if say:
-                    print(f"Iteration {it}: {loss_string(tuple(parts))} maxgrad={stepper.total_grad.abs().max():g}")
-                history.append(float(total))
+        run_steps(stepper, HyperParams["Iters"], history, say)
         torch.cuda.synchronize(scene.vertices.device)
         stats["step_seconds"] += time.perf_counter() - t0
         stats["collective_seconds"] += stepper.collective_seconds()
@@ -671,50 +595,25 @@ def optimize(scene, data, HyperParams, remesh="isotropic", output=True, fused=Fa
     ``path_law=(max_bounces, tir)`` (keyword; None or (2, "drop"): today's kernels) selects the same law explicitly and works with both
     loops: with ``fused=True`` the refraction term is the one-pass ``Scene.paths_ray_loss_fused``, with ``fused=False`` it takes the
     ``render_paths`` + ``ray_loss`` route of the ``HyperParams`` keys.  Not together with ``ior_lr``."""
+    law_kw = check_loop_config(HyperParams, path_law, "the fused loop" if fused else "optimize", one_pass=fused, loop=True)
+    remesh = resolve_remesh(remesh)
     ior_lr = float(HyperParams.get("ior_lr", 0) or 0)
-    if ior_lr > 0 and fused:
-        raise NotImplementedError("HyperParams['ior_lr'] > 0 (a learnable IOR) is not supported by the fused loop: use the drop-in loop "
-                                  "optimize(..., fused=False)")
-    law = _law_of(HyperParams)
-    if law is not None and fused:
-        _refuse_path_law(HyperParams, "the fused loop")
-    if law is not None and ior_lr > 0:
-        raise NotImplementedError("HyperParams['max_bounces'] / ['tir'] cannot be combined with ior_lr > 0: Scene.render_paths differentiates "
-                                  "the vertices only")
-    law_kw = path_law_keyword(path_law, HyperParams, "optimize")
-    if remesh == "isotropic":               # on the device (drt_amd.remesh_gpu); "isotropic-host": the sequential host version, its checker
-        from .remesh_gpu import GpuMeshlabserver
-        remesh = GpuMeshlabserver().remesh
-    elif remesh == "isotropic-host":
-        from .remesh import Meshlabserver
-        remesh = Meshlabserver().remesh
     ior = None
     if ior_lr > 0:
         ior = torch.tensor(float(HyperParams["IOR"]), dtype=Float, device=scene.vertices.device, requires_grad=True)
     Render.intIOR = HyperParams["IOR"] if ior is None else ior
     Render.resy, Render.resx = data.resy, data.resx
-    loss_calculator = Loss_calculator(scene, data, HyperParams, fused=fused, path_law=law_kw)
+    loss_calculator = Loss_calculator(scene, data, HyperParams, fused=fused, path_law=law_kw)       # (and the one view schedule across passes)
     start_time = time.time()
     history = []
-    for i_pass in range(HyperParams["Pass"]):
-        if HyperParams["Pass"] > 1:
-            remesh_len = interp_R(HyperParams["start_len"], HyperParams["end_len"], i_pass, HyperParams["Pass"])
-            lr = interp_R(HyperParams["start_lr"], HyperParams["lr_decay"] * HyperParams["start_lr"], i_pass, HyperParams["Pass"])
-        else:
-            remesh_len, lr = HyperParams["start_len"], HyperParams["start_lr"]
+    for i_pass, remesh_len, lr in pass_schedule(HyperParams):
         if output:
             print(f"remesh_len {remesh_len:g} lr {lr:g}")
         if remesh is not None:
             remesh(scene, remesh_len)
         if fused:      # the one-pass terms without the autograd graph around them (same arithmetic, a third of the host work)
-            stepper = FusedIteration(scene, data, HyperParams, lr, path_law=law_kw)
-            stepper.ray_view, stepper.silh_view = loss_calculator.ray_view, loss_calculator.silh_view      # one view schedule across passes
-            for it in range(HyperParams["Iters"]):
-                total, parts = stepper.step()
-                if it % 100 == 0:
-                    if output:
-                        print(f"Iteration {it}: {loss_string(tuple(parts))} maxgrad={stepper.total_grad.abs().max():g}")
-                    history.append(float(total))
+            stepper = FusedIteration(scene, data, HyperParams, lr, path_law=law_kw, schedule=(loss_calculator.ray_view, loss_calculator.silh_view))
+            run_steps(stepper, HyperParams["Iters"], history, output)
             continue
         init_vertices, parameter, opt = setup_opt(scene, lr, HyperParams)
         if ior is not None:

@@ -473,15 +473,22 @@ class _Dihedral(torch.autograd.Function):
         return det.value(grad_v, v), None
 
 
+def enqueue_sm_term(scene, vertices, loss_ptr, grad_ptr):
+    """Enqueues the smoothness term -- sum -log(1 + cos dihedral) and its vertex gradient -- on the current stream: the one place that
+    calls drt_sm_loss_fused.  ``loss_ptr`` / ``grad_ptr``: raw device addresses the kernel ADDS into (float64, or fixed-point cells in
+    deterministic mode).  Reads ``vertices`` and the scene's own edge table only: nothing for the caller to keep."""
+    e2f = scene.E2F
+    _lib.check(_lib.lib().drt_sm_loss_fused(vertices.data_ptr(), e2f.data_ptr(), e2f.shape[0], loss_ptr, grad_ptr, _stream()))
+
+
 class _SmLossFused(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, vertices, E2F):
+    def forward(ctx, vertices, scene):
         v = _f64c(vertices.detach(), "vertices")
-        e2f = E2F.contiguous()
         loss = det.scalar(v.device)
         grad_v = det.acc(v)
         with _on(v.device):
-            _lib.check(_lib.lib().drt_sm_loss_fused(v.data_ptr(), e2f.data_ptr(), e2f.shape[0], loss.data_ptr(), grad_v.data_ptr(), _stream()))
+            enqueue_sm_term(scene, v, loss.data_ptr(), grad_v.data_ptr())
         ctx.save_for_backward(det.value(grad_v, v))
         return det.value(loss)
 
@@ -541,25 +548,35 @@ class _EdgeSample(torch.autograd.Function):
         return det.value(grad_v, v), None, None, None, None, None, None, None, None, None
 
 
+def enqueue_vh_term(scene, vertices, views, res_x, res_y, detach_depth, loss_ptr, grad_ptr):
+    """Enqueues the silhouette term summed over ``views`` = [(camera_M or its packed [50] tensor, eye [3], soft_mask [res_y * res_x]), ...]
+    and its vertex gradient on the current stream: the one place that calls drt_vh_loss_fused.  ``loss_ptr`` / ``grad_ptr``: raw device
+    addresses the kernels ADD into (float64, or fixed-point cells in deterministic mode).  The caller is inside ``_on(device)``.  Returns
+    the tensors whose memory the enqueued kernels read: the caller keeps them alive until the work is done."""
+    n = len(views)
+    cams, orgs, softs = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
+    keep = []
+    for k, (cam, eye, soft_mask) in enumerate(views):
+        if not isinstance(cam, torch.Tensor):
+            cam = pack_camera(cam)
+        o, sm = _f64c(eye.detach(), "origin"), _f64c(soft_mask, "soft_mask")
+        assert sm.numel() == res_x * res_y and o.numel() == 3 and cam.numel() == 50
+        keep += [cam, o, sm]
+        cams[k], orgs[k], softs[k] = cam.data_ptr(), o.data_ptr(), sm.data_ptr()
+    e2f = scene.E2F
+    _lib.check(_lib.lib().drt_vh_loss_fused(scene.optix_mesh._h, vertices.data_ptr(), scene.Edges.data_ptr(), e2f.data_ptr(), e2f.shape[0], n,
+                                            cams, orgs, softs, int(res_x), int(res_y), int(bool(detach_depth)), loss_ptr, grad_ptr, _stream()))
+    return keep
+
+
 class _VhLossFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, scene, res_x, res_y, detach_depth, *flat):
         v = _f64c(vertices.detach(), "vertices")
         loss = det.scalar(v.device)
         grad_v = det.acc(v)
-        n = len(flat) // 3
-        cams, orgs, softs = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
-        keep = []
-        for k in range(n):
-            o = _f64c(flat[3 * k + 1].detach(), "origin")
-            sm = _f64c(flat[3 * k + 2], "soft_mask")
-            assert sm.numel() == res_x * res_y and o.numel() == 3 and flat[3 * k].numel() == 50
-            keep += [o, sm]
-            cams[k], orgs[k], softs[k] = flat[3 * k].data_ptr(), o.data_ptr(), sm.data_ptr()
-        edges, e2f = scene.Edges, scene.E2F
         with _on(v.device):
-            _lib.check(_lib.lib().drt_vh_loss_fused(scene.optix_mesh._h, v.data_ptr(), edges.data_ptr(), e2f.data_ptr(), e2f.shape[0], n,
-                                                    cams, orgs, softs, res_x, res_y, int(bool(detach_depth)), loss.data_ptr(), grad_v.data_ptr(), _stream()))
+            enqueue_vh_term(scene, v, list(zip(flat[0::3], flat[1::3], flat[2::3])), res_x, res_y, detach_depth, loss.data_ptr(), grad_v.data_ptr())
         ctx.save_for_backward(det.value(grad_v, v))
         ctx.n_in = len(flat)
         return det.value(loss)

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import IOR, ROOT, data_path
+from conftest import IOR, ROOT, data_path, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -124,8 +124,9 @@ def test_weighted_partial_then_step_total_equals_limit_sgd_step3():
 
 # ---- the loop on 1, 2 and 3 ranks ---------------------------------------------------------------------------------------------------
 
-def _setup(rank, world, det_mode, hp):
-    """hand_vh and a synthetic capture of N_VIEWS views of which this rank renders only its own."""
+def _setup(rank, world, det_mode, hp, smooth=False):
+    """hand_vh (``smooth``: its smoothed form, on which every dihedral term is finite) and a synthetic capture of N_VIEWS views of which
+    this rank renders only its own."""
     from drt_amd import captured_data, det, diffrender as Render, dist as ddist, mesh_io, views
     det.enable(det_mode)
     Render.intIOR = IOR
@@ -137,6 +138,8 @@ def _setup(rank, world, det_mode, hp):
     mine = sorted(set(ddist.owned_views(ray_ids, rank, world)) | set(ddist.owned_views(captured_data.silh_view_ids(N_VIEWS), rank, world)))
     data = captured_data.SyntheticData(gt, center, extent, RES, RES, num_view=hp["num_view"], n_total=N_VIEWS, view_ids=mine, seed=0, name="hand")
     assert sorted(data.Views) == mine
+    if smooth:
+        mesh = mesh_io.TriMesh(golden("hand_smooth_sm")["vertices"].astype(np.float64), mesh.faces)
     return Render.Scene(mesh, 0), data
 
 
@@ -250,6 +253,96 @@ def test_one_rank_one_view_is_the_fused_loop(det_restored, det_mode):
     else:
         assert np.abs(pf - ps).max() <= 1e-12 * np.abs(pf).max()
         np.testing.assert_allclose(ls, lf, rtol=1e-12)
+
+
+# ---- the one-pass terms: one enqueue function per term behind the autograd Functions and behind the loops ------------------------------
+
+def _drawn_schedule(data):
+    """(first refraction view, the one after it, the first eight silhouette views) of the capture's generators."""
+    ray, silh = data.ray_view_generator(), data.silh_view_generator()
+    first, second = next(ray), next(ray)
+    assert first != second
+    return first, second, [next(silh) for _ in range(8)]
+
+
+@pytest.mark.parametrize("law", [None, (4, "reflect")], ids=["two-bounce", "4-reflect"])
+def test_the_functions_and_the_loop_share_their_terms(det_restored, law):
+    """Deterministic mode, one mesh state, one drawn schedule (one refraction view, eight silhouette views): the per-term losses and
+    [V, 3] gradients of Scene.ray_loss_fused (paths_ray_loss_fused under a law) / vh_loss_fused_views / sm_loss_fused through autograd
+    with unit seeds ARE those of a FusedIteration step from the same state (lr = 0) -- torch.equal, the sums are exact integers.  An
+    argument that reached the shared enqueue functions differently from the two callers, or a wrong offset into the accumulator block,
+    would show here.  Negative control: the refraction term of the NEXT view differs."""
+    from drt_amd import optim as O
+    hp = _hp()
+    scene, data = _setup(0, 1, True, hp, smooth=True)
+    data.rng = np.random.RandomState(0)
+    ray_id, next_ray_id, silh_ids = _drawn_schedule(data)
+    V = scene.vertices.detach().clone().requires_grad_(True)
+    scene.update_verticex(V)
+
+    def through_autograd(term):
+        V.grad = None
+        loss = term()
+        loss.backward()
+        return loss.detach().clone(), V.grad.clone()
+
+    def ray_term(view_id):
+        target, valid, _, origin, ray_dir, _ = data.get_view(view_id)
+        if law is None:
+            return scene.ray_loss_fused(origin, ray_dir, target, valid)
+        return scene.paths_ray_loss_fused(origin, ray_dir, target, valid, *law)
+
+    def vh_term():
+        views_ = []
+        for v in silh_ids:
+            _, _, soft_mask, origin, _, camera_M = data.get_view(v)
+            views_.append((camera_M, origin[0], soft_mask))
+        return scene.vh_loss_fused_views(views_)
+
+    want = [through_autograd(lambda: ray_term(ray_id)), through_autograd(vh_term), through_autograd(scene.sm_loss_fused)]
+    other = through_autograd(lambda: ray_term(next_ray_id))
+    it = O.FusedIteration(scene, data, hp, 0.0, path_law=law, schedule=(iter([ray_id]), iter(silh_ids)))
+    total, parts = it.step()
+    torch.cuda.synchronize()
+    assert not it.parameter.any()                               # (lr = 0: the state the Functions saw)
+    for k, (loss, grad) in enumerate(want):
+        print(f"term {k}: loss {float(loss):.17g}, largest gradient entry {float(grad.abs().max()):.3e}")
+        assert np.isfinite(float(loss)) and float(loss) != 0 and float(grad.abs().max()) > 0 and bool(torch.isfinite(grad).all())
+        assert torch.equal(parts[k], loss), (k, float(parts[k]), float(loss))
+        assert torch.equal(it.grads[k], grad), (k, float((it.grads[k] - grad).abs().max()))
+    assert not torch.equal(parts[0], other[0]) and not torch.equal(it.grads[0], other[1])
+
+
+@pytest.mark.parametrize("form", ["FusedIteration", "ShardedIteration"])
+def test_a_step_keeps_what_its_kernels_read(det_restored, form):
+    """After step(), both iteration forms hold every tensor the enqueue functions returned -- the refraction view's rays, targets and
+    flags, the silhouette views' cameras, eyes and masks -- next to the vertices, until the next step replaces the list."""
+    from drt_amd import optim as O
+    from drt_amd.silhouette import pack_camera
+    hp = _hp()
+    scene, data = _setup(0, 1, True, hp, smooth=True)
+    data.rng = np.random.RandomState(0)
+    first, second, silh_ids = _drawn_schedule(data)
+    it = getattr(O, form)(scene, data, hp, 0.1, schedule=(iter([first, second]), iter(silh_ids + silh_ids)))
+    assert it._keep == []
+
+    def read_by_the_ray_term(view_id):         # (without the origins: the silhouette term reads every view's first one, the eye)
+        target, valid, _, _, ray_dir, _ = data.get_view(view_id)
+        return {t.data_ptr() for t in (ray_dir, target, valid)}
+
+    it.step()
+    keep, vertices = it._keep, it._vertices
+    held = {t.data_ptr() for t in keep}
+    assert len(keep) == 4 + 3 * 8 and all(isinstance(t, torch.Tensor) and t.is_cuda for t in keep)
+    assert read_by_the_ray_term(first) <= held and not read_by_the_ray_term(second) & held
+    for v in silh_ids:
+        _, _, soft_mask, origin, _, camera_M = data.get_view(v)
+        assert {soft_mask.data_ptr(), origin.data_ptr(), pack_camera(camera_M).data_ptr()} <= held
+    it.step()
+    torch.cuda.synchronize()
+    assert it._keep is not keep and it._vertices is not vertices and len(it._keep) == len(keep)
+    held = {t.data_ptr() for t in it._keep}
+    assert read_by_the_ray_term(second) <= held and not read_by_the_ray_term(first) & held
 
 
 def test_device_remesher_repeats_itself():

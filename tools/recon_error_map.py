@@ -60,16 +60,11 @@ def report(tag, sc):
 
 report("hull  ", scene)
 t0 = time.time()
-views_ray = views_sil = None
-for i_pass in range(hp["Pass"]):
-    remesh_len = optim.interp_R(hp["start_len"], hp["end_len"], i_pass, hp["Pass"])
-    lr = optim.interp_R(hp["start_lr"], hp["lr_decay"] * hp["start_lr"], i_pass, hp["Pass"])
+schedule = (data.ray_view_generator(), data.silh_view_generator())
+for i_pass, remesh_len, lr in optim.pass_schedule(hp):
     if ml is not None:
         ml.remesh(scene, remesh_len)
-    stepper = optim.FusedIteration(scene, data, hp, lr)
-    if views_ray is not None:
-        stepper.ray_view, stepper.silh_view = views_ray, views_sil
-    views_ray, views_sil = stepper.ray_view, stepper.silh_view
+    stepper = optim.FusedIteration(scene, data, hp, lr, schedule=schedule)
     for it in range(hp["Iters"]):
         stepper.step()
 torch.cuda.synchronize()

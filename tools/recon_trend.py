@@ -20,17 +20,12 @@ ml = Meshlabserver() if os.environ.get("REMESH", "gpu") == "host" else GpuMeshla
 print("remesher:", type(ml).__name__)
 t0 = time.time()
 t_remesh = 0.0
-views_ray = views_sil = None
-for i_pass in range(hp["Pass"]):
-    remesh_len = optim.interp_R(hp["start_len"], hp["end_len"], i_pass, hp["Pass"])
-    lr = optim.interp_R(hp["start_lr"], hp["lr_decay"] * hp["start_lr"], i_pass, hp["Pass"])
+schedule = (data.ray_view_generator(), data.silh_view_generator())
+for i_pass, remesh_len, lr in optim.pass_schedule(hp):
     torch.cuda.synchronize(); tr = time.time()
     ml.remesh(scene, remesh_len)
     torch.cuda.synchronize(); t_remesh += time.time() - tr
-    stepper = optim.FusedIteration(scene, data, hp, lr)
-    if views_ray is not None:
-        stepper.ray_view, stepper.silh_view = views_ray, views_sil
-    views_ray, views_sil = stepper.ray_view, stepper.silh_view
+    stepper = optim.FusedIteration(scene, data, hp, lr, schedule=schedule)
     for it in range(hp["Iters"]):
         total, parts = stepper.step()
     h = metrics.hausdorff(scene, scan)
