@@ -25,37 +25,7 @@
 #include "drt_trace_kernel.h"
 #include "drt_pathsink.h"
 #include "drt_paths.h"
-
-// per-ray state byte while a call is in flight: refractions made so far (<= 8) | kPathDone once the path has ended valid
-constexpr uint8_t kPathDone = 0x80;
-// words of the counter block: sizes of lists 0 .. K, the second-pass counts of the K + 1 traversals, k_trace's retired-workgroup counter,
-// the number of valid rays
-constexpr int kCntList = 0, kCntRedo = 16, kCntDone = 32, kCntValid = 33, kCntWords = 40;
-static_assert(kMaxBounces + 1 <= kCntRedo - kCntList && kMaxBounces + 1 <= kCntDone - kCntRedo, "counter block layout");
-
-struct PathsWs {
-    int64_t cap = 0;
-    int32_t* idx[2] = {nullptr, nullptr};
-    float* ray[2] = {nullptr, nullptr};
-    int32_t* face[2] = {nullptr, nullptr};
-    int32_t* redo = nullptr;
-    uint8_t* state = nullptr;
-    unsigned* cnt = nullptr;
-    int32_t* slow_stack = nullptr;       // overflow area of k_trace's second pass: [kPathBlock * kStackSlowDev]
-    // the one-pass form only (ensure_paths_fused_ws): float64 ray in flight [2][fused_cap,3], face tape [kMaxBounces, fused_cap], hit counts
-    int64_t fused_cap = 0;
-    double* park = nullptr;
-    int32_t* tape = nullptr;
-    uint8_t* hits = nullptr;
-};
-
-// each block takes one contiguous run of [0, n), so that what it appends stays in input order
-__device__ __forceinline__ void block_run(unsigned n, unsigned& first, unsigned& last) {
-    const unsigned per_block = ((n + gridDim.x - 1) / gridDim.x + kPathBlock - 1) / kPathBlock * kPathBlock;
-    first = blockIdx.x * per_block;
-    last = min(n, first + per_block);
-    if (first > last) first = last;
-}
+#include "drt_pathws.h"
 
 __global__ void __launch_bounds__(kPathBlock) k_paths_start(const Node4Q* __restrict__ nodes, int n_tris, const double* __restrict__ origin,
                                                              const double* __restrict__ dir, unsigned n, double* __restrict__ out_ori,
@@ -319,9 +289,9 @@ __global__ void __launch_bounds__(256) k_paths_loss_bwd_ior(PathCtx c, const dou
     if (n_valid && cnt) atomicAdd(n_valid, (unsigned long long)cnt);
 }
 
-static PathsWs* ws_of(drt_scene* s) { return static_cast<PathsWs*>(s->paths_ws); }
+static PathsWs* ws_of(drt_scene* s) { return paths_ws_of(s); }
 
-static int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st, const char* who) {
+int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st, const char* who) {
     PathsWs* w = ws_of(s);
     if (w && n <= w->cap) return DRT_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -353,13 +323,13 @@ static int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st, const char* 
 }
 
 // the workspace rows of the one-pass form, grown like the ray lists
-static int ensure_paths_fused_ws(drt_scene* s, int64_t n, hipStream_t st) {
+int ensure_paths_fused_ws(drt_scene* s, int64_t n, hipStream_t st, const char* who) {
     PathsWs* w = ws_of(s);
     if (n <= w->fused_cap) return DRT_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(DRT_E_INVALID, "drt_render_paths_ray_loss_fused: the first call of this size allocates its parked rays and face tape and cannot "
-                                   "run inside a stream capture: issue one such call eagerly before capturing");
+        return fail(DRT_E_INVALID, "%s: the first call of this size allocates its parked rays and face tape and cannot "
+                                   "run inside a stream capture: issue one such call eagerly before capturing", who);
     (void)hipFree(w->park); (void)hipFree(w->tape); (void)hipFree(w->hits);
     w->park = nullptr; w->tape = nullptr; w->hits = nullptr; w->fused_cap = 0;
     HIP_TRY(hipMalloc(&w->park, sizeof(double) * 6 * (size_t)n));
@@ -422,6 +392,7 @@ void paths_free(drt_scene* s) {
     for (int k = 0; k < 2; ++k) { (void)hipFree(w->idx[k]); (void)hipFree(w->ray[k]); (void)hipFree(w->face[k]); }
     (void)hipFree(w->redo); (void)hipFree(w->state); (void)hipFree(w->cnt); (void)hipFree(w->slow_stack);
     (void)hipFree(w->park); (void)hipFree(w->tape); (void)hipFree(w->hits);
+    (void)hipFree(w->thr);
     delete w;
     s->paths_ws = nullptr;
 }
@@ -501,7 +472,7 @@ static int paths_ray_loss_fused(drt_scene* s, const double* d_verts, const doubl
     if (!d_verts || !d_origin || !d_dir || !d_screen_pixel || !d_valid || !d_loss || (!d_grad_verts && !d_grad_ior)) return fail(DRT_E_INVALID, "null pointer argument");
     hipStream_t st = (hipStream_t)stream;
     { int rc = ensure_paths_ws(s, n_rays, st, who); if (rc) return rc; }
-    { int rc = ensure_paths_fused_ws(s, n_rays, st); if (rc) return rc; }
+    { int rc = ensure_paths_fused_ws(s, n_rays, st, who); if (rc) return rc; }
     { int rc = wait_build(s, st); if (rc) return rc; }
     const PathsWs& w = *ws_of(s);
     PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);

@@ -1034,6 +1034,38 @@ class Scene(StepwiseMixin):
         ior = self._check_paths_call("render_paths", origin, ray_dir, max_bounces, tir, refraction)
         return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), _law_flags(tir, refraction))
 
+    def render_image(self, camera_M, height, width, screen, texture, *, supersample=1, max_bounces=2, tir="drop", refraction="reference",
+                     fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False):
+        """What the pinhole camera ``camera_M`` = (R, K, R^-1, K^-1) sees of a textured planar screen through this mesh: a float32 image
+        ``[height, width, C]`` on the device (drt_render_image; csrc/drt_image.h and DESIGN.md 10.2 state the law).  ``screen``: a
+        ``drt_amd.render.Screen``; ``texture``: float32 ``[Th, Tw, C]`` (or ``[Th, Tw]``), C in {1, 3}, numpy or a device tensor.
+        Every pixel is the mean of ``supersample``^2 (1..4) sample rays made in the kernel (``supersample=1``: ``views.generate_ray``'s
+        ray).  A sample follows the path law of ``render_paths`` (``max_bounces``, ``tir``, ``refraction``; ``intIOR`` / ``extIOR`` of
+        this module, read as ``render_paths`` reads them); with ``fresnel`` every refracting interaction weights it by 1 - R
+        (FrDielectric), a mirrored one does not.  A sample without any interaction looks straight at the screen, one whose path
+        completes looks along its exit ray -- the bilinear texture sample, or ``void`` off the screen; every other sample is
+        ``invalid`` (each one number or C of them; the fills are not weighted).  The image is rendered in bands of at most
+        ``max_samples`` samples (158 B of workspace each, shared with the path calls); the bands give the bits of the whole.  ``want_planes``: also return
+        float32 ``[height, width]`` planes ``hit`` (share of samples with an interaction) and ``through`` (share whose path completed).
+        Forward only: the image has no autograd graph and no gradient w.r.t. anything.  Two calls give the same bits."""
+        from . import render as _render
+        a = _render.check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid,
+                                      max_samples, want_planes)
+        ior = _ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR")
+        dev = self._dev
+        with _on(dev):
+            tex = torch.as_tensor(a["texture"], device=dev).to(torch.float32).contiguous()
+            v = _f64c(self.vertices.detach(), "vertices")
+            H, W, C = a["height"], a["width"], a["channels"]
+            image = torch.empty((H, W, C), dtype=torch.float32, device=dev)
+            planes = tuple(torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(2)) if a["want_planes"] else (None, None)
+            for y0, y1 in a["bands"]:
+                _lib.check(_lib.lib().drt_render_image(
+                    self.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
+                    a["law_flags"], a["fresnel"], a["screen"].ctypes.data, tex.data_ptr(), tex.shape[0], tex.shape[1], C, a["void"].ctypes.data,
+                    a["invalid"].ctypes.data, image.data_ptr(), _lib.ptr(planes[0]), _lib.ptr(planes[1]), _stream()))
+        return (image,) + planes if a["want_planes"] else image
+
     @staticmethod
     def _check_law(max_bounces, tir, refraction):
         """The checks of the law itself, shared by every K-interaction call."""

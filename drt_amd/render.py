@@ -1,0 +1,362 @@
+"""The refracted image of a mesh in front of a textured screen: what a camera sees THROUGH the glass object.
+
+    python -m drt_amd.render --name horse [--mesh result.ply] [--capture horse.h5 | --views N] --view-ids 0 9 18 --res H W
+                             --supersample 3 --max-bounces 6 --tir reflect --refraction snell [--no-fresnel]
+                             [--background checker|ramp|FILE] -o DIR [--force]
+
+``Scene.render_image`` (drt_amd.diffrender) is the entry point; this module holds what goes with it: the screen, procedural
+textures, image files, the band plan and the command line.  The law is stated once, in csrc/drt_image.h (and DESIGN.md section 10.2):
+s x s sample rays per pixel made in the kernel, the K-interaction path law of ``Scene.render_paths`` with a Fresnel throughput, the
+exit ray's bilinear sample of the screen's texture, the mean per pixel.  Forward only: the image has no gradient.  There is no CPU
+fallback: the kernels are the implementation (tests/image_ref.py restates the law for the tests)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+
+import numpy as np
+
+MAX_SUPERSAMPLE = 4
+ORTHO_TOL = 1e-12
+
+
+class Screen:
+    """A textured planar screen: ``p0`` the world position of texel (0, 0), ``eu`` / ``ev`` the world vectors of one texel step along the
+    texture's x and y.  The axes must be orthogonal (|eu . ev| <= 1e-12 |eu| |ev|) and non-zero; the screen has two faces."""
+
+    def __init__(self, p0, eu, ev):
+        self.p0, self.eu, self.ev = (_vec3(a, n) for a, n in ((p0, "p0"), (eu, "eu"), (ev, "ev")))
+        lu, lv = float(np.linalg.norm(self.eu)), float(np.linalg.norm(self.ev))
+        if not (lu > 0.0 and lv > 0.0):
+            raise ValueError(f"screen: eu and ev must be non-zero, got |eu| = {lu}, |ev| = {lv}")
+        if abs(float(self.eu @ self.ev)) > ORTHO_TOL * lu * lv:
+            raise ValueError(f"screen: eu and ev must be orthogonal, got eu . ev = {float(self.eu @ self.ev)!r} with |eu| |ev| = {lu * lv!r}")
+
+    def packed(self):
+        """The nine doubles of the C ABI: p0, eu, ev."""
+        return np.ascontiguousarray(np.concatenate([self.p0, self.eu, self.ev]), dtype=np.float64)
+
+    @classmethod
+    def behind(cls, camera_M, center, extent, tex_w, tex_h, plane_factor=1.5, span=2.0):
+        """A screen perpendicular to the view axis of ``camera_M`` = (R, K, R^-1, K^-1), centred behind the object where
+        ``views.screen_targets`` places its plane (``center + plane_factor * extent * z_camera``) and spanning ``span * extent`` along both
+        camera axes: texel (0, 0) is the corner the image's top-left looks at, x runs along the camera's x, y along its y.  A calibrated R
+        is orthonormal to 1e-7 or so, not to the 1e-12 a screen asks for: the y axis is made orthogonal to the x axis here (Gram-Schmidt),
+        and the plane's normal is their cross product rather than R's third row."""
+        tex_w, tex_h = _int(tex_w, "tex_w"), _int(tex_h, "tex_h")
+        if tex_w < 2 or tex_h < 2:
+            raise ValueError(f"tex_w, tex_h must be at least 2, got {(tex_w, tex_h)}")
+        span, extent, plane_factor = float(span), float(extent), float(plane_factor)
+        if not (span > 0.0 and extent > 0.0 and np.isfinite(span * extent)):
+            raise ValueError(f"span and extent must be positive and finite, got span = {span!r}, extent = {extent!r}")
+        R = _mat(camera_M[0], (4, 4), "camera_M[0] (R)")
+        xc, yc, zc = R[0, :3], R[1, :3], R[2, :3]
+        if not (np.linalg.norm(xc) > 0.0 and np.linalg.norm(zc) > 0.0):
+            raise ValueError("camera_M[0] (R) must have non-zero rows")
+        xc = xc / np.linalg.norm(xc)
+        yc = yc - (yc @ xc) * xc
+        yc = yc - (yc @ xc) * xc                          # twice: the first pass leaves a residue of the order of the defect squared
+        if not np.linalg.norm(yc) > 0.0:
+            raise ValueError("camera_M[0] (R): its first two rows must not be parallel")
+        yc = yc / np.linalg.norm(yc)
+        zc = zc / np.linalg.norm(zc)
+        mid = _vec3(center, "center") + (plane_factor * extent) * zc
+        eu = xc * (span * extent / (tex_w - 1))
+        ev = yc * (span * extent / (tex_h - 1))
+        return cls(mid - eu * ((tex_w - 1) / 2.0) - ev * ((tex_h - 1) / 2.0), eu, ev)
+
+
+def _vec3(a, name):
+    try:
+        a = _host(a)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be three finite numbers, got {a!r}") from None
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be three finite numbers, got {a!r}")
+    return a
+
+
+def _host(a):
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    return np.array(a, dtype=np.float64)
+
+
+def _mat(a, shape, name):
+    try:
+        a = _host(a)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a finite {shape[0]} x {shape[1]} matrix, got {type(a).__name__}") from None
+    if a.shape != shape or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be a finite {shape[0]} x {shape[1]} matrix, got shape {a.shape}")
+    return a
+
+
+def _int(x, name):
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, got {x!r}")
+    return int(x)
+
+
+# ---- procedural textures ---------------------------------------------------------------------------------------------------------------
+def checker(tex_h, tex_w, squares=8):
+    """float32 [tex_h, tex_w, 1]: a checkerboard of ``squares`` squares along the longer side, values 0.1 and 0.9."""
+    tex_h, tex_w, squares = _int(tex_h, "tex_h"), _int(tex_w, "tex_w"), _int(squares, "squares")
+    if tex_h < 2 or tex_w < 2 or squares < 1:
+        raise ValueError(f"checker needs tex_h, tex_w >= 2 and squares >= 1, got {(tex_h, tex_w, squares)}")
+    side = max(tex_h, tex_w) / squares
+    yy, xx = np.meshgrid(np.arange(tex_h), np.arange(tex_w), indexing="ij")
+    odd = (np.floor(yy / side) + np.floor(xx / side)) % 2
+    return (0.1 + 0.8 * odd).astype(np.float32)[:, :, None]
+
+
+def ramp(tex_h, tex_w):
+    """float32 [tex_h, tex_w, 3]: red grows along x, green along y, blue marks a 16-texel grid -- every texel tells where it is."""
+    tex_h, tex_w = _int(tex_h, "tex_h"), _int(tex_w, "tex_w")
+    if tex_h < 2 or tex_w < 2:
+        raise ValueError(f"ramp needs tex_h, tex_w >= 2, got {(tex_h, tex_w)}")
+    yy, xx = np.meshgrid(np.arange(tex_h), np.arange(tex_w), indexing="ij")
+    grid = ((yy % 16 == 0) | (xx % 16 == 0)).astype(np.float64)
+    return np.stack([xx / (tex_w - 1), yy / (tex_h - 1), 0.25 + 0.5 * grid], axis=2).astype(np.float32)
+
+
+# ---- image files -----------------------------------------------------------------------------------------------------------------------
+def _read_netpbm(path):
+    with open(path, "rb") as f:
+        raw = f.read()
+    tokens, pos = [], 0
+    while len(tokens) < 4:
+        while raw[pos:pos + 1].isspace():
+            pos += 1
+        if raw[pos:pos + 1] == b"#":
+            pos = raw.index(b"\n", pos) + 1
+            continue
+        end = pos
+        while not raw[end:end + 1].isspace():
+            end += 1
+        tokens.append(raw[pos:end])
+        pos = end
+    magic, w, h, top = tokens[0], int(tokens[1]), int(tokens[2]), int(tokens[3])
+    if magic not in (b"P5", b"P6") or top != 255:
+        raise ValueError(f"{path}: only binary 8-bit PGM / PPM files are read, got {magic!r} with maximum {top}")
+    c = 1 if magic == b"P5" else 3
+    return np.frombuffer(raw, np.uint8, h * w * c, pos + 1).reshape(h, w, c)
+
+
+def load_texture(path):
+    """float32 [Th, Tw, C] in [0, 1] from ``.npy`` (float arrays as they are, uint8 scaled by 1 / 255), binary ``.ppm`` / ``.pgm``, or
+    any image file PIL reads when it is importable."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        a = np.load(path)
+    elif ext in (".ppm", ".pgm"):
+        a = _read_netpbm(path)
+    else:
+        try:
+            from PIL import Image
+        except ImportError:
+            raise ValueError(f"{path}: reading {ext or 'this'} files needs PIL; without it use .npy, .ppm or .pgm") from None
+        with Image.open(path) as im:
+            a = np.asarray(im.convert("L" if im.mode in ("L", "1", "I", "F") else "RGB"))
+    a = a.astype(np.float32) / np.float32(255.0) if a.dtype == np.uint8 else a.astype(np.float32)
+    return check_texture(a)
+
+
+def to_bytes(image):
+    """uint8 [H, W, C] of a float image: clipped to [0, 1], scaled by 255, rounded to nearest."""
+    a = _host(image)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] not in (1, 3) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"image must be [H, W], [H, W, 1] or [H, W, 3], got shape {a.shape}")
+    return np.rint(np.clip(np.nan_to_num(a, nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def write_image(path, image, force=False):
+    """Write a float image ([H, W], [H, W, 1] or [H, W, 3], values in [0, 1]) as 8 bits per channel and return the path written:
+    ``.ppm`` / ``.pgm`` as binary netpbm; anything else through PIL when it is importable, otherwise as netpbm next to the requested name
+    (extension replaced).  An existing file is only replaced with ``force``."""
+    a = to_bytes(image)
+    ext = os.path.splitext(path)[1].lower()
+    pil = None
+    if ext not in (".ppm", ".pgm"):
+        try:
+            from PIL import Image as pil
+        except ImportError:
+            path = os.path.splitext(path)[0] + (".pgm" if a.shape[2] == 1 else ".ppm")
+    if os.path.exists(path) and not force:
+        raise FileExistsError(f"{path} exists: pass force=True (--force) to overwrite it")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    if pil is not None:
+        pil.fromarray(a[:, :, 0] if a.shape[2] == 1 else a).save(path)
+    else:
+        with open(path, "wb") as f:
+            f.write(b"%s\n%d %d\n255\n" % (b"P5" if a.shape[2] == 1 else b"P6", a.shape[1], a.shape[0]))
+            f.write(a.tobytes())
+    return path
+
+
+# ---- the call's arguments (checked before anything touches the device) -----------------------------------------------------------------
+def plan_bands(height, width, s, max_samples):
+    """Rows [y0, y1) of the bands of an image of ``height`` x ``width`` pixels with ``s`` x ``s`` samples each: consecutive, covering every
+    row once, each of at most ``max_samples`` samples -- except that a band is never less than one row."""
+    height, width, s, max_samples = _int(height, "height"), _int(width, "width"), _int(s, "supersample"), _int(max_samples, "max_samples")
+    if height < 1 or width < 1:
+        raise ValueError(f"height, width must be at least 1, got {(height, width)}")
+    if not 1 <= s <= MAX_SUPERSAMPLE:
+        raise ValueError(f"supersample must be in 1..{MAX_SUPERSAMPLE}, got {s}")
+    if max_samples < 1:
+        raise ValueError(f"max_samples must be at least 1, got {max_samples}")
+    rows = max(1, max_samples // (width * s * s))
+    return [(y0, min(height, y0 + rows)) for y0 in range(0, height, rows)]
+
+
+def check_texture(texture):
+    """The texture as a contiguous float32 array [Th, Tw, C] (numpy) -- or, a device tensor, as it is after the same checks."""
+    t = texture
+    if not (hasattr(t, "shape") and hasattr(t, "dtype")):
+        t = np.asarray(t)
+    if t.ndim == 2:
+        t = t[:, :, None]
+    if t.ndim != 3 or t.shape[2] not in (1, 3):
+        raise ValueError(f"texture must be [Th, Tw], [Th, Tw, 1] or [Th, Tw, 3], got shape {tuple(t.shape)}")
+    if t.shape[0] < 2 or t.shape[1] < 2:
+        raise ValueError(f"texture must be at least 2 x 2 texels, got {tuple(t.shape[:2])}")
+    kind = str(t.dtype)
+    if "float" not in kind:
+        raise ValueError(f"texture must be a float array (float32 is used), got dtype {kind}")
+    if isinstance(t, np.ndarray):
+        return np.ascontiguousarray(t, dtype=np.float32)
+    return t
+
+
+def _fill(x, channels, name):
+    try:
+        a = _host(x).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be one finite number or {channels} of them (one per channel), got {x!r}") from None
+    if a.size == 1:
+        a = np.repeat(a, channels)
+    if a.size != channels or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be one finite number or {channels} of them (one per channel), got {x!r}")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def check_render_args(camera_M, height, width, screen, texture, supersample=1, max_bounces=2, tir="drop", refraction="reference",
+                      fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False):
+    """Every argument check of ``Scene.render_image``, none of which needs a device.  Returns a dict: camera (21 doubles: K^-1, then the
+    top 3 x 4 of R^-1), screen (9 doubles), texture, void / invalid (C doubles), bands, law_flags and the scalars."""
+    try:
+        n_cam = len(camera_M)
+    except TypeError:
+        raise ValueError(f"camera_M must be the tuple (R, K, R^-1, K^-1), got {type(camera_M).__name__}") from None
+    if n_cam != 4:
+        raise ValueError(f"camera_M must be the tuple (R, K, R^-1, K^-1), got {n_cam} entries")
+    rinv, kinv = _mat(camera_M[2], (4, 4), "camera_M[2] (R^-1)"), _mat(camera_M[3], (3, 3), "camera_M[3] (K^-1)")
+    bands = plan_bands(height, width, supersample, max_samples)
+    if isinstance(max_bounces, bool) or not isinstance(max_bounces, (int, np.integer)) or not 2 <= int(max_bounces) <= 8:
+        raise ValueError(f"max_bounces must be an integer in 2..8, got {max_bounces!r}")
+    if tir not in ("drop", "reflect"):
+        raise ValueError(f"tir must be 'drop' or 'reflect', got {tir!r}")
+    if not isinstance(refraction, str) or refraction not in ("reference", "snell"):
+        raise ValueError(f"refraction must be 'reference' or 'snell', got {refraction!r}")
+    if not isinstance(fresnel, (bool, np.bool_)):
+        raise ValueError(f"fresnel must be True or False, got {fresnel!r}")
+    if not isinstance(want_planes, (bool, np.bool_)):
+        raise ValueError(f"want_planes must be True or False, got {want_planes!r}")
+    if not isinstance(screen, Screen):
+        raise ValueError(f"screen must be a drt_amd.render.Screen, got {type(screen).__name__}")
+    tex = check_texture(texture)
+    channels = int(tex.shape[2])
+    return dict(camera=np.ascontiguousarray(np.concatenate([kinv.reshape(-1), rinv[:3, :].reshape(-1)]), dtype=np.float64),
+                screen=screen.packed(), texture=tex, channels=channels, void=_fill(void, channels, "void"),
+                invalid=_fill(invalid, channels, "invalid"), bands=bands, height=int(height), width=int(width), supersample=int(supersample),
+                max_bounces=int(max_bounces), law_flags=int(tir == "reflect") | (2 if refraction == "snell" else 0), fresnel=int(bool(fresnel)),
+                want_planes=bool(want_planes))
+
+
+# ---- command line ----------------------------------------------------------------------------------------------------------------------
+def _background(spec, tex):
+    if spec == "checker":
+        return checker(tex, tex, 16)
+    if spec == "ramp":
+        return ramp(tex, tex)
+    return load_texture(spec)
+
+
+def capture_cameras(path, view_ids):
+    """(height, width, {view: camera_M}) of a capture file (``captured_data``'s formats and datasets): ``cam_proj`` [n, 4, 4] world ->
+    camera, ``cam_k`` [3, 3], the image size from ``mask`` [n, H, W].  Only these are read: the renderer makes its own rays."""
+    from . import captured_data
+    cap = captured_data._open_capture(path)
+    try:
+        K = np.asarray(cap["cam_k"][:], dtype=np.float64)
+        n, height, width = (int(v) for v in cap["mask"].shape)
+        cams = {}
+        for k in view_ids:
+            if not 0 <= k < n:
+                raise ValueError(f"view {k}: the capture has views 0..{n - 1}")
+            R = np.asarray(cap["cam_proj"][k], dtype=np.float64)
+            cams[k] = (R, K, np.linalg.inv(R), np.linalg.inv(K))
+    finally:
+        if hasattr(cap, "close"):
+            cap.close()
+    return height, width, cams
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Render what a camera sees of a textured screen through the glass object and write one image per view.")
+    ap.add_argument("--name", default="horse")
+    ap.add_argument("--data-path", default="./data/")
+    ap.add_argument("--mesh", default=None, help="the mesh to look through (default: <data-path>/<name>_vh.ply)")
+    ap.add_argument("--capture", default=None, help=".npz / .h5 capture: its cameras (cam_proj, cam_k) and its resolution are used")
+    ap.add_argument("--views", type=int, default=72, help="views of the turntable used without --capture")
+    ap.add_argument("--view-ids", type=int, nargs="+", default=[0])
+    ap.add_argument("--res", type=int, nargs=2, default=[512, 512], metavar=("H", "W"), help="image size of the turntable cameras (a capture has its own)")
+    ap.add_argument("--supersample", type=int, default=2)
+    ap.add_argument("--max-bounces", type=int, default=6)
+    ap.add_argument("--tir", choices=("drop", "reflect"), default="reflect")
+    ap.add_argument("--refraction", choices=("reference", "snell"), default="snell")
+    ap.add_argument("--no-fresnel", action="store_true")
+    ap.add_argument("--ior", type=float, default=None, help="index of refraction of the object (default: the package's intIOR)")
+    ap.add_argument("--background", default="checker", help="checker, ramp, or a texture file (.npy, .ppm, .pgm, or what PIL reads)")
+    ap.add_argument("--texture-size", type=int, default=1024, help="texels per side of a procedural background")
+    ap.add_argument("--span", type=float, default=2.0, help="side of the screen in units of the object's extent")
+    ap.add_argument("--invalid", type=float, nargs="+", default=[0.0], help="colour of samples whose path does not complete")
+    ap.add_argument("--void", type=float, nargs="+", default=[0.0], help="colour of samples that miss the screen")
+    ap.add_argument("-o", "--output", required=True, help="directory the images are written to")
+    ap.add_argument("--format", default="png", help="png (needs PIL; netpbm is written without it), ppm / pgm")
+    ap.add_argument("--force", action="store_true", help="overwrite existing images")
+    a = ap.parse_args(argv)
+    stem = os.path.join(a.output, a.name + "_view{:03d}")
+    for k in a.view_ids:
+        for ext in {a.format, "ppm", "pgm"}:
+            if os.path.exists(stem.format(k) + "." + ext) and not a.force:
+                raise SystemExit(f"{stem.format(k)}.{ext} exists: pass --force to overwrite it")
+    from . import diffrender as Render, views
+    scene = Render.Scene(a.mesh or os.path.join(a.data_path, f"{a.name}_vh.ply"), 0)
+    if a.ior is not None:
+        Render.intIOR = a.ior
+    center, extent = views.mesh_frame(scene.mesh.vertices)
+    if a.capture is not None:
+        height, width, cams = capture_cameras(a.capture, a.view_ids)
+    else:
+        height, width = a.res
+        turntable = views.turntable_cameras(center, extent, a.views, width, height)
+        cams = {k: turntable[k] for k in a.view_ids}
+    texture = _background(a.background, a.texture_size)
+    report = {"name": a.name, "height": height, "width": width, "views": []}
+    for k in a.view_ids:
+        screen = Screen.behind(cams[k], center, extent, texture.shape[1], texture.shape[0], span=a.span)
+        image, hit, through = scene.render_image(cams[k], height, width, screen, texture, supersample=a.supersample, max_bounces=a.max_bounces,
+                                                 tir=a.tir, refraction=a.refraction, fresnel=not a.no_fresnel, void=a.void, invalid=a.invalid,
+                                                 want_planes=True)
+        path = write_image(stem.format(k) + "." + a.format, image, force=a.force)
+        report["views"].append({"view": k, "image": path, "hit_share": float(hit.mean()), "through_share": float(through.mean())})
+    print(json.dumps(report))
+    return report
+
+
+if __name__ == "__main__":
+    main()

@@ -34,7 +34,7 @@ typedef struct drt_scene drt_scene_t;
 const char* drt_last_error(void);
 int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
                             * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused;
-                            * 7: drt_hull_field / drt_hull_mark / drt_hull_emit */
+                            * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -631,6 +631,41 @@ int drt_hull_mark(const float* d_field, int nx, int ny, int nz, double level, ui
 int drt_hull_emit(const float* d_field, int nx, int ny, int nz, double lo_x, double lo_y, double lo_z, double cell, double level,
                   const uint8_t* d_edge_mask, const int32_t* d_v_inc, const int32_t* d_t_inc, int64_t n_verts, int64_t n_faces,
                   double* d_verts, int32_t* d_faces, void* stream);
+
+/* ---- the refracted image of the mesh in front of a textured screen (csrc/drt_image.h states the law) ---------
+ * A forward renderer, opt-in, without a gradient: rows [y0, y1) of the float32 image [height, width, channels] a pinhole camera sees.
+ * camera21 (HOST, 21 doubles) = K^-1 [3,3] then the top [3,4] of R^-1, row-major; screen9 (HOST) = p0, eu, ev: the world position of
+ * texel (0, 0) and the world vectors of one texel step along the texture's x and y; fill_void / fill_invalid (HOST, `channels` doubles).
+ * d_verts float64 [V,3], d_texture float32 [tex_h, tex_w, channels], d_image, d_hit / d_through float32 [height, width] (may be NULL):
+ * device pointers.  Every expression is float64 in the stated association:
+ *   sample  pixel (x, y) has s^2 samples (s = supersample, 1..4); sample j = b s + a looks through (px, py) = (x + (a + 0.5)/s - 0.5,
+ *           y + (b + 0.5)/s - 0.5); p_r = (Kinv[r][0] px + Kinv[r][1] py) + Kinv[r][2], w_r = (Rinv[r][0] p_0 + Rinv[r][1] p_1) + Rinv[r][2] p_2,
+ *           dir = w / sqrt((w_x^2 + w_y^2) + w_z^2), origin = Rinv[:3, 3]: at s = 1 the ray of the integer pixel centre.
+ *   path    the K-interaction law of drt_render_paths_law_forward (max_bounces 2..8, law_flags DRT_LAW_REFLECT | DRT_LAW_SNELL), unchanged,
+ *           with a throughput T = 1 that every REFRACTING interaction multiplies by 1 - R when `fresnel` is 1 (0: geometry only): R is the
+ *           reference's FrDielectric with cos(theta_i) from the flipped normal and the eta_i, eta_t of that interaction,
+ *           sinT = sqrt(clamp(1 - ci ci, 0, 1)) eta_i / eta_t, cosT = sqrt(max(1 - sinT sinT, 0)),
+ *           R = (((eta_t ci - eta_i cosT) / (eta_t ci + eta_i cosT))^2 + ((eta_i ci - eta_t cosT) / (eta_i ci + eta_t cosT))^2) / 2;
+ *           a mirrored (TIR) interaction leaves T alone.
+ *   class   direct: no interaction at all (exit ray = camera ray, T = 1); through: the path completed validly; invalid: everything else.
+ *   screen  direct and through samples with exit ray (o, d): n = eu x ev, t = (p0 - o) . n / (d . n); seen iff d . n != 0 and t > 0 (two
+ *           faces; NaN fails); u = (o + t d - p0) . eu / (eu . eu), v likewise with ev; on the screen iff 0 <= u <= tex_w - 1 and
+ *           0 <= v <= tex_h - 1 (texel centres at the integers): colour = T * the bilinear sample (drt_hull_field's formula, float64);
+ *           otherwise fill_void; an invalid sample has fill_invalid.  The fills are not weighted.
+ *   pixel   (((c_0 + c_1) + c_2) + ...) / s^2 in sample order, stored as float32; d_hit = the share of samples with at least one
+ *           interaction, d_through = the share whose path completed.
+ * Only rows [y0, y1) of the three outputs are written; a band gives the bits the whole image gives.  Workspace: 158 bytes per sample of the
+ * band, kept by the scene: the ray lists (69) and the rows of the one-pass path call (81: parked float64 ray, hit count and its face tape,
+ * which this call leaves alone), shared with those calls and scratch to each, plus one float64 throughput (8); the first call of a size allocates and cannot run inside a
+ * stream capture.  Everything is enqueued on `stream`, nothing is read back.  No accumulation target: the call is the same under
+ * drt_deterministic, and two runs give the same bits.  A scene without triangles renders every sample as direct.  DRT_E_INVALID (nothing
+ * written): supersample outside 1..4, channels not 1 or 3, a texture side below 2, zero / non-finite / non-orthogonal axes
+ * (|eu . ev| > 1e-12 |eu| |ev|), a bad max_bounces, law_flags or fresnel, an empty or inverted band or one outside the image, more than
+ * 2^31 - 1 samples, a null pointer, a workspace that would have to grow inside a stream capture. */
+int drt_render_image(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                     double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                     const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                     float* d_image, float* d_hit, float* d_through, void* stream);
 
 /* ---- measurement (bench.py's live per-kernel timing) --------------------------------------------
  * When enabled (on = 1; on = 2 additionally collects the traversal statistics below, which perturbs
