@@ -201,6 +201,7 @@ struct drt_scene {
     bool use_raster = true;        // DRT_RASTER=0: every primary ray takes the BVH path (A/B measurement)
     bool built = false;
     void* paths_ws = nullptr;      // ray lists and counters of drt_render_paths_forward (drt_paths.hip), allocated on first use
+    void* image_loss_ws = nullptr; // pixel seeds of drt_render_image_loss (drt_image_loss.hip), allocated on first use
 };
 
 
@@ -216,6 +217,8 @@ int launch_raster(drt_scene* s, drt_scene::Sub& w, hipStream_t st, const double*
 
 // defined in drt_paths.hip
 void paths_free(drt_scene* s);
+// defined in drt_image_loss.hip
+void image_loss_free(drt_scene* s);
 
 // defined in drt_api.hip
 int ensure_slow_stack(drt_scene* s, hipStream_t st);

@@ -276,6 +276,63 @@ def check_render_args(camera_M, height, width, screen, texture, supersample=1, m
                 want_planes=bool(want_planes))
 
 
+def _plane(x, shape, name, allow_bytes):
+    """A float32 plane of ``shape`` for the device: numpy (checked for finite values, made contiguous; uint8 scaled by 1 / 255 where
+    allowed) or a device tensor (shape and dtype checked, converted by the caller)."""
+    if x is None or not (hasattr(x, "shape") and hasattr(x, "dtype")):
+        try:
+            x = None if x is None else np.asarray(x)
+        except (TypeError, ValueError):
+            x = None
+        if x is None or x.dtype == object:
+            raise ValueError(f"{name} must be an array of shape {shape}")
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(x.shape)}")
+    kind = str(x.dtype).replace("torch.", "")
+    if kind not in (("float32", "uint8") if allow_bytes else ("float32",)):
+        raise ValueError(f"{name} must be float32{' or uint8 (read as value / 255)' if allow_bytes else ''}, got dtype {kind}")
+    if isinstance(x, np.ndarray):
+        x = x.astype(np.float32) / np.float32(255.0) if kind == "uint8" else x
+        if not np.isfinite(x).all():
+            raise ValueError(f"{name} must be finite")
+        return np.ascontiguousarray(x, dtype=np.float32)
+    return x
+
+
+def _ior_arg(x, name):
+    """An IOR argument of ``Scene.image_loss_fused``: None, a positive finite float (returned), or a 0-dim tensor (None returned: its
+    value is read by the caller)."""
+    if x is None:
+        return None
+    if hasattr(x, "numel") and hasattr(x, "dtype"):
+        if x.numel() != 1:
+            raise ValueError(f"{name} must be a float or a 0-dim tensor, got shape {tuple(x.shape)}")
+        return None
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or not x > 0:
+        raise ValueError(f"{name} must be a positive finite float or a 0-dim tensor, got {x!r}")
+    return float(x)
+
+
+def check_image_loss_args(camera_M, height, width, screen, texture, target, weight=None, ior_int=None, ior_ext=None, vertices=True,
+                          want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
+                          invalid=0.0, max_samples=1 << 22):
+    """Every argument check of ``Scene.image_loss_fused``, none of which needs a device: ``check_render_args``' dict plus target
+    (float32 [H, W, C]; uint8 is read as value / 255; [H, W] with a one-channel texture), weight (float32 [H, W] or None), ior (the float
+    of each IOR given as a number, else None), vertices and want_image."""
+    a = check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples)
+    H, W, C = a["height"], a["width"], a["channels"]
+    if target is not None and hasattr(target, "shape") and len(target.shape) == 2 and C == 1:
+        target = target[:, :, None]
+    a["target"] = _plane(target, (H, W, C), "target", True)
+    a["weight"] = None if weight is None else _plane(weight, (H, W), "weight", False)
+    a["ior"] = (_ior_arg(ior_int, "ior_int"), _ior_arg(ior_ext, "ior_ext"))
+    for name, flag in (("vertices", vertices), ("want_image", want_image)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False, got {flag!r}")
+    a["vertices"], a["want_image"] = bool(vertices), bool(want_image)
+    return a
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------------------
 def _background(spec, tex):
     if spec == "checker":

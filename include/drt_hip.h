@@ -34,7 +34,7 @@ typedef struct drt_scene drt_scene_t;
 const char* drt_last_error(void);
 int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
                             * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused;
-                            * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image */
+                            * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image; 9: drt_render_image_loss */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -666,6 +666,28 @@ int drt_render_image(drt_scene_t* s, const double* d_verts, const double* camera
                      double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
                      const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
                      float* d_image, float* d_hit, float* d_through, void* stream);
+
+/* ---- the photometric loss of that image, with its vertex and IOR gradients (csrc/drt_image_loss.h states the law) ---
+ * drt_render_image's forward on rows [y0, y1) of one view, every forward quantity exactly as stated there, then, per pixel p of the band,
+ *   I[p][ch] = the float64 pixel mean (the value drt_render_image rounds to float32),  r = I - (double)d_target[p][ch],
+ *   *d_loss += w_p ((r_0^2 + r_1^2) + r_2^2),   w_p = 1, or (double)d_weight[p] with a float32 plane [height, width]
+ * and the derivative of that sum w.r.t. the vertices (d_grad_verts [V,3] +=, may be NULL: the kernel then runs without its gradient
+ * table), ior_int and ior_ext (d_grad_ior[0] +=, [1] +=; may be NULL), under torch's conventions.  Only THROUGH samples that land on the
+ * screen carry a gradient (c = T B, seed 2 w_p r_ch / s^2): bilinear -> screen plane -> path (the adjoint of
+ * drt_render_paths_law_ray_loss_ior_fused with the plane's exit seeds) and, with `fresnel`, the throughput -- every refracting
+ * interaction receives the seed of T times the product of the OTHER factors, R's adjoint follows FrDielectric line by line (a root whose
+ * argument is not positive is the constant 0 and passes nothing) and enters the bounce through ci = -(n . d).  Direct, void and invalid
+ * samples are constants; a sample's class, the face tape, the TIR flags, the entering branch, floor and the clamp of the bilinear cell and
+ * the on-screen test carry no gradient.  d_target: float32 [height, width, channels].  d_image (may be NULL): float32
+ * [height, width, channels], rows [y0, y1) written with the bits of drt_render_image.  *d_count (int64, may be NULL) += the through
+ * samples on the screen.  The accumulation targets are float64, or FxCell arrays under drt_deterministic (then exact: bands, runs and a
+ * graph replay give the same bits).  Workspace: drt_render_image's plus 8 bytes per pixel and channel; the first call of a size allocates
+ * and cannot run inside a stream capture.  Everything is enqueued on `stream`, nothing is read back.  DRT_E_INVALID as drt_render_image. */
+int drt_render_image_loss(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                          double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                          const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                          const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                          int64_t* d_count, void* stream);
 
 /* ---- measurement (bench.py's live per-kernel timing) --------------------------------------------
  * When enabled (on = 1; on = 2 additionally collects the traversal statistics below, which perturbs
