@@ -1,36 +1,20 @@
 // drt_image.hip -- the forward renderer (drt_image.h holds the law): the refracted image of the mesh in front of a textured planar
-// screen, one band of rows per call, as the wavefront loop of drt_paths.hip with the rays made in the kernel.
+// screen, one band of rows per call, as the wavefront loop of drt_paths.hip with the rays made in the kernel.  The forward wavefront
+// (image_forward, declared in drt_image_wave.h) is also what drt_render_image_loss (drt_image_loss.hip) starts with.
 //
 //   k_image_start   all samples : forms the sample ray (image_sample_ray), top-box test; candidates -> list 0 (index + float32 ray), their
 //                                 float64 ray and a throughput of 1 parked in the workspace; one state byte and one hit count per sample
-//   per interaction k = 0 .. K:
+//   per interaction k = 0 .. K (drt_pathws.h trace_lists):
 //     k_trace       list k      : drt_trace.hip's, through launch_trace_list, unchanged
-//     k_image_shade list k      : k_paths_shade without the face tape, plus the throughput update (image_interact)
-//   k_image_resolve all pixels  : walks the s x s contiguous samples of its pixel in order: class, screen plane, bilinear fetch, weight, mean
+//     k_image_shade list k      : k_paths_shade plus the throughput update (image_interact); TAPE: the loss's form, which records the face of
+//                                 the interaction in the tape of the workspace -- the renderer's own form leaves the tape alone
+//   k_image_resolve all pixels  : walks the s x s contiguous samples of its pixel in order (image_pixel_walk): class, screen plane, bilinear
+//                                 fetch, weight, mean
 // Sample i of a band belongs to pixel i / s^2 (pixel-major, sample-minor: a wave covers neighbouring pixels).  No origin / dir tensor
 // exists at any point: a sample without interaction has its camera ray formed again by the resolve kernel -- the same function, the same
 // bits.  Every list size stays on the device, nothing is read back, all launches go to the caller's stream.  The only atomics are the
 // list appends' reservations; a list's ORDER is never read (every value is stored under its sample index), so two runs give the same bits.
-#include "drt_device.h"
-#include "drt_trace_kernel.h"
-#include "drt_pathsink.h"
-#include "drt_pathws.h"
-#include "drt_image.h"
-
-struct ImageBand {
-    int width, y0, s;              // image width, first row of the band, supersampling
-    unsigned n;                    // samples of the band: rows * width * s * s
-};
-
-// sample i of the band -> its pixel and its number within the pixel
-__device__ __forceinline__ void band_sample(const ImageBand& b, unsigned i, int& x, int& y, int& j) {
-    const unsigned s2 = (unsigned)(b.s * b.s), pix = i / s2;
-    j = (int)(i - pix * s2);
-    y = b.y0 + (int)(pix / (unsigned)b.width);
-    x = (int)(pix % (unsigned)b.width);
-}
-
-struct ImageFill { double c_void[kImageMaxChannels], c_invalid[kImageMaxChannels]; };
+#include "drt_image_wave.h"
 
 __global__ void __launch_bounds__(kPathBlock) k_image_start(const Node4Q* __restrict__ nodes, int n_tris, ImageCam cam, ImageBand band,
                                                              double* __restrict__ park_ori, double* __restrict__ park_dir, double* __restrict__ thr,
@@ -61,12 +45,13 @@ __global__ void __launch_bounds__(kPathBlock) k_image_start(const Node4Q* __rest
     stage_flush(stage, out, count);
 }
 
-// list k -> list k + 1, as k_paths_shade (drt_paths.hip); FRESNEL: a refracting interaction multiplies the sample's throughput by 1 - R.
-template <bool SNELL, bool FRESNEL>
+// list k -> list k + 1, as k_paths_shade (drt_paths.hip); FRESNEL: a refracting interaction multiplies the sample's throughput by 1 - R;
+// TAPE: the face of the interaction is written to tape[k, i] (without it `tape` is never touched and may be null).
+template <bool SNELL, bool FRESNEL, bool TAPE>
 __global__ void __launch_bounds__(kPathBlock) k_image_shade(PathCtx c, int64_t n_rays, int k, int max_bounces, bool reflect, RayList in,
                                                              const unsigned* __restrict__ n_in, RayList out, unsigned* n_out,
                                                              double* __restrict__ park_ori, double* __restrict__ park_dir, double* __restrict__ thr,
-                                                             uint8_t* __restrict__ state, uint8_t* __restrict__ hits) {
+                                                             uint8_t* __restrict__ state, uint8_t* __restrict__ hits, int32_t* __restrict__ tape) {
     __shared__ StageMem stage;
     stage_init(stage);
     const unsigned n = *n_in;
@@ -86,6 +71,7 @@ __global__ void __launch_bounds__(kPathBlock) k_image_shade(PathCtx c, int64_t n
                 if (f < 0) {
                     if (path_exit_valid(n_refr)) state[i] = (uint8_t)n_refr | kPathDone;
                 } else if (!last_stage) {
+                    if constexpr (TAPE) tape[(int64_t)k * n_rays + i] = f;
                     hits[i] = (uint8_t)(k + 1);
                     d3 o = load_d3(park_ori, i), d = load_d3(park_dir, i);
                     double T = FRESNEL ? thr[i] : 1.0;
@@ -115,25 +101,8 @@ __global__ void __launch_bounds__(kPathBlock) k_image_resolve(ImageCam cam, Imag
     const int s2 = band.s * band.s;
     const int y = band.y0 + (int)(pix / band.width), x = (int)(pix % band.width);
     double acc[kImageMaxChannels] = {0.0, 0.0, 0.0};
-    int n_hit = 0, n_through = 0;
-    for (int j = 0; j < s2; ++j) {
-        const int64_t i = pix * s2 + j;
-        const bool was_hit = hits[i] != 0, done = (state[i] & kPathDone) != 0;
-        const int cls = image_class(was_hit, done);
-        n_hit += was_hit ? 1 : 0;
-        n_through += cls == kImageThrough ? 1 : 0;
-        d3 o{0.0, 0.0, 0.0}, d{0.0, 0.0, 1.0};
-        double T = 1.0;
-        if (cls == kImageDirect) {
-            image_sample_ray(cam, band.s, x, y, j, o, d);
-        } else if (cls == kImageThrough) {
-            o = load_d3(park_ori, i); d = load_d3(park_dir, i);
-            if (fresnel) T = thr[i];
-        }
-        double c[kImageMaxChannels];
-        image_sample_colour(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c);
-        for (int ch = 0; ch < tx.c; ++ch) acc[ch] = j == 0 ? c[ch] : acc[ch] + c[ch];
-    }
+    int n_hit, n_through;
+    image_pixel_walk(cam, band, pix, x, y, sc, tx, fill, fresnel, park_ori, park_dir, thr, state, hits, acc, n_hit, n_through);
     const int64_t row = (int64_t)y * band.width + x;
     for (int ch = 0; ch < tx.c; ++ch) image[row * tx.c + ch] = (float)(acc[ch] / (double)s2);
     if (hit) hit[row] = (float)((double)n_hit / (double)s2);
@@ -143,13 +112,13 @@ __global__ void __launch_bounds__(kPathBlock) k_image_resolve(ImageCam cam, Imag
 namespace {
 
 // one throughput per sample, grown like the rows of the one-pass form it sits beside
-int ensure_image_ws(drt_scene* s, int64_t n, hipStream_t st) {
+int ensure_image_thr(drt_scene* s, int64_t n, hipStream_t st, const char* who) {
     PathsWs* w = paths_ws_of(s);
     if (n <= w->thr_cap) return DRT_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(DRT_E_INVALID, "drt_render_image: the first call of this size allocates its throughputs and cannot run inside a stream "
-                                   "capture: issue one such call eagerly before capturing");
+        return fail(DRT_E_INVALID, "%s: the first call of this size allocates its throughputs and cannot run inside a stream "
+                                   "capture: issue one such call eagerly before capturing", who);
     (void)hipFree(w->thr);
     w->thr = nullptr; w->thr_cap = 0;
     HIP_TRY(hipMalloc(&w->thr, sizeof(double) * (size_t)n));
@@ -157,22 +126,20 @@ int ensure_image_ws(drt_scene* s, int64_t n, hipStream_t st) {
     return DRT_OK;
 }
 
-template <bool SNELL>
-void launch_image_shade(bool fresnel, int gs, hipStream_t st, const PathCtx& pc, int64_t n, int k, int max_bounces, bool reflect, const RayList& in,
-                        const unsigned* n_in, const RayList& out, unsigned* n_out, double* park_ori, double* park_dir, const PathsWs& w) {
-    if (fresnel) k_image_shade<SNELL, true><<<gs, kPathBlock, 0, st>>>(pc, n, k, max_bounces, reflect, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state, w.hits);
-    else k_image_shade<SNELL, false><<<gs, kPathBlock, 0, st>>>(pc, n, k, max_bounces, reflect, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state, w.hits);
+// k_image_shade under (snell, fresnel, tape)
+using ImageShade = void (*)(PathCtx, int64_t, int, int, bool, RayList, const unsigned*, RayList, unsigned*, double*, double*, double*, uint8_t*, uint8_t*, int32_t*);
+ImageShade image_shade_kernel(bool snell, bool fresnel, bool tape) {
+    static const ImageShade kernels[8] = {k_image_shade<false, false, false>, k_image_shade<false, false, true>, k_image_shade<false, true, false>,
+                                          k_image_shade<false, true, true>,   k_image_shade<true, false, false>, k_image_shade<true, false, true>,
+                                          k_image_shade<true, true, false>,   k_image_shade<true, true, true>};
+    return kernels[(snell ? 4 : 0) | (fresnel ? 2 : 0) | (tape ? 1 : 0)];
 }
 
 }  // namespace
 
-extern "C" {
-
-int drt_render_image(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
-                     double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
-                     const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
-                     float* d_image, float* d_hit, float* d_through, void* stream) {
-    CHECK_BUILT(s);
+int image_call_check(const double* camera21, int height, int width, int y0, int y1, int supersample, double ior_int, double ior_ext, int max_bounces,
+                     int law_flags, int fresnel, const double* screen9, const float* d_texture, int tex_h, int tex_w, int channels,
+                     const double* fill_void, const double* fill_invalid, bool device_ok, const char* device_msg, ImageCall& call) {
     if (max_bounces < 2 || max_bounces > kMaxBounces) return fail(DRT_E_INVALID, "max_bounces = %d: must be 2 .. %d", max_bounces, kMaxBounces);
     if (law_flags & ~(DRT_LAW_REFLECT | DRT_LAW_SNELL))
         return fail(DRT_E_INVALID, "law_flags = %d: must be a combination of DRT_LAW_REFLECT (%d) and DRT_LAW_SNELL (%d)", law_flags, DRT_LAW_REFLECT, DRT_LAW_SNELL);
@@ -183,46 +150,64 @@ int drt_render_image(drt_scene_t* s, const double* d_verts, const double* camera
     if (height < 1 || width < 1) return fail(DRT_E_INVALID, "height x width = %d x %d: the image must have at least one pixel", height, width);
     if (y0 < 0 || y1 > height || y0 >= y1) return fail(DRT_E_INVALID, "band [y0, y1) = [%d, %d): must be a non-empty range of rows inside [0, %d)", y0, y1, height);
     if (!camera21 || !screen9 || !fill_void || !fill_invalid) return fail(DRT_E_INVALID, "null host pointer argument (camera21, screen9, fill_void, fill_invalid)");
-    if (!d_texture || !d_image || (s->n_faces > 0 && !d_verts)) return fail(DRT_E_INVALID, "null device pointer argument (d_verts, d_texture, d_image)");
-    ImageCam cam;
-    memcpy(cam.kinv, camera21, sizeof(double) * 9);
-    memcpy(cam.rinv, camera21 + 9, sizeof(double) * 12);
-    const ImageScreen sc{d3{screen9[0], screen9[1], screen9[2]}, d3{screen9[3], screen9[4], screen9[5]}, d3{screen9[6], screen9[7], screen9[8]}};
-    if (!image_screen_ok(sc)) return fail(DRT_E_INVALID, "screen9: the axes eu, ev must be finite, non-zero and orthogonal (|eu . ev| <= 1e-12 |eu| |ev|)");
+    if (!device_ok) return fail(DRT_E_INVALID, "%s", device_msg);
+    memcpy(call.cam.kinv, camera21, sizeof(double) * 9);
+    memcpy(call.cam.rinv, camera21 + 9, sizeof(double) * 12);
+    call.sc = ImageScreen{d3{screen9[0], screen9[1], screen9[2]}, d3{screen9[3], screen9[4], screen9[5]}, d3{screen9[6], screen9[7], screen9[8]}};
+    if (!image_screen_ok(call.sc)) return fail(DRT_E_INVALID, "screen9: the axes eu, ev must be finite, non-zero and orthogonal (|eu . ev| <= 1e-12 |eu| |ev|)");
     const int s2 = supersample * supersample;
-    const int64_t n_pix = (int64_t)(y1 - y0) * width, n = n_pix * s2;
-    if (n > INT32_MAX) return fail(DRT_E_INVALID, "the band has %lld samples: at most 2^31 - 1 per call (render fewer rows)", (long long)n);
-    hipStream_t st = (hipStream_t)stream;
-    { int rc = ensure_paths_ws(s, n, st, "drt_render_image"); if (rc) return rc; }
-    { int rc = ensure_paths_fused_ws(s, n, st, "drt_render_image"); if (rc) return rc; }
-    { int rc = ensure_image_ws(s, n, st); if (rc) return rc; }
+    call.n_pix = (int64_t)(y1 - y0) * width;
+    call.n = call.n_pix * s2;
+    if (call.n > INT32_MAX) return fail(DRT_E_INVALID, "the band has %lld samples: at most 2^31 - 1 per call (render fewer rows)", (long long)call.n);
+    call.tx = ImageTex{d_texture, tex_h, tex_w, channels};
+    call.fill = ImageFill{};
+    for (int ch = 0; ch < channels; ++ch) { call.fill.c_void[ch] = fill_void[ch]; call.fill.c_invalid[ch] = fill_invalid[ch]; }
+    call.band = ImageBand{width, y0, supersample, (unsigned)call.n};
+    call.ior_int = ior_int; call.ior_ext = ior_ext;
+    call.max_bounces = max_bounces;
+    call.reflect = (law_flags & DRT_LAW_REFLECT) != 0; call.snell = (law_flags & DRT_LAW_SNELL) != 0; call.fresnel = fresnel != 0;
+    return DRT_OK;
+}
+
+int image_forward(drt_scene* s, const double* d_verts, const ImageCall& c, bool keep_tape, hipStream_t st, const char* who) {
+    { int rc = ensure_paths_ws(s, c.n, st, who); if (rc) return rc; }
+    { int rc = ensure_paths_fused_ws(s, c.n, st, who); if (rc) return rc; }
+    { int rc = ensure_image_thr(s, c.n, st, who); if (rc) return rc; }
     { int rc = wait_build(s, st); if (rc) return rc; }
     const PathsWs& w = *paths_ws_of(s);
-    PathCtx pc = path_ctx(s, d_verts, ior_int, ior_ext);
-    pc.tc.slow_stack = w.slow_stack;
-    const ImageBand band{width, y0, supersample, (unsigned)n};
-    const ImageTex tx{d_texture, tex_h, tex_w, channels};
-    ImageFill fill{};
-    for (int ch = 0; ch < channels; ++ch) { fill.c_void[ch] = fill_void[ch]; fill.c_invalid[ch] = fill_invalid[ch]; }
-    const int gs = grid_for(n, kPathBlock, 8 * s->n_cu);
-    double* const park_ori = w.park;                 // the rows of the one-pass form: scratch to every call, the face tape is left alone
+    const PathCtx pc = image_path_ctx(s, d_verts, c);
+    const int gs = grid_for(c.n, kPathBlock, 8 * s->n_cu);
+    double* const park_ori = w.park;                 // the rows of the one-pass form: scratch to every call
     double* const park_dir = w.park + 3 * w.fused_cap;
-    const bool reflect = (law_flags & DRT_LAW_REFLECT) != 0, snell = (law_flags & DRT_LAW_SNELL) != 0;
     HIP_TRY(hipMemsetAsync(w.cnt, 0, sizeof(unsigned) * kCntWords, st));
-    const RayList l0{w.idx[0], w.ray[0], w.face[0]}, l1{w.idx[1], w.ray[1], w.face[1]};
-    k_image_start<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, cam, band, park_ori, park_dir, w.thr, w.state, w.hits, l0, w.cnt + kCntList);
+    const RayList l0{w.idx[0], w.ray[0], w.face[0]};
+    k_image_start<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, c.cam, c.band, park_ori, park_dir, w.thr, w.state, w.hits, l0, w.cnt + kCntList);
     if (s->n_faces > 0) {
-        for (int k = 0; k <= max_bounces; ++k) {
-            const RayList& in = (k & 1) ? l1 : l0;
-            const RayList& out = (k & 1) ? l0 : l1;
-            launch_trace_list(k < max_bounces ? kTraceClosest : kTraceAny, s->grid_path, st, pc.tc, in.ray, w.cnt + kCntList + k,
-                              TraceOut{in.face, nullptr, nullptr, nullptr}, w.redo, w.cnt + kCntRedo + k, w.cnt + kCntDone, s->refill_min, s->inner_min, nullptr);
-            if (snell) launch_image_shade<true>(fresnel != 0, gs, st, pc, n, k, max_bounces, reflect, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1, park_ori, park_dir, w);
-            else launch_image_shade<false>(fresnel != 0, gs, st, pc, n, k, max_bounces, reflect, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1, park_ori, park_dir, w);
-        }
+        const ImageShade shade = image_shade_kernel(c.snell, c.fresnel, keep_tape);
+        int32_t* const tape = keep_tape ? w.tape : nullptr;
+        trace_lists(s, w, pc.tc, st, c.max_bounces, [&](int k, const RayList& in, const unsigned* n_in, const RayList& out, unsigned* n_out) {
+            shade<<<gs, kPathBlock, 0, st>>>(pc, (int64_t)c.n, k, c.max_bounces, c.reflect, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state, w.hits, tape);
+        });
     }
-    k_image_resolve<<<(unsigned)((n_pix + kPathBlock - 1) / kPathBlock), kPathBlock, 0, st>>>(cam, band, n_pix, sc, tx, fill, fresnel != 0, park_ori, park_dir, w.thr, w.state,
-                                                                                               w.hits, d_image, d_hit, d_through);
+    return DRT_OK;
+}
+
+extern "C" {
+
+int drt_render_image(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                     double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                     const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                     float* d_image, float* d_hit, float* d_through, void* stream) {
+    CHECK_BUILT(s);
+    ImageCall c;
+    { int rc = image_call_check(camera21, height, width, y0, y1, supersample, ior_int, ior_ext, max_bounces, law_flags, fresnel, screen9, d_texture, tex_h, tex_w,
+                                channels, fill_void, fill_invalid, d_texture && d_image && (s->n_faces == 0 || d_verts),
+                                "null device pointer argument (d_verts, d_texture, d_image)", c); if (rc) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    { int rc = image_forward(s, d_verts, c, false, st, "drt_render_image"); if (rc) return rc; }
+    const PathsWs& w = *paths_ws_of(s);
+    k_image_resolve<<<(unsigned)((c.n_pix + kPathBlock - 1) / kPathBlock), kPathBlock, 0, st>>>(c.cam, c.band, c.n_pix, c.sc, c.tx, c.fill, c.fresnel, w.park,
+                                                                                                 w.park + 3 * w.fused_cap, w.thr, w.state, w.hits, d_image, d_hit, d_through);
     HIP_TRY(hipGetLastError());
     return DRT_OK;
 }

@@ -1,0 +1,84 @@
+// drt_image_wave.h -- what the two calls on the refracted image share (drt_image.hip: drt_render_image; drt_image_loss.hip:
+// drt_render_image_loss): the band of rows of one call, the checked call, the forward wavefront (defined in drt_image.hip, as
+// launch_trace_list is in drt_trace.hip) and the walk over the samples of a pixel that both resolve kernels make.
+#pragma once
+#include "drt_device.h"
+#include "drt_pathws.h"
+#include "drt_image.h"
+
+struct ImageBand {
+    int width, y0, s;              // image width, first row of the band, supersampling
+    unsigned n;                    // samples of the band: rows * width * s * s
+};
+
+// sample i of the band -> its pixel and its number within the pixel
+__device__ __forceinline__ void band_sample(const ImageBand& b, unsigned i, int& x, int& y, int& j) {
+    const unsigned s2 = (unsigned)(b.s * b.s), pix = i / s2;
+    j = (int)(i - pix * s2);
+    y = b.y0 + (int)(pix / (unsigned)b.width);
+    x = (int)(pix % (unsigned)b.width);
+}
+
+struct ImageFill { double c_void[kImageMaxChannels], c_invalid[kImageMaxChannels]; };
+
+// One call after image_call_check: the arguments the two entry points have in common, unpacked.
+struct ImageCall {
+    ImageCam cam;
+    ImageScreen sc;
+    ImageTex tx;
+    ImageFill fill;
+    ImageBand band;
+    int64_t n_pix, n;              // pixels and samples of the band
+    double ior_int, ior_ext;
+    int max_bounces;
+    bool reflect, snell, fresnel;
+};
+
+// The argument checks of the two entry points (after CHECK_BUILT), in the order in which their errors win: scalars, host pointers, the
+// entry point's own device pointers (device_ok, and device_msg when not), the screen, the sample count.  Fills `call` on DRT_OK.
+int image_call_check(const double* camera21, int height, int width, int y0, int y1, int supersample, double ior_int, double ior_ext, int max_bounces,
+                     int law_flags, int fresnel, const double* screen9, const float* d_texture, int tex_h, int tex_w, int channels,
+                     const double* fill_void, const double* fill_invalid, bool device_ok, const char* device_msg, ImageCall& call);
+
+// The forward wavefront on `st`: the workspace grown to the band (ray lists, rows of the one-pass form, throughputs; never inside a stream
+// capture), the build waited for, the counters zeroed, k_image_start, then K + 1 rounds of k_trace and k_image_shade.  Afterwards the
+// workspace holds per sample the state byte, the hit count, the parked exit ray and the throughput; with keep_tape also the face tape
+// [K, n] -- without it the tape is left untouched.  `who`: the entry point, for messages.
+int image_forward(drt_scene* s, const double* d_verts, const ImageCall& call, bool keep_tape, hipStream_t st, const char* who);
+
+// The context image_forward traced with (the same for the adjoint of the loss).
+inline PathCtx image_path_ctx(const drt_scene* s, const double* d_verts, const ImageCall& call) {
+    PathCtx pc = path_ctx(s, d_verts, call.ior_int, call.ior_ext);
+    pc.tc.slow_stack = static_cast<const PathsWs*>(s->paths_ws)->slow_stack;
+    return pc;
+}
+
+// The s x s contiguous samples of pixel `pix` = (x, y) of the band, in order: class, the camera ray formed again (direct) or the parked
+// exit ray and throughput (through), colour; sum[0 .. tx.c) is the ordered float64 sum of the colours, n_hit / n_through count the
+// samples that met the mesh / completed their path.
+__device__ __forceinline__ void image_pixel_walk(const ImageCam& cam, const ImageBand& band, int64_t pix, int x, int y, const ImageScreen& sc, const ImageTex& tx,
+                                                 const ImageFill& fill, bool fresnel, const double* __restrict__ park_ori,
+                                                 const double* __restrict__ park_dir, const double* __restrict__ thr,
+                                                 const uint8_t* __restrict__ state, const uint8_t* __restrict__ hits, double* sum, int& n_hit,
+                                                 int& n_through) {
+    const int s2 = band.s * band.s;
+    n_hit = 0; n_through = 0;
+    for (int j = 0; j < s2; ++j) {
+        const int64_t i = pix * s2 + j;
+        const bool was_hit = hits[i] != 0, done = (state[i] & kPathDone) != 0;
+        const int cls = image_class(was_hit, done);
+        n_hit += was_hit ? 1 : 0;
+        n_through += cls == kImageThrough ? 1 : 0;
+        d3 o{0.0, 0.0, 0.0}, d{0.0, 0.0, 1.0};
+        double T = 1.0;
+        if (cls == kImageDirect) {
+            image_sample_ray(cam, band.s, x, y, j, o, d);
+        } else if (cls == kImageThrough) {
+            o = load_d3(park_ori, i); d = load_d3(park_dir, i);
+            if (fresnel) T = thr[i];
+        }
+        double c[kImageMaxChannels];
+        image_sample_colour(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c);
+        for (int ch = 0; ch < tx.c; ++ch) sum[ch] = j == 0 ? c[ch] : sum[ch] + c[ch];
+    }
+}

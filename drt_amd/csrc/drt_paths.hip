@@ -156,9 +156,8 @@ __global__ void k_paths_count(const unsigned* __restrict__ count, int64_t* __res
 }
 
 // Backward over the list of valid rays: recompute every interaction from the camera ray and the face tape, reverse, scatter the vertex
-// gradients through the LDS hash sink.  A ray brings up to 3 * K vertex references (24 at K = 8, against 6 of the two-bounce path), so a
-// table fill takes a quarter of k_render_bwd's rays; neighbouring rays still share most of their vertices.
-constexpr int kPathsBwdBatch = 256;
+// gradients through the LDS hash sink, kPathsBwdBatch rays per table fill (drt_pathsink.h); neighbouring rays still share most of their
+// vertices.
 template <bool DET, bool SNELL>
 __global__ void __launch_bounds__(256) k_paths_bwd(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir, int64_t n_rays,
                                                    int max_bounces, const int32_t* __restrict__ tape, const uint8_t* __restrict__ hits,
@@ -236,13 +235,6 @@ __global__ void __launch_bounds__(256) k_paths_loss_bwd(PathCtx c, const double*
 // thread and per wave and flushed with one atomic per wave into grad_ior[0] / [1] -- float64, or, deterministic, two FxCells (exact, as the
 // loss).  VERTS = false is the calibration mode of a fixed mesh: no vertex gradient is wanted, `add` discards, the kernel has no table in
 // LDS and the compiler drops the vertex chains of the adjoints.
-struct DiscardAdd3 {
-    __device__ __forceinline__ void operator()(int32_t, d3) const {}
-};
-template <bool DET>
-__device__ __forceinline__ double* paths_ior_slot(double* ior, int k) {
-    return DET ? reinterpret_cast<double*>(reinterpret_cast<FxCell*>(ior) + k) : ior + k;
-}
 template <bool DET, bool SNELL, bool VERTS>
 __global__ void __launch_bounds__(256) k_paths_loss_bwd_ior(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir,
                                                             const double* __restrict__ screen_pixel, int64_t n_rays, int max_bounces,
@@ -397,23 +389,20 @@ void paths_free(drt_scene* s) {
     s->paths_ws = nullptr;
 }
 
-// The wavefront loop behind list 0: trace list k, shade it into list k + 1 (the other ping-pong buffer), K + 1 times.  ray_ori / ray_dir
-// [N,3]: the rows the float64 ray in flight parks in; hits [N], tape [K,N]: written per list item.
-static void trace_lists(drt_scene* s, const PathsWs& w, const PathCtx& pc, hipStream_t st, int gs, int64_t n_rays, int max_bounces, bool reflect,
-                        bool snell, double* ray_ori, double* ray_dir, uint8_t* hits, int32_t* tape) {
-    const RayList l0{w.idx[0], w.ray[0], w.face[0]}, l1{w.idx[1], w.ray[1], w.face[1]};
-    for (int k = 0; k <= max_bounces; ++k) {
-        const RayList& in = (k & 1) ? l1 : l0;
-        const RayList& out = (k & 1) ? l0 : l1;
-        launch_trace_list(k < max_bounces ? kTraceClosest : kTraceAny, s->grid_path, st, pc.tc, in.ray, w.cnt + kCntList + k,
-                          TraceOut{in.face, nullptr, nullptr, nullptr}, w.redo, w.cnt + kCntRedo + k, w.cnt + kCntDone, s->refill_min, s->inner_min, nullptr);
+// The pass loop (drt_pathws.h trace_lists) with k_paths_shade.  ray_ori / ray_dir [N,3]: the rows the float64 ray in flight parks in;
+// hits [N], tape [K,N]: written per list item.
+static void paths_rounds(drt_scene* s, const PathsWs& w, const PathCtx& pc, hipStream_t st, int gs, int64_t n_rays, int max_bounces, bool reflect,
+                         bool snell, double* ray_ori, double* ray_dir, uint8_t* hits, int32_t* tape) {
+    trace_lists(s, w, pc.tc, st, max_bounces, [&](int k, const RayList& in, const unsigned* n_in, const RayList& out, unsigned* n_out) {
         if (snell)
-            k_paths_shade<true><<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1,
-                                                           ray_ori, ray_dir, w.state, hits, tape);
+            k_paths_shade<true><<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect, in, n_in, out, n_out, ray_ori, ray_dir, w.state, hits, tape);
         else
-            k_paths_shade<false><<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1,
-                                                            ray_ori, ray_dir, w.state, hits, tape);
-    }
+            k_paths_shade<false><<<gs, kPathBlock, 0, st>>>(pc, n_rays, k, max_bounces, reflect, in, n_in, out, n_out, ray_ori, ray_dir, w.state, hits, tape);
+    });
+}
+
+void launch_paths_collect(int grid, hipStream_t st, unsigned n, const uint8_t* state, int32_t* done_idx, unsigned* n_done) {
+    k_paths_collect<<<grid, kPathBlock, 0, st>>>(n, state, done_idx, n_done);
 }
 
 // The bodies behind the entry points; the law has been checked.  `who`: the entry point, for messages.
@@ -440,7 +429,7 @@ static int paths_forward(drt_scene* s, const double* d_verts, const double* d_or
     HIP_TRY(hipMemsetAsync(d_tape, 0xFF, sizeof(int32_t) * (size_t)max_bounces * (size_t)n_rays, st));
     const RayList l0{w.idx[0], w.ray[0], w.face[0]};
     k_paths_start<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, d_origin, d_dir, n, d_out_ori, d_out_dir, w.state, d_hits, l0, w.cnt + kCntList);
-    trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, snell, d_out_ori, d_out_dir, d_hits, d_tape);
+    paths_rounds(s, w, pc, st, gs, n_rays, max_bounces, reflect, snell, d_out_ori, d_out_dir, d_hits, d_tape);
     k_paths_finish<<<gs, kPathBlock, 0, st>>>(n, d_out_ori, d_out_dir, d_mask, w.state, d_hits, d_valid_idx, w.cnt + kCntValid);
     k_paths_count<<<1, 64, 0, st>>>(w.cnt + kCntValid, d_n_valid);
     HIP_TRY(hipGetLastError());
@@ -484,9 +473,9 @@ static int paths_ray_loss_fused(drt_scene* s, const double* d_verts, const doubl
     HIP_TRY(hipMemsetAsync(w.cnt, 0, sizeof(unsigned) * kCntWords, st));
     const RayList l0{w.idx[0], w.ray[0], w.face[0]};
     k_paths_start_fused<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, d_origin, d_dir, d_valid, n, park_ori, park_dir, w.state, l0, w.cnt + kCntList);
-    trace_lists(s, w, pc, st, gs, n_rays, max_bounces, reflect, snell, park_ori, park_dir, w.hits, w.tape);
+    paths_rounds(s, w, pc, st, gs, n_rays, max_bounces, reflect, snell, park_ori, park_dir, w.hits, w.tape);
     int32_t* const done = w.idx[0];          // (both ping-pong lists are free once the loop has ended)
-    k_paths_collect<<<gs, kPathBlock, 0, st>>>(n, w.state, done, w.cnt + kCntValid);
+    launch_paths_collect(gs, st, n, w.state, done, w.cnt + kCntValid);
     if (d_grad_ior)
         DET_LAW_VERTS_LAUNCH(k_paths_loss_bwd_ior, snell, d_grad_verts != nullptr, (d_grad_verts ? DRT_BWD_BPC : kPathsIorBpc) * s->n_cu, 256, st, pc, d_origin, d_dir,
                              d_screen_pixel, n_rays, max_bounces, park_ori, park_dir, w.tape, w.hits, done, w.cnt + kCntValid, d_loss, d_grad_verts, d_grad_ior,

@@ -1,6 +1,6 @@
 // drt_pathsink.h -- what the path kernels of more than one translation unit share (drt_pipeline.hip: the two-bounce pipeline;
-// drt_paths.hip: paths of up to K interactions): the compact ray list, the staged list append and the LDS hash sink of the
-// vertex gradients.
+// drt_paths.hip: paths of up to K interactions; drt_image.hip / drt_image_loss.hip: the refracted image and its loss): the compact
+// ray list, the staged list append, the LDS hash sink of the vertex gradients and the small pieces of the K-interaction backward kernels.
 #pragma once
 #include "drt_device.h"
 
@@ -194,3 +194,16 @@ struct PathSink {
     __device__ __forceinline__ void clear() const { if (DET) fx_hash_clear(keys, lo(), hi()); else hash_clear(keys, sums); }
     __device__ __forceinline__ void flush() const { if (DET) fx_hash_flush(keys, lo(), hi(), g); else hash_flush(keys, sums, g); }
 };
+
+// The backward kernels of the K-interaction law (drt_paths.hip, drt_image_loss.hip).  A ray brings up to 3 * K vertex references (24 at
+// K = 8, against 6 of the two-bounce path), so a table fill takes a quarter of k_render_bwd's rays.
+constexpr int kPathsBwdBatch = 256;
+// The sink of a call that wants no vertex gradient: the kernel has no table in LDS and the compiler drops the vertex chains of the adjoints.
+struct DiscardAdd3 {
+    __device__ __forceinline__ void operator()(int32_t, d3) const {}
+};
+// Element k of an IOR-gradient target in the two accumulation modes: float64, or, deterministic, an FxCell.
+template <bool DET>
+__device__ __forceinline__ double* paths_ior_slot(double* ior, int k) {
+    return DET ? reinterpret_cast<double*>(reinterpret_cast<FxCell*>(ior) + k) : ior + k;
+}

@@ -1,8 +1,10 @@
 // drt_pathws.h -- what the translation units that run the K-interaction wavefront loop share (drt_paths.hip: the path calls; drt_image.hip:
-// the forward renderer): the workspace behind drt_scene::paths_ws, the per-ray state byte, the counter block and the block runs that keep
-// a staged append in input order.
+// the forward wavefront of the refracted image; drt_image_loss.hip: its loss): the workspace behind drt_scene::paths_ws, the per-ray state
+// byte, the counter block, the block runs that keep a staged append in input order, the pass loop and the launcher of k_paths_collect.
 #pragma once
 #include "drt_device.h"
+#include "drt_trace_kernel.h"
+#include "drt_pathsink.h"
 #include "drt_paths.h"
 
 // per-ray state byte while a call is in flight: refractions made so far (<= 8) | kPathDone once the path has ended valid
@@ -26,7 +28,7 @@ struct PathsWs {
     double* park = nullptr;
     int32_t* tape = nullptr;
     uint8_t* hits = nullptr;
-    // the forward renderer only (drt_image.hip), beside the rows of the one-pass form: one float64 throughput per sample
+    // the forward wavefront of the image only (drt_image.hip image_forward), beside the rows of the one-pass form: one float64 throughput per sample
     int64_t thr_cap = 0;
     double* thr = nullptr;
 };
@@ -44,3 +46,19 @@ inline PathsWs* paths_ws_of(drt_scene* s) { return static_cast<PathsWs*>(s->path
 int ensure_paths_ws(drt_scene* s, int64_t n, hipStream_t st, const char* who);
 // ... and the workspace rows of the one-pass form (parked float64 rays, face tape, hit counts); needs ensure_paths_ws first
 int ensure_paths_fused_ws(drt_scene* s, int64_t n, hipStream_t st, const char* who);
+// defined in drt_paths.hip: k_paths_collect -- the rays whose state byte says that the path completed -> index list done_idx, its size in *n_done
+void launch_paths_collect(int grid, hipStream_t st, unsigned n, const uint8_t* state, int32_t* done_idx, unsigned* n_done);
+
+// The wavefront loop behind list 0: trace list k (closest hit; any hit at k = K, where every interaction is used up), shade it into list
+// k + 1 (the other ping-pong buffer), K + 1 times.  shade(k, in, n_in, out, n_out) launches the caller's shade kernel of round k on `st`.
+template <typename Shade>
+inline void trace_lists(const drt_scene* s, const PathsWs& w, const TraceCtx& tc, hipStream_t st, int max_bounces, Shade shade) {
+    const RayList l0{w.idx[0], w.ray[0], w.face[0]}, l1{w.idx[1], w.ray[1], w.face[1]};
+    for (int k = 0; k <= max_bounces; ++k) {
+        const RayList& in = (k & 1) ? l1 : l0;
+        const RayList& out = (k & 1) ? l0 : l1;
+        launch_trace_list(k < max_bounces ? kTraceClosest : kTraceAny, s->grid_path, st, tc, in.ray, w.cnt + kCntList + k,
+                          TraceOut{in.face, nullptr, nullptr, nullptr}, w.redo, w.cnt + kCntRedo + k, w.cnt + kCntDone, s->refill_min, s->inner_min, nullptr);
+        shade(k, in, w.cnt + kCntList + k, out, w.cnt + kCntList + k + 1);
+    }
+}

@@ -1,7 +1,7 @@
 // drt_scene.h -- what the translation units of libdrt_hip.so share: the scene object behind drt_scene_t, launch
 // constants, error plumbing, the per-stage timer.  (drt_build.hip: LBVH build + checks; drt_trace.hip: B1 queries and
-// closest point; drt_pipeline.hip: the refraction pipeline, its backward and losses; drt_paths.hip: paths of up to K interactions; drt_edges.hip: silhouette and
-// smoothness branches; drt_api.hip: create / destroy / profiling.)
+// closest point; drt_pipeline.hip: the refraction pipeline, its backward and losses; drt_paths.hip: paths of up to K interactions; drt_image.hip:
+// the refracted image and its forward wavefront; drt_image_loss.hip: the loss of that image; drt_edges.hip: silhouette and smoothness branches; drt_api.hip: create / destroy / profiling.)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared.  Wave size is 64 throughout.
 #pragma once

@@ -1,7 +1,7 @@
 // tests/hostsim/image_loss.cpp -- drt_amd/csrc/drt_image_loss.h compiled for the host (g++ -ffp-contract=off): the photometric loss of the
 // refracted image and its adjoint, run over a whole view in plain loops.  The classes and the face tape are handed in (the restatement's,
 // from the oracle's tracer), so that no tracer takes part: a through sample's exit ray and throughput are recomputed from its tape with the
-// functions k_image_loss_shade runs (image_interact), its adjoint is image_sample_backward -- what k_image_loss_bwd runs.  Test-only.
+// functions k_image_shade runs (image_interact), its adjoint is image_sample_backward -- what k_image_loss_bwd runs.  Test-only.
 #include "../../drt_amd/csrc/drt_image_loss.h"
 
 using namespace drt;

@@ -13,7 +13,7 @@ import image_cases
 import image_loss_cases as cases
 import image_loss_ref
 from conftest import IOR
-from drt_amd import _lib, det, diffrender as Render, render
+from drt_amd import _lib, det, diffrender as Render, render, views
 
 pytestmark = pytest.mark.gpu
 EXT = cases.EXT
@@ -122,16 +122,17 @@ def test_the_calls_own_image_as_target_gives_a_loss_of_rounding_only(hand_scene)
 
 # ------------------------------------------------------------------------------------------------------------------ bands, repeats, modes
 def _small_view(scene, height, width, s, channels, **kw):
-    """A view of the hand against a random target: (loss, grad_V, g_int, g_ext) on the device."""
+    """A view of the hand against a random target: (loss, grad_V, g_int, g_ext) on the device, and the image behind them with want_image."""
     center, extent = image_cases.frame()
     cam = image_cases.camera(5, height, width)
     screen = render.Screen.behind(cam, center, extent, image_cases.TEX, image_cases.TEX, span=image_cases.SPAN)
     target = np.random.default_rng(3).random((height, width, channels), dtype=np.float32)[:, :, 0 if channels == 1 else slice(None)]
     ii = torch.tensor(IOR, dtype=torch.float64, device="cuda", requires_grad=True)
     ie = torch.tensor(EXT, dtype=torch.float64, device="cuda", requires_grad=True)
-    loss = scene.image_loss_fused(cam, height, width, screen, image_cases.texture(channels), np.ascontiguousarray(target), ior_int=ii, ior_ext=ie, supersample=s, max_bounces=6,
-                                  tir="reflect", refraction="snell", void=0.25, invalid=0.75, **kw)
-    return (loss.detach().clone(),) + tuple(g.clone() for g in torch.autograd.grad(loss, [scene.vertices, ii, ie]))
+    out = scene.image_loss_fused(cam, height, width, screen, image_cases.texture(channels), np.ascontiguousarray(target), ior_int=ii, ior_ext=ie, supersample=s, max_bounces=6,
+                                 tir="reflect", refraction="snell", void=0.25, invalid=0.75, **kw)
+    loss, image = (out[0], (out[1],)) if kw.get("want_image") else (out, ())
+    return (loss.detach().clone(),) + tuple(g.clone() for g in torch.autograd.grad(loss, [scene.vertices, ii, ie])) + image
 
 
 def _banded_cases(scene):
@@ -226,6 +227,53 @@ def test_a_captured_replay_gives_the_eager_bits(deterministic):
         with torch.cuda.graph(g2):
             scene.image_loss_fused(sc["camera_M"], sc["height"], sc["width"], sc["screen"], tex, tgt, supersample=4, void=sc["void"], invalid=sc["invalid"])
     torch.cuda.synchronize()
+
+
+def test_calls_of_growing_and_shrinking_size_on_one_scene_give_the_bits_of_a_fresh_scene(deterministic):
+    """render_image and image_loss_fused grow one workspace (ray lists, parked rows and tape, throughputs; the loss also its pixel seeds):
+    render_image sizes it for 1 024 samples of 256 pixels; the loss of 480 samples finds all of that large enough and allocates only its
+    seeds, for 480 pixels; then the first size again, as an image and as a loss whose seeds are now more than it needs.  Every result is
+    that of the same call on a scene built for it alone, and the one-pass path call, which shares the lists, the rows and the tape the loss
+    has just written, is not disturbed."""
+    mesh = image_cases.hand()
+    center, extent = image_cases.frame()
+
+    def fresh():
+        scene = Render.Scene(mesh, 0)
+        scene.update_verticex(torch.tensor(mesh.vertices, dtype=torch.float64, device="cuda", requires_grad=True))
+        return scene
+
+    def image(scene, height, width, s):
+        cam = image_cases.camera(5, height, width)
+        screen = render.Screen.behind(cam, center, extent, image_cases.TEX, image_cases.TEX, span=image_cases.SPAN)
+        return scene.render_image(cam, height, width, screen, image_cases.texture(3), supersample=s, max_bounces=6, tir="reflect", refraction="snell", void=0.25,
+                                  invalid=0.75, want_planes=True)
+
+    cam = image_cases.camera(5, 24, 20)
+    o, d = (t.cuda() for t in views.generate_ray(24, 20, cam[3], cam[2]))
+    rng = np.random.default_rng(5)
+    sp = torch.tensor(rng.standard_normal((24 * 20, 3)) * 40.0 + np.asarray(center) + np.array([0.0, 0.0, 150.0]), device="cuda")
+    valid = torch.tensor(rng.random(24 * 20) > 0.1, device="cuda")
+
+    def paths(scene):
+        loss = scene.paths_ray_loss_fused(o, d, sp, valid, 6, "reflect", "snell")
+        return loss.detach().clone(), torch.autograd.grad(loss, scene.vertices)[0].clone()
+
+    steps = [lambda sc: image(sc, 16, 16, 2),
+             lambda sc: _small_view(sc, 24, 20, 1, 3, want_image=True),
+             paths,
+             lambda sc: image(sc, 16, 16, 2),
+             lambda sc: _small_view(sc, 16, 16, 2, 3, want_image=True)]
+    scene = fresh()
+    got = [step(scene) for step in steps]
+    assert got[0][1].max() > 0 and got[0][2].max() > 0                                    # the object is in the picture and light gets through it
+    assert float(got[1][0]) > 0 and got[1][1].any() and got[1][2] != 0 and float(got[2][0]) > 0 and got[2][1].any()
+    for step, mine in zip(steps, got):
+        alone = step(fresh())
+        assert len(alone) == len(mine)
+        for a, b in zip(alone, mine):
+            assert torch.equal(a, b)
+    assert torch.equal(got[4][4], got[3][0])                                             # (and want_image is render_image at that size too)
 
 
 # -------------------------------------------------------------------------------------------------------------------------- the C ABI
