@@ -79,38 +79,18 @@ __global__ void __launch_bounds__(256) k_image_loss_bwd(PathCtx c, ImageCam cam,
     if (n > (int64_t)band.n) n = band.n;
     LossAcc<DET> acc_int, acc_ext;
     unsigned cnt = 0;
-    if constexpr (VERTS) {
-        __shared__ int32_t hkeys[kHashSize];
-        __shared__ double hsums[3 * kHashSize];
-        const PathSink<DET> add{hkeys, hsums, grad_verts};
-        for (int64_t base = blockIdx.x * (int64_t)kPathsBwdBatch; base < n; base += (int64_t)gridDim.x * kPathsBwdBatch) {
-            add.clear();
-            const int64_t end = base + kPathsBwdBatch < n ? base + kPathsBwdBatch : n;
-            for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
-                const int64_t i = list[k];
-                if (i < 0 || i >= (int64_t)band.n) continue;
-                double gi, ge;
-                if (loss_bwd_sample<SNELL, FRESNEL>(c, cam, band, sc, tx, max_bounces, park_ori, park_dir, thr, tape, hits, g_c, i, add, gi, ge)) {
-                    acc_int.add(gi); acc_ext.add(ge);
-                    ++cnt;
-                }
-            }
-            add.flush();
+    sink_pass<DET, kPathsBwdBatch, VERTS>(n, grad_verts, [&](int64_t k, auto add) {
+        const int64_t i = list[k];
+        if (i < 0 || i >= (int64_t)band.n) return;
+        double gi, ge;
+        if (loss_bwd_sample<SNELL, FRESNEL>(c, cam, band, sc, tx, max_bounces, park_ori, park_dir, thr, tape, hits, g_c, i, add, gi, ge)) {
+            acc_int.add(gi); acc_ext.add(ge);
+            ++cnt;
         }
-    } else {
-        for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t i = list[k];
-            if (i < 0 || i >= (int64_t)band.n) continue;
-            double gi, ge;
-            if (loss_bwd_sample<SNELL, FRESNEL>(c, cam, band, sc, tx, max_bounces, park_ori, park_dir, thr, tape, hits, g_c, i, DiscardAdd3{}, gi, ge)) {
-                acc_int.add(gi); acc_ext.add(ge);
-                ++cnt;
-            }
-        }
-    }
+    });
     if (grad_ior) {
-        acc_int.flush(paths_ior_slot<DET>(grad_ior, 0));
-        acc_ext.flush(paths_ior_slot<DET>(grad_ior, 1));
+        acc_int.flush(ior_slot<DET>(grad_ior, 0));
+        acc_ext.flush(ior_slot<DET>(grad_ior, 1));
     }
     if (count && cnt) atomicAdd(count, (unsigned long long)cnt);
 }

@@ -2,7 +2,8 @@
 //
 //   trace_path              <- Scene.trace2 + the occlusion test of Scene.render_transparent
 //                              (reference DiffRender.py:537-546, 420-432)
-//   path_recompute_backward <- what autograd does for that graph w.r.t. Scene.vertices
+//   path_recompute +
+//   path_backward           <- what autograd does for that graph w.r.t. Scene.vertices
 // Plain C++ (also compiled by tests/hostsim); the gradient sink is a functor so the GPU
 // can use float64 atomics.
 #pragma once
@@ -60,17 +61,18 @@ DRT_HD bool trace_path(const PathCtx& c, Stack& st, d3 o, d3 d, int32_t& f1, int
     return true;
 }
 
-// Recompute both bounces from the saved face ids, reverse them, hand the six vertex
-// gradients to `add(vertex_id, d3)`.
-template <typename Add>
-DRT_HD void path_recompute_backward(const PathCtx& c, d3 o, d3 d, int32_t f1, int32_t f2, d3 g_ori, d3 g_dir, Add add) {
+// Recompute both bounces from the saved face ids: b1, b2 on the faces whose vertex ids are vid1, vid2.
+DRT_HD void path_recompute(const PathCtx& c, d3 o, d3 d, int32_t f1, int32_t f2, Bounce& b1, Bounce& b2, int32_t (&vid1)[3], int32_t (&vid2)[3]) {
     d3 v0, v1, v2;
-    int32_t vid1[3], vid2[3];
-    Bounce b1, b2;
     load_tri64(c, f1, v0, v1, v2, vid1);
     bounce_forward(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b1);
     load_tri64(c, f2, v0, v1, v2, vid2);
     bounce_forward(b1.new_o, b1.wt, v0, v1, v2, c.ior_ext, c.ior_int, b2);
+}
+
+// Reverse a recomputed path, hand the six vertex gradients to `add(vertex_id, d3)`: face 2 first, then face 1.
+template <typename Add>
+DRT_HD void path_backward(const Bounce& b1, const Bounce& b2, const int32_t (&vid1)[3], const int32_t (&vid2)[3], d3 g_ori, d3 g_dir, Add add) {
     const d3 z{0.0, 0.0, 0.0};
     d3 ga = z, gb = z, gc = z, g_o, g_d;
     bounce_backward(b2, g_ori, g_dir, ga, gb, gc, g_o, g_d);
@@ -81,8 +83,17 @@ DRT_HD void path_recompute_backward(const PathCtx& c, d3 o, d3 d, int32_t f1, in
     add(vid1[0], ga); add(vid1[1], gb); add(vid1[2], gc);
 }
 
+// The two together: what a kernel with nothing to do between the halves calls.
+template <typename Add>
+DRT_HD void path_recompute_backward(const PathCtx& c, d3 o, d3 d, int32_t f1, int32_t f2, d3 g_ori, d3 g_dir, Add add) {
+    int32_t vid1[3], vid2[3];
+    Bounce b1, b2;
+    path_recompute(c, o, d, f1, f2, b1, b2, vid1, vid2);
+    path_backward(b1, b2, vid1, vid2, g_ori, g_dir, add);
+}
+
 // Adjoint of a recomputed path (b1, b2 on the faces vid1, vid2) w.r.t. the vertices -- the same gradients, in the same order, as
-// path_recompute_backward -- AND the camera ray (g_o0, g_d0; set) and the two indices of refraction (g_int, g_ext; set).
+// path_backward -- AND the camera ray (g_o0, g_d0; set) and the two indices of refraction (g_int, g_ext; set).
 template <typename Add>
 DRT_HD void path_backward_inputs(const PathCtx& c, const Bounce& b1, const Bounce& b2, const int32_t (&vid1)[3], const int32_t (&vid2)[3],
                                  d3 g_ori, d3 g_dir, Add add, d3& g_o0, d3& g_d0, double& g_int, double& g_ext) {
@@ -103,13 +114,9 @@ DRT_HD void path_backward_inputs(const PathCtx& c, const Bounce& b1, const Bounc
 template <typename Add>
 DRT_HD void path_recompute_backward_inputs(const PathCtx& c, d3 o, d3 d, int32_t f1, int32_t f2, d3 g_ori, d3 g_dir, Add add,
                                            d3& g_o0, d3& g_d0, double& g_int, double& g_ext) {
-    d3 v0, v1, v2;
     int32_t vid1[3], vid2[3];
     Bounce b1, b2;
-    load_tri64(c, f1, v0, v1, v2, vid1);
-    bounce_forward(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b1);
-    load_tri64(c, f2, v0, v1, v2, vid2);
-    bounce_forward(b1.new_o, b1.wt, v0, v1, v2, c.ior_ext, c.ior_int, b2);
+    path_recompute(c, o, d, f1, f2, b1, b2, vid1, vid2);
     path_backward_inputs(c, b1, b2, vid1, vid2, g_ori, g_dir, add, g_o0, g_d0, g_int, g_ext);
 }
 

@@ -163,24 +163,16 @@ __global__ void __launch_bounds__(256) k_paths_bwd(PathCtx c, const double* __re
                                                    int max_bounces, const int32_t* __restrict__ tape, const uint8_t* __restrict__ hits,
                                                    const double* __restrict__ g_out_ori, const double* __restrict__ g_out_dir, double* grad_verts,
                                                    const int32_t* __restrict__ list, const int64_t* __restrict__ n_list) {
-    __shared__ int32_t hkeys[kHashSize];
-    __shared__ double hsums[3 * kHashSize];
     int64_t n = *n_list;
     if (n > n_rays) n = n_rays;
-    const PathSink<DET> add{hkeys, hsums, grad_verts};
-    for (int64_t base = blockIdx.x * (int64_t)kPathsBwdBatch; base < n; base += (int64_t)gridDim.x * kPathsBwdBatch) {
-        add.clear();
-        const int64_t end = base + kPathsBwdBatch < n ? base + kPathsBwdBatch : n;
-        for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
-            const int64_t i = list[k];
-            if (i < 0 || i >= n_rays) continue;
-            const d3 z{0.0, 0.0, 0.0};
-            const d3 g_ori = g_out_ori ? load_d3(g_out_ori, i) : z;
-            const d3 g_dir = g_out_dir ? load_d3(g_out_dir, i) : z;
-            path_recompute_backward_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces), g_ori, g_dir, add);
-        }
-        add.flush();
-    }
+    sink_pass<DET, kPathsBwdBatch>(n, grad_verts, [&](int64_t k, const PathSink<DET>& add) {
+        const int64_t i = list[k];
+        if (i < 0 || i >= n_rays) return;
+        const d3 z{0.0, 0.0, 0.0};
+        const d3 g_ori = g_out_ori ? load_d3(g_out_ori, i) : z;
+        const d3 g_dir = g_out_dir ? load_d3(g_out_dir, i) : z;
+        path_recompute_backward_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces), g_ori, g_dir, add);
+    });
 }
 
 // The one-pass form: the rays whose path completed (state byte) -> index list; order does not matter to the sums.
@@ -208,25 +200,17 @@ __global__ void __launch_bounds__(256) k_paths_loss_bwd(PathCtx c, const double*
                                                         const int32_t* __restrict__ tape, const uint8_t* __restrict__ hits,
                                                         const int32_t* __restrict__ list, const unsigned* __restrict__ n_list, double* loss,
                                                         double* grad_verts, unsigned long long* n_valid) {
-    __shared__ int32_t hkeys[kHashSize];
-    __shared__ double hsums[3 * kHashSize];
     int64_t n = *n_list;
     if (n > n_rays) n = n_rays;
-    const PathSink<DET> add{hkeys, hsums, grad_verts};
     LossAcc<DET> acc;
     unsigned cnt = 0;
-    for (int64_t base = blockIdx.x * (int64_t)kPathsBwdBatch; base < n; base += (int64_t)gridDim.x * kPathsBwdBatch) {
-        add.clear();
-        const int64_t end = base + kPathsBwdBatch < n ? base + kPathsBwdBatch : n;
-        for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
-            const int64_t i = list[k];
-            if (i < 0 || i >= n_rays) continue;
-            acc.add(path_loss_backward_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
-                                         load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), add));
-            ++cnt;
-        }
-        add.flush();
-    }
+    sink_pass<DET, kPathsBwdBatch>(n, grad_verts, [&](int64_t k, const PathSink<DET>& add) {
+        const int64_t i = list[k];
+        if (i < 0 || i >= n_rays) return;
+        acc.add(path_loss_backward_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
+                                     load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), add));
+        ++cnt;
+    });
     acc.flush(loss);
     if (n_valid && cnt) atomicAdd(n_valid, (unsigned long long)cnt);
 }
@@ -246,38 +230,18 @@ __global__ void __launch_bounds__(256) k_paths_loss_bwd_ior(PathCtx c, const dou
     if (n > n_rays) n = n_rays;
     LossAcc<DET> acc, acc_int, acc_ext;
     unsigned cnt = 0;
-    if constexpr (VERTS) {
-        __shared__ int32_t hkeys[kHashSize];
-        __shared__ double hsums[3 * kHashSize];
-        const PathSink<DET> add{hkeys, hsums, grad_verts};
-        for (int64_t base = blockIdx.x * (int64_t)kPathsBwdBatch; base < n; base += (int64_t)gridDim.x * kPathsBwdBatch) {
-            add.clear();
-            const int64_t end = base + kPathsBwdBatch < n ? base + kPathsBwdBatch : n;
-            for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
-                const int64_t i = list[k];
-                if (i < 0 || i >= n_rays) continue;
-                double gi, ge;
-                acc.add(path_loss_backward_ior_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
-                                                        load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), add, gi, ge));
-                acc_int.add(gi); acc_ext.add(ge);
-                ++cnt;
-            }
-            add.flush();
-        }
-    } else {
-        for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t i = list[k];
-            if (i < 0 || i >= n_rays) continue;
-            double gi, ge;
-            acc.add(path_loss_backward_ior_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
-                                                    load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), DiscardAdd3{}, gi, ge));
-            acc_int.add(gi); acc_ext.add(ge);
-            ++cnt;
-        }
-    }
+    sink_pass<DET, kPathsBwdBatch, VERTS>(n, grad_verts, [&](int64_t k, auto add) {
+        const int64_t i = list[k];
+        if (i < 0 || i >= n_rays) return;
+        double gi, ge;
+        acc.add(path_loss_backward_ior_k<SNELL>(c, load_d3(origin, i), load_d3(dir, i), tape + i, n_rays, min((int)hits[i], max_bounces),
+                                                load_d3(park_ori, i), load_d3(park_dir, i), load_d3(screen_pixel, i), add, gi, ge));
+        acc_int.add(gi); acc_ext.add(ge);
+        ++cnt;
+    });
     acc.flush(loss);
-    acc_int.flush(paths_ior_slot<DET>(grad_ior, 0));
-    acc_ext.flush(paths_ior_slot<DET>(grad_ior, 1));
+    acc_int.flush(ior_slot<DET>(grad_ior, 0));
+    acc_ext.flush(ior_slot<DET>(grad_ior, 1));
     if (n_valid && cnt) atomicAdd(n_valid, (unsigned long long)cnt);
 }
 

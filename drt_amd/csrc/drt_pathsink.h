@@ -1,6 +1,7 @@
 // drt_pathsink.h -- what the path kernels of more than one translation unit share (drt_pipeline.hip: the two-bounce pipeline;
 // drt_paths.hip: paths of up to K interactions; drt_image.hip / drt_image_loss.hip: the refracted image and its loss): the compact
-// ray list, the staged list append, the LDS hash sink of the vertex gradients and the small pieces of the K-interaction backward kernels.
+// ray list, the staged list append, the LDS hash sink of the vertex gradients, the small pieces of the K-interaction backward kernels and
+// the pass of every gradient kernel over its list through that sink (sink_pass).
 #pragma once
 #include "drt_device.h"
 
@@ -204,6 +205,27 @@ struct DiscardAdd3 {
 };
 // Element k of an IOR-gradient target in the two accumulation modes: float64, or, deterministic, an FxCell.
 template <bool DET>
-__device__ __forceinline__ double* paths_ior_slot(double* ior, int k) {
+__device__ __forceinline__ double* ior_slot(double* ior, int k) {
     return DET ? reinterpret_cast<double*>(reinterpret_cast<FxCell*>(ior) + k) : ior + k;
+}
+
+// One pass of a gradient kernel over its list of n items (whole grid, whole blocks), body(k, add) per item k; the index type is n's.
+// VERTS: the LDS table and its PathSink live here.  Block b takes the BATCH-sized batches b, b + gridDim.x, ...; thread t of a batch its
+// items base + t, base + t + blockDim.x, ...; clear() before and flush() after every batch.  Without: no table, a grid-stride loop, and
+// the body gets a DiscardAdd3 -- so a body written once, as a generic lambda, serves both.
+template <bool DET, int BATCH, bool VERTS = true, typename Index, typename Body>
+__device__ __forceinline__ void sink_pass(Index n, double* grad_verts, Body body) {
+    if constexpr (VERTS) {
+        __shared__ int32_t hkeys[kHashSize];
+        __shared__ double hsums[3 * kHashSize];
+        const PathSink<DET> add{hkeys, hsums, grad_verts};
+        for (Index base = blockIdx.x * (Index)BATCH; base < n; base += (Index)gridDim.x * BATCH) {
+            add.clear();
+            const Index end = base + BATCH < n ? base + BATCH : n;
+            for (Index k = base + threadIdx.x; k < end; k += blockDim.x) body(k, add);
+            add.flush();
+        }
+    } else {
+        for (Index k = blockIdx.x * (Index)blockDim.x + threadIdx.x; k < n; k += (Index)gridDim.x * blockDim.x) body(k, DiscardAdd3{});
+    }
 }

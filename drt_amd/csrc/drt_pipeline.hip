@@ -868,10 +868,6 @@ struct InputGrads {
     double* dir;
     double* ior;
 };
-template <bool DET>
-__device__ __forceinline__ double* ior_slot(double* ior, int k) {
-    return DET ? reinterpret_cast<double*>(reinterpret_cast<FxCell*>(ior) + k) : ior + k;
-}
 // What one thread of a path backward adds to InputGrads: the rows at once, the IOR partials at the end of the kernel (whole waves).
 template <bool DET>
 struct InputAcc {
@@ -893,30 +889,22 @@ __global__ void __launch_bounds__(256) k_render_bwd(PathCtx c, const double* __r
                                                     const double* __restrict__ g_out_ori, const double* __restrict__ g_out_dir,
                                                     double* grad_verts, const int32_t* __restrict__ list, const unsigned* __restrict__ n_u32,
                                                     const int64_t* __restrict__ n_i64, InputGrads in) {
-    __shared__ int32_t hkeys[kHashSize];
-    __shared__ double hsums[3 * kHashSize];
     const int64_t n = n_i64 ? *n_i64 : (int64_t)*n_u32;
-    const PathSink<DET> add{hkeys, hsums, grad_verts};
     InputAcc<DET> inp;
-    for (int64_t base = blockIdx.x * (int64_t)kBwdBatch; base < n; base += (int64_t)gridDim.x * kBwdBatch) {
-        add.clear();
-        const int64_t end = base + kBwdBatch < n ? base + kBwdBatch : n;
-        for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
-            const int64_t i = list[k];
-            const d3 z{0.0, 0.0, 0.0};
-            const d3 g_ori = g_out_ori ? load_d3(g_out_ori, i) : z;
-            const d3 g_dir = g_out_dir ? load_d3(g_out_dir, i) : z;
-            if constexpr (INPUTS) {
-                d3 g_o0, g_d0;
-                double gi, ge;
-                path_recompute_backward_inputs(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], g_ori, g_dir, add, g_o0, g_d0, gi, ge);
-                inp.add(in, i, g_o0, g_d0, gi, ge);
-            } else {
-                path_recompute_backward(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], g_ori, g_dir, add);
-            }
+    sink_pass<DET, kBwdBatch>(n, grad_verts, [&](int64_t k, const PathSink<DET>& add) {
+        const int64_t i = list[k];
+        const d3 z{0.0, 0.0, 0.0};
+        const d3 g_ori = g_out_ori ? load_d3(g_out_ori, i) : z;
+        const d3 g_dir = g_out_dir ? load_d3(g_out_dir, i) : z;
+        if constexpr (INPUTS) {
+            d3 g_o0, g_d0;
+            double gi, ge;
+            path_recompute_backward_inputs(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], g_ori, g_dir, add, g_o0, g_d0, gi, ge);
+            inp.add(in, i, g_o0, g_d0, gi, ge);
+        } else {
+            path_recompute_backward(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], g_ori, g_dir, add);
         }
-        add.flush();
-    }
+    });
     if constexpr (INPUTS) inp.flush(in);
 }
 
@@ -1057,40 +1045,20 @@ __global__ void __launch_bounds__(256) k_loss_bwd_fused(PathCtx c, const double*
                                                         const double* __restrict__ screen_pixel, const int32_t* __restrict__ face1,
                                                         const int32_t* __restrict__ face2, Pipe p, double* loss, double* grad_verts,
                                                         unsigned long long* n_valid) {
-    __shared__ int32_t hkeys[kHashSize];
-    __shared__ double hsums[3 * kHashSize];
     const unsigned n2 = p.count[2];
-    const PathSink<DET> add{hkeys, hsums, grad_verts};
     LossAcc<DET> acc;
     unsigned cnt = 0;
-    for (unsigned base = blockIdx.x * kBwdBatch; base < n2; base += gridDim.x * kBwdBatch) {
-        add.clear();
-        const unsigned end = base + kBwdBatch < n2 ? base + kBwdBatch : n2;
-        for (unsigned k = base + threadIdx.x; k < end; k += blockDim.x) {
-            if (p.r2.face[k] >= 0) continue;   // occluded exit ray
-            const int64_t i = p.r2.idx[k];
-            const int32_t f2 = face2[i];
-            const d3 o = load_d3(origin, i), d = load_d3(dir, i);
-            d3 v0, v1, v2;
-            int32_t vid1[3], vid2[3];
-            Bounce b1, b2;
-            load_tri64(c, face1[i], v0, v1, v2, vid1);
-            bounce_forward(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b1);
-            load_tri64(c, f2, v0, v1, v2, vid2);
-            bounce_forward(b1.new_o, b1.wt, v0, v1, v2, c.ior_ext, c.ior_int, b2);
-            d3 g_dir;
-            acc.add(ray_loss_term(b2.new_o, b2.wt, load_d3(screen_pixel, i), g_dir));
-            ++cnt;
-            const d3 z{0.0, 0.0, 0.0};
-            d3 ga = z, gb = z, gc = z, g_o, g_d, g_o0, g_d0;
-            bounce_backward(b2, z, g_dir, ga, gb, gc, g_o, g_d);
-            add(vid2[0], ga); add(vid2[1], gb); add(vid2[2], gc);
-            ga = z; gb = z; gc = z;
-            bounce_backward(b1, g_o, g_d, ga, gb, gc, g_o0, g_d0);
-            add(vid1[0], ga); add(vid1[1], gb); add(vid1[2], gc);
-        }
-        add.flush();
-    }
+    sink_pass<DET, kBwdBatch>(n2, grad_verts, [&](unsigned k, const PathSink<DET>& add) {
+        if (p.r2.face[k] >= 0) return;   // occluded exit ray
+        const int64_t i = p.r2.idx[k];
+        int32_t vid1[3], vid2[3];
+        Bounce b1, b2;
+        path_recompute(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], b1, b2, vid1, vid2);
+        d3 g_dir;
+        acc.add(ray_loss_term(b2.new_o, b2.wt, load_d3(screen_pixel, i), g_dir));
+        ++cnt;
+        path_backward(b1, b2, vid1, vid2, d3{0.0, 0.0, 0.0}, g_dir, add);
+    });
     acc.flush(loss);
     if (n_valid && cnt) atomicAdd(n_valid, (unsigned long long)cnt);
 }
@@ -1105,44 +1073,27 @@ __global__ void __launch_bounds__(256) k_render_bwd_rows(PathCtx c, const double
                                                          const int32_t* __restrict__ face2, const int32_t* __restrict__ rows,
                                                          const unsigned* __restrict__ n_rows, const double* __restrict__ scale, double* grad_verts,
                                                          InputGrads in) {
-    __shared__ int32_t hkeys[kHashSize];
-    __shared__ double hsums[3 * kHashSize];
     const unsigned n = *n_rows;
     const double sc = *scale;
-    const PathSink<DET> add{hkeys, hsums, grad_verts};
     InputAcc<DET> inp;
-    for (unsigned base = blockIdx.x * kBwdBatch; base < n; base += gridDim.x * kBwdBatch) {
-        add.clear();
-        const unsigned end = base + kBwdBatch < n ? base + kBwdBatch : n;
-        for (unsigned k = base + threadIdx.x; k < end; k += blockDim.x) {
-            const int64_t i = rows[k];
-            d3 v0, v1, v2;
-            int32_t vid1[3], vid2[3];
-            Bounce b1, b2;
-            load_tri64(c, face1[i], v0, v1, v2, vid1);
-            bounce_forward(load_d3(origin, i), load_d3(dir, i), v0, v1, v2, c.ior_ext, c.ior_int, b1);
-            load_tri64(c, face2[i], v0, v1, v2, vid2);
-            bounce_forward(b1.new_o, b1.wt, v0, v1, v2, c.ior_ext, c.ior_int, b2);
-            d3 g_dir;
-            (void)ray_loss_term(b2.new_o, b2.wt, load_d3(screen_pixel, i), g_dir);
-            g_dir = sc * g_dir;
-            const d3 z{0.0, 0.0, 0.0};
-            if constexpr (INPUTS) {
-                d3 g_o0, g_d0;
-                double gi, ge;
-                path_backward_inputs(c, b1, b2, vid1, vid2, z, g_dir, add, g_o0, g_d0, gi, ge);
-                inp.add(in, i, g_o0, g_d0, gi, ge);
-                continue;
-            }
-            d3 ga = z, gb = z, gc = z, g_o, g_d, g_o0, g_d0;
-            bounce_backward(b2, z, g_dir, ga, gb, gc, g_o, g_d);
-            add(vid2[0], ga); add(vid2[1], gb); add(vid2[2], gc);
-            ga = z; gb = z; gc = z;
-            bounce_backward(b1, g_o, g_d, ga, gb, gc, g_o0, g_d0);
-            add(vid1[0], ga); add(vid1[1], gb); add(vid1[2], gc);
+    sink_pass<DET, kBwdBatch>(n, grad_verts, [&](unsigned k, const PathSink<DET>& add) {
+        const int64_t i = rows[k];
+        int32_t vid1[3], vid2[3];
+        Bounce b1, b2;
+        path_recompute(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], b1, b2, vid1, vid2);
+        d3 g_dir;
+        (void)ray_loss_term(b2.new_o, b2.wt, load_d3(screen_pixel, i), g_dir);
+        g_dir = sc * g_dir;
+        const d3 z{0.0, 0.0, 0.0};
+        if constexpr (INPUTS) {
+            d3 g_o0, g_d0;
+            double gi, ge;
+            path_backward_inputs(c, b1, b2, vid1, vid2, z, g_dir, add, g_o0, g_d0, gi, ge);
+            inp.add(in, i, g_o0, g_d0, gi, ge);
+        } else {
+            path_backward(b1, b2, vid1, vid2, z, g_dir, add);
         }
-        add.flush();
-    }
+    });
     if constexpr (INPUTS) inp.flush(in);
 }
 
@@ -1158,39 +1109,21 @@ __global__ void __launch_bounds__(256) k_loss_bwd_listed(PathCtx c, const double
                                                          const int32_t* __restrict__ paths, const int64_t* __restrict__ n_paths,
                                                          const unsigned* __restrict__ first_ptr, const unsigned* __restrict__ n32_ptr,
                                                          double* loss, double* grad_verts) {
-    __shared__ int32_t hkeys[kHashSize];
-    __shared__ double hsums[3 * kHashSize];
     // the listed range: [*first_ptr (0 without one), *n32_ptr or *n_paths)
     const int64_t first = first_ptr ? (int64_t)*first_ptr : 0;
     paths += first;
     const int64_t n = (n32_ptr ? (int64_t)*n32_ptr : *n_paths) - first;
-    const PathSink<DET> add{hkeys, hsums, grad_verts};
     LossAcc<DET> acc;
-    for (int64_t base = blockIdx.x * (int64_t)kBwdBatch; base < n; base += (int64_t)gridDim.x * kBwdBatch) {
-        add.clear();
-        const int64_t end = base + kBwdBatch < n ? base + kBwdBatch : n;
-        for (int64_t k = base + threadIdx.x; k < end; k += blockDim.x) {
-            const int64_t i = paths[k];
-            if (!valid[i]) continue;
-            d3 v0, v1, v2;
-            int32_t vid1[3], vid2[3];
-            Bounce b1, b2;
-            load_tri64(c, face1[i], v0, v1, v2, vid1);
-            bounce_forward(load_d3(origin, i), load_d3(dir, i), v0, v1, v2, c.ior_ext, c.ior_int, b1);
-            load_tri64(c, face2[i], v0, v1, v2, vid2);
-            bounce_forward(b1.new_o, b1.wt, v0, v1, v2, c.ior_ext, c.ior_int, b2);
-            d3 g_dir;
-            acc.add(ray_loss_term(b2.new_o, b2.wt, load_d3(screen_pixel, i), g_dir));
-            const d3 z{0.0, 0.0, 0.0};
-            d3 ga = z, gb = z, gc = z, g_o, g_d, g_o0, g_d0;
-            bounce_backward(b2, z, g_dir, ga, gb, gc, g_o, g_d);
-            add(vid2[0], ga); add(vid2[1], gb); add(vid2[2], gc);
-            ga = z; gb = z; gc = z;
-            bounce_backward(b1, g_o, g_d, ga, gb, gc, g_o0, g_d0);
-            add(vid1[0], ga); add(vid1[1], gb); add(vid1[2], gc);
-        }
-        add.flush();
-    }
+    sink_pass<DET, kBwdBatch>(n, grad_verts, [&](int64_t k, const PathSink<DET>& add) {
+        const int64_t i = paths[k];
+        if (!valid[i]) return;
+        int32_t vid1[3], vid2[3];
+        Bounce b1, b2;
+        path_recompute(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], b1, b2, vid1, vid2);
+        d3 g_dir;
+        acc.add(ray_loss_term(b2.new_o, b2.wt, load_d3(screen_pixel, i), g_dir));
+        path_backward(b1, b2, vid1, vid2, d3{0.0, 0.0, 0.0}, g_dir, add);
+    });
     acc.flush(loss);
 }
 
