@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(256) k_fx_from_limbs(const int64_t* __restrict
 extern "C" {
 
 const char* drt_last_error(void) { return g_err; }
-int drt_version(void) { return 9; }
+int drt_version(void) { return 10; }
 
 int drt_deterministic(int on) {
     const int was = det_mode() ? 1 : 0;
@@ -277,6 +277,13 @@ int drt_profile_read(drt_scene_t* s, double* ms_out, int64_t* launches_out, int6
     for (int k = 0; k < 12; ++k) s->trace_stats[k] = (int64_t)h[kProfStages + k];
     HIP_TRY(hipMemset(s->prof_counts, 0, sizeof(h)));
     s->prof_used = 0;
+    return DRT_OK;
+}
+
+int drt_route_counts(drt_scene_t* s, int64_t* out8) {
+    CHECK_SCENE(s);
+    if (!out8) return fail(DRT_E_INVALID, "null pointer argument");
+    for (int k = 0; k < 8; ++k) out8[k] = s->route_counts[k];
     return DRT_OK;
 }
 

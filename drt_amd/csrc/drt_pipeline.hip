@@ -1326,6 +1326,17 @@ static int launch_chunk(drt_scene* s, drt_scene::Sub& w, hipStream_t st, const P
     const bool park = !FUSED && !mega && rz.views && grid_mode == DRT_GRID_TRUST && pre_ori && pre_dir && pre_mask && s->cull_park;      // (with or without `direct`: k_shade1 parks too)
     const Ray64 r64p = park ? Ray64{out_ori, out_dir} : r64;      // (k_shade1 and k_gen_late, which serve the untrusted images, park likewise)
     if (park) HIP_TRY(hipStreamWaitEvent(st, s->prefill_done, 0));
+    {   // which route this sub-batch takes (drt_route_counts)
+        int64_t* rc = s->route_counts;
+        rc[kRouteTotal] += 1;
+        rc[kRouteRaster] += rz.views != nullptr;
+        rc[kRouteTrust] += rz.views && grid_mode == DRT_GRID_TRUST;
+        rc[kRouteDirect] += direct;
+        rc[kRoutePark] += park;
+        rc[kRouteLateFill] += late_fill;
+        rc[kRouteTreeLate] += tree_late;
+        rc[kRouteMega] += mega;
+    }
     { StageTimer t(s, st, kStageCull);
       const unsigned n_patches = (unsigned)((n + kPathBlock - 1) / kPathBlock);
       if (rz.views && grid_mode == DRT_GRID_TRUST) {

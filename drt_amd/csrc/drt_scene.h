@@ -61,6 +61,8 @@ constexpr int64_t kChunkRays = 1 << 26; // max rays per pipeline pass; bounds th
 
 constexpr int kSortBlock = 256, kSortItems = 8, kSortTile = kSortBlock * kSortItems, kRadix = 256;
 
+// entries of drt_route_counts
+enum { kRouteTotal = 0, kRouteRaster, kRouteTrust, kRouteDirect, kRoutePark, kRouteLateFill, kRouteTreeLate, kRouteMega };
 // stage ids of drt_profile_read
 enum { kStageBuild = 0, kStageCull, kStageTrace1, kStageShade1, kStageTrace2, kStageShade2, kStageTrace3, kStageFinish, kStageCollect, kStageBackward, kStageLossBwdFused, kStageRaster, kStageFill, kStagePath, kProfStages };
 static_assert(kProfStages == DRT_PROFILE_STAGES, "include/drt_hip.h");
@@ -99,6 +101,9 @@ struct drt_scene {
     bool cull_direct = true;       // DRT_CULL_DIRECT=0: bounce #1 as a pass of its own (k_shade1) over list R0, as before round 4
     bool cull_park = true;         // DRT_CULL_PARK=0: k_shade2 recomputes bounce #1 instead of reading the parked refracted ray
     int64_t cull_direct_min_rays = (int64_t)1 << 25;   // sub-batches below this keep the separate pass (DRT_CULL_DIRECT_MIN_LOG2)
+    // drt_route_counts: sub-batches launch_chunk has enqueued since drt_create, and how many of them took each route (host counters, in the
+    // order of the kRoute* ids; a test reads them to know which kernels its call ran)
+    int64_t route_counts[8] = {0};
     int tree_mode = 0, rebuild_every = 1, since_full = 0;
     bool topology_fixed = false;   // mode 2: the host's topology is installed for the current faces
     uint32_t* bounds_acc = nullptr;  // [6] scene-box accumulators of drt_update_vert_f64's cast kernel (order-preserving uint encodings; put back to +-inf by the build that read them)

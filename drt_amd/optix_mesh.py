@@ -220,6 +220,15 @@ class optix_mesh:
             _lib.check(_lib.lib().drt_profile_read(self._h, ms, launches, items))
         return {k: (ms[i], launches[i], items[i]) for i, k in enumerate(self.STAGES)}
 
+    ROUTES = ("total", "raster", "trust", "direct", "park", "late_fill", "tree_late", "mega")
+
+    def route_counts(self):
+        """{route: sub-batches of the render calls that took it since the scene was created} (include/drt_hip.h: drt_route_counts);
+        host counters, no synchronisation."""
+        out = (ctypes.c_int64 * len(self.ROUTES))()
+        _lib.check(_lib.lib().drt_route_counts(self._h, out))
+        return dict(zip(self.ROUTES, out))
+
     def trace_stats(self):
         """Per k_trace stage: (wave_steps, lane_steps, refills, max_wave_steps) of the last profile_read interval."""
         out = (ctypes.c_int64 * 12)()

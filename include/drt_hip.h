@@ -34,7 +34,8 @@ typedef struct drt_scene drt_scene_t;
 const char* drt_last_error(void);
 int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
                             * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused;
-                            * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image; 9: drt_render_image_loss */
+                            * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image; 9: drt_render_image_loss;
+                            * 10: drt_route_counts */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -715,6 +716,14 @@ int drt_profile_read(drt_scene_t* s, double* ms_out, int64_t* launches_out, int6
  * lane-steps / (64 * wave-steps) = SIMD lane utilisation), the wave-steps that were leaf (triangle) visits
  * (the others are inner-node visits), longest wavefront. */
 int drt_profile_trace_stats(drt_scene_t* s, int64_t* out12);
+/* Which route the sub-batches of drt_render_forward / drt_render_ray_loss_fused took: host-side counts since drt_create (no device work,
+ * no synchronisation).  out8 = { sub-batches enqueued, of these: with the projected primary visibility (whole images of a multiple-of-64
+ * width), as a DRT_GRID_TRUST call of it (k_patch_list + k_cull_listed), with bounce #1 inside the cull of the listed patches
+ * (DRT_CULL_DIRECT, sub-batches of at least 2^DRT_CULL_DIRECT_MIN_LOG2 rays), with the refracted float64 rays parked in the rows of the
+ * dense outputs (DRT_CULL_PARK), with the dense-output fills issued behind the cull stage (DRT_FILL_OVERLAP), with the wait for the tree
+ * moved behind the first shading (DRT_GRID_ALL_VERIFIED), with the one-kernel back half (DRT_MEGA_MAX_LOG2) }.  The K-interaction and
+ * image entry points are not counted. */
+int drt_route_counts(drt_scene_t* s, int64_t* out8);
 
 /* Debug builds (hipcc -DDRT_CHECK=1): the persistent traversal kernels assert the invariants of their bound-check-free LDS stack
  * (csrc/drt_traverse.h FastStack) and count violations on the device.  out4 = {stores above a lane's rows, pops of an empty stack,

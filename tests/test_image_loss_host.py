@@ -8,6 +8,7 @@ ten times that, LOSS_REL, which is far below the 1e-10 the figure may never exce
 the largest entry of the reference and 1e-5 absolute, for the vertex gradient and the two IOR partials."""
 import ctypes
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -236,6 +237,7 @@ def test_entry_point_is_declared_everywhere():
     header = open(os.path.join(ROOT, "include", "drt_hip.h")).read()
     assert "int drt_render_image_loss(" in header
     api = open(os.path.join(ROOT, "drt_amd", "csrc", "drt_api.hip")).read()
-    assert "int drt_version(void) { return 9; }" in api
+    version = re.search(r"int drt_version\(void\) \{ return (\d+); \}", api)
+    assert version and int(version.group(1)) >= 9
     from drt_amd import diffrender
     assert callable(diffrender.Scene.image_loss_fused)
