@@ -7,6 +7,10 @@ the capture's targets is smallest, under any K-interaction law -- Snell's includ
 ``Scene.paths_ray_loss_ior_fused(..., vertices=False)`` summed over the refraction views.  The loss as a function of the IOR is only
 piecewise smooth (paths change face and validity), so a fixed-step optimiser rings around the minimum; the SIGN of the summed
 derivative is right well away from it, and the fit bisects a bracket on that sign.
+
+``fit_screen`` fits the POSE of the textured screen behind the object -- placed by hand, calibrated separately -- to plain photographs:
+a rigid motion of the initial screen under the photometric loss of ``Scene.image_loss_fused(..., screen_param=)``,
+mesh and IORs fixed.  It has no command line.
 """
 from __future__ import annotations
 
@@ -74,6 +78,80 @@ def fit_ior(scene, data, path_law=(2, "drop", "snell"), bracket=(1.2, 1.8), halv
         else:
             hi = mid
     return {"ior": 0.5 * (lo + hi), "bracket": (lo, hi), "evaluations": len(history), "history": history}
+
+
+def screen_pose(screen, tex_h, tex_w, six):
+    """float64 [3, 3], rows p0, eu, ev: ``screen`` (a ``render.Screen`` under a texture of ``tex_h`` x ``tex_w`` texels) moved rigidly by
+    the six numbers ``six`` (a float64 tensor; differentiable): rotated about its centre by the rotation vector ``six[3:] / h`` and then
+    translated by ``pitch * six[:3]``, with pitch = |eu| and h = the half diagonal of the screen in texels -- so that one unit of any of
+    the six moves a corner of the screen by about one texel.  The pitch is untouched and the axes stay orthogonal: both are rotated by
+    the same orthogonal matrix (the matrix exponential of the rotation vector's cross-product matrix)."""
+    p0, eu, ev = (torch.as_tensor(a, dtype=torch.float64) for a in (screen.p0, screen.eu, screen.ev))
+    half_u, half_v = (tex_w - 1) / 2.0, (tex_h - 1) / 2.0
+    centre = p0 + eu * half_u + ev * half_v
+    w = six[3:] / float((half_u * half_u + half_v * half_v) ** 0.5)
+    zero = torch.zeros((), dtype=torch.float64)
+    K = torch.stack([torch.stack([zero, -w[2], w[1]]), torch.stack([w[2], zero, -w[0]]), torch.stack([-w[1], w[0], zero])])
+    R = torch.linalg.matrix_exp(K)
+    shift = six[:3] * float(torch.linalg.norm(eu))
+    return torch.stack([centre + R @ (p0 - centre) + shift, R @ eu, R @ ev])
+
+
+def fit_pose(loss_of, screen, tex_h, tex_w, steps, lr):
+    """The optimiser of ``fit_screen`` over any ``loss_of(rows)`` (rows: ``screen_pose``'s tensor, which requires grad; returns a scalar
+    tensor): Adam with step ``lr`` (in texels, see ``screen_pose``) on the six numbers from zero.  Returns (the six numbers of the smallest
+    loss seen, the loss history: one float per step, evaluated BEFORE that step's update)."""
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError(f"steps must be a positive integer, got {steps!r}")
+    if not (float(lr) > 0.0):
+        raise ValueError(f"lr must be positive, got {lr!r}")
+    six = torch.zeros(6, dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.Adam([six], lr=float(lr))
+    history, best = [], (None, None)
+    for _ in range(int(steps)):
+        opt.zero_grad()
+        loss = loss_of(screen_pose(screen, tex_h, tex_w, six))
+        value = float(loss.detach())
+        if best[0] is None or value < best[0]:
+            best = (value, six.detach().clone())
+        history.append(value)
+        loss.backward()
+        opt.step()
+    return best[1], history
+
+
+def fit_screen(scene, views, screen, texture, *, steps, lr, **law):
+    """The pose of the screen behind the fixed mesh of ``scene`` from photographs: a rigid motion of the initial ``screen`` (a
+    ``render.Screen``; ``screen_pose`` builds the pose from six numbers in torch) that minimises the photometric loss summed over
+    ``views`` = [(camera_M, photograph[, weight]), ...] -- ``Scene.image_loss_fused(camera_M, H, W, None, texture, photograph,
+    screen_param=pose, vertices=False, **law)`` with H, W the photograph's.  The kernel hands back the nine partials of the pose; the
+    chain from them to the six numbers is torch autograd.  ``steps`` Adam steps of ``lr`` texels.  ``law``: the law, IOR and band
+    keywords of ``image_loss_fused``.  Returns (the fitted ``Screen``: the pose of the smallest loss seen, the loss history)."""
+    from . import render
+    if not isinstance(screen, render.Screen):
+        raise ValueError(f"screen must be a drt_amd.render.Screen, got {type(screen).__name__}")
+    views = [tuple(v) for v in views]
+    if not views or any(len(v) not in (2, 3) for v in views):
+        raise ValueError("views must be a non-empty list of (camera_M, photograph) or (camera_M, photograph, weight)")
+    for bad in ("screen_param", "texture_param", "vertices", "want_image"):
+        if bad in law:
+            raise ValueError(f"fit_screen sets {bad} itself")
+    tex = render.check_texture(texture)
+    tex_h, tex_w = int(tex.shape[0]), int(tex.shape[1])
+
+    def loss_of(rows):
+        total = None
+        for v in views:
+            photo = v[1]
+            term = scene.image_loss_fused(v[0], int(photo.shape[0]), int(photo.shape[1]), None, tex, photo, weight=v[2] if len(v) == 3 else None,
+                                          vertices=False, screen_param=rows, **law)
+            term = term.to(rows.device)
+            total = term if total is None else total + term
+        return total
+
+    six, history = fit_pose(loss_of, screen, tex_h, tex_w, steps, lr)
+    rows = screen_pose(screen, tex_h, tex_w, six).numpy()
+    return render.Screen(rows[0], rows[1], rows[2]), history
 
 
 def main(argv=None):

@@ -11,6 +11,8 @@
 //   k_image_loss_bwd      that list   : image_sample_backward per sample: camera ray formed again (image_sample_ray), exit ray and T from
 //                                       the parked rows, g_c of pixel i / s^2; vertex gradients through PathSink in kPathsBwdBatch-sized
 //                                       fills, the IOR partials through two LossAcc; VERTS = false: no table in LDS
+//   k_image_screen_bwd    all pixels  : drt_render_image_loss_screen only (drt_image_screen.hip, through launch_image_screen_bwd): the screen-pose
+//                                       and texture gradients from the same seeds
 // Everything runs on the caller's stream, nothing is read back, every list size stays on the device.
 #include "drt_image_wave.h"
 #include "drt_image_loss.h"
@@ -98,13 +100,13 @@ __global__ void __launch_bounds__(256) k_image_loss_bwd(PathCtx c, ImageCam cam,
 namespace {
 
 // the pixel seeds [n_seed], grown like the throughputs they sit beside (drt_image.hip)
-int ensure_image_loss_ws(drt_scene* s, int64_t n_seed, hipStream_t st) {
+int ensure_image_loss_ws(drt_scene* s, int64_t n_seed, hipStream_t st, const char* who) {
     ImageLossWs* lw = static_cast<ImageLossWs*>(s->image_loss_ws);
     if (lw && n_seed <= lw->cap) return DRT_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(DRT_E_INVALID, "drt_render_image_loss: the first call of this size allocates its pixel seeds and cannot run "
-                                   "inside a stream capture: issue one such call eagerly before capturing");
+        return fail(DRT_E_INVALID, "%s: the first call of this size allocates its pixel seeds and cannot run "
+                                   "inside a stream capture: issue one such call eagerly before capturing", who);
     if (!lw) {
         lw = new (std::nothrow) ImageLossWs();
         if (!lw) return fail(DRT_E_NOMEM, "host allocation failed");
@@ -151,21 +153,25 @@ void image_loss_free(drt_scene* s) {
     s->image_loss_ws = nullptr;
 }
 
-extern "C" {
+namespace {
 
-int drt_render_image_loss(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
-                          double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
-                          const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
-                          const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
-                          int64_t* d_count, void* stream) {
+// The one host body of drt_render_image_loss and drt_render_image_loss_screen (`who`, for messages): the former hands no screen and no
+// texture accumulator and enqueues what it always has.
+int image_loss_call(drt_scene* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample, double ior_int,
+                    double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9, const float* d_texture, int tex_h, int tex_w,
+                    int channels, const double* fill_void, const double* fill_invalid, const float* d_target, const float* d_weight, double* d_loss,
+                    double* d_grad_verts, double* d_grad_ior, float* d_image, int64_t* d_count, double* d_grad_screen, double* d_grad_texture, void* stream,
+                    const char* who) {
     CHECK_BUILT(s);
     ImageCall c;
     { int rc = image_call_check(camera21, height, width, y0, y1, supersample, ior_int, ior_ext, max_bounces, law_flags, fresnel, screen9, d_texture, tex_h, tex_w,
                                 channels, fill_void, fill_invalid, d_texture && d_target && d_loss && (s->n_faces == 0 || d_verts),
                                 "null device pointer argument (d_verts, d_texture, d_target, d_loss)", c); if (rc) return rc; }
     hipStream_t st = (hipStream_t)stream;
-    { int rc = ensure_image_loss_ws(s, c.n_pix * channels, st); if (rc) return rc; }
-    { int rc = image_forward(s, d_verts, c, true, st, "drt_render_image_loss"); if (rc) return rc; }
+    if (d_grad_texture && (int64_t)tex_h * tex_w > INT32_MAX)
+        return fail(DRT_E_INVALID, "tex_h x tex_w = %d x %d: a texture gradient takes at most 2^31 - 1 texels", tex_h, tex_w);
+    { int rc = ensure_image_loss_ws(s, c.n_pix * channels, st, who); if (rc) return rc; }
+    { int rc = image_forward(s, d_verts, c, true, st, who); if (rc) return rc; }
     const PathsWs& w = *paths_ws_of(s);
     const ImageLossWs& lw = *static_cast<ImageLossWs*>(s->image_loss_ws);
     const PathCtx pc = image_path_ctx(s, d_verts, c);
@@ -185,7 +191,32 @@ int drt_render_image_loss(drt_scene_t* s, const double* d_verts, const double* c
                               w.hits, done, w.cnt + kCntValid, lw.g_c, d_grad_verts, d_grad_ior, reinterpret_cast<unsigned long long*>(d_count));
     }
     HIP_TRY(hipGetLastError());
+    if (d_grad_screen || d_grad_texture) return launch_image_screen_bwd(s, c, lw.g_c, d_grad_screen, d_grad_texture, st);
     return DRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int drt_render_image_loss(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                          double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                          const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                          const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                          int64_t* d_count, void* stream) {
+    return image_loss_call(s, d_verts, camera21, height, width, y0, y1, supersample, ior_int, ior_ext, max_bounces, law_flags, fresnel, screen9, d_texture, tex_h,
+                           tex_w, channels, fill_void, fill_invalid, d_target, d_weight, d_loss, d_grad_verts, d_grad_ior, d_image, d_count, nullptr, nullptr,
+                           stream, "drt_render_image_loss");
+}
+
+int drt_render_image_loss_screen(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                                 double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                                 const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                                 const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                                 int64_t* d_count, double* d_grad_screen, double* d_grad_texture, void* stream) {
+    return image_loss_call(s, d_verts, camera21, height, width, y0, y1, supersample, ior_int, ior_ext, max_bounces, law_flags, fresnel, screen9, d_texture, tex_h,
+                           tex_w, channels, fill_void, fill_invalid, d_target, d_weight, d_loss, d_grad_verts, d_grad_ior, d_image, d_count, d_grad_screen,
+                           d_grad_texture, stream, "drt_render_image_loss_screen");
 }
 
 }  // extern "C"

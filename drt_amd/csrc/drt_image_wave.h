@@ -46,6 +46,11 @@ int image_call_check(const double* camera21, int height, int width, int y0, int 
 // [K, n] -- without it the tape is left untouched.  `who`: the entry point, for messages.
 int image_forward(drt_scene* s, const double* d_verts, const ImageCall& call, bool keep_tape, hipStream_t st, const char* who);
 
+// Defined in drt_image_screen.hip: k_image_screen_bwd on `st` over the pixels of the band, behind image_forward and the resolve kernel
+// of the loss, whose pixel seeds g_c [n_pix, C] it reads.  d_grad_screen (nine accumulators: p0, eu, ev) and d_grad_texture
+// ([tex_h, tex_w, C] accumulators, padded to a multiple of three values) are accumulated into; one of them may be null.
+int launch_image_screen_bwd(const drt_scene* s, const ImageCall& call, const double* g_c, double* d_grad_screen, double* d_grad_texture, hipStream_t st);
+
 // The context image_forward traced with (the same for the adjoint of the loss).
 inline PathCtx image_path_ctx(const drt_scene* s, const double* d_verts, const ImageCall& call) {
     PathCtx pc = path_ctx(s, d_verts, call.ior_int, call.ior_ext);

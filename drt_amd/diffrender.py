@@ -890,6 +890,64 @@ class _ImageLossFused(torch.autograd.Function):
         return g_v, g_ior[0], g_ior[1], None, None, None, None, None, None, None
 
 
+class _ImageLossScreenFused(torch.autograd.Function):
+    """_ImageLossFused that also differentiates the screen's pose and the texture (drt_render_image_loss_screen):
+    ``screen_param`` / ``texture_param`` stand for the tensors autograd tracks (or None); ``a["screen"]`` and ``tex`` carry their values.
+    The nine screen partials and the texture gradient are computed here with a unit seed, band after band into one set of accumulators --
+    each allocated only when its input requires grad --; the backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, vertices, ior_int, ior_ext, screen_param, texture_param, scene, a, ior, tex, target, weight, out):
+        v = _f64c(vertices.detach(), "vertices")
+        dev = v.device
+        H, W, C = a["height"], a["width"], a["channels"]
+        loss = det.scalar(dev)
+        grad_v = det.acc(v) if a["vertices"] else None
+        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=dev))
+        n_tex = tex.numel()
+        like_s = torch.empty(9, dtype=torch.float64, device=dev)
+        like_t = torch.empty((n_tex + 2) // 3 * 3, dtype=torch.float64, device=dev)      # (a one-channel texture is scattered in threes)
+        grad_s = det.acc(like_s) if screen_param is not None and ctx.needs_input_grad[3] else None
+        grad_t = det.acc(like_t) if texture_param is not None and ctx.needs_input_grad[4] else None
+        count = torch.zeros((), dtype=torch.int64, device=dev)
+        image = torch.empty((H, W, C), dtype=torch.float32, device=dev) if a["want_image"] else None
+        with _on(dev):
+            for y0, y1 in a["bands"]:
+                _lib.check(_lib.lib().drt_render_image_loss_screen(
+                    scene.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
+                    a["law_flags"], a["fresnel"], a["screen"].ctypes.data, tex.data_ptr(), tex.shape[0], tex.shape[1], C, a["void"].ctypes.data,
+                    a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss.data_ptr(), _lib.ptr(grad_v), grad_ior.data_ptr(),
+                    _lib.ptr(image), count.data_ptr(), _lib.ptr(grad_s), _lib.ptr(grad_t), _stream()))
+        out["image"], out["count"] = image, count
+        ctx.ior_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
+        ctx.end_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (screen_param, texture_param))
+        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
+        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v), det.value(grad_ior, torch.empty(2, dtype=torch.float64)),
+                              None if grad_s is None else det.value(grad_s, like_s), None if grad_t is None else det.value(grad_t, like_t)[:n_tex])
+        return det.value(loss)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        grad_v, both, grad_s, grad_t = ctx.saved_tensors
+        g_ior, g_end = [None, None], [None, None]
+        for k in (0, 1):
+            if ctx.needs_input_grad[1 + k]:
+                shape, dtype, dev = ctx.ior_like[k]
+                g_ior[k] = (both[k] * g_loss).reshape(shape).to(dtype=dtype, device=dev)
+        for k, g in enumerate((grad_s, grad_t)):
+            if g is not None and ctx.needs_input_grad[3 + k]:
+                shape, dtype, dev = ctx.end_like[k]
+                g_end[k] = (g * g_loss).reshape(shape).to(dtype=dtype, device=dev)
+        if grad_v is None or not ctx.needs_input_grad[0]:
+            g_v = None
+        elif det.SINK is not None and ctx.wide is not None:
+            det.SINK.append((ctx.wide, g_loss))
+            g_v = None
+        else:
+            g_v = grad_v * g_loss
+        return g_v, g_ior[0], g_ior[1], g_end[0], g_end[1], None, None, None, None, None, None, None
+
+
 def ray_loss(out_ori, out_dir, mask, screen_pixel, valid):
     """sum over valid & mask rays of |out_dir - normalize(screen_pixel - out_ori.detach())|^2."""
     link = getattr(out_dir, "_drt_link", None) if SPARSE_LOSS_GRAD else None
@@ -1115,23 +1173,31 @@ class Scene(StepwiseMixin):
 
     def image_loss_fused(self, camera_M, height, width, screen, texture, target, *, weight=None, ior_int=None, ior_ext=None, vertices=True,
                          want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
-                         invalid=0.0, max_samples=1 << 22):
+                         invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None):
         """The photometric loss of ``render_image`` against a photograph: sum over pixels and channels of ``w (I - target)^2`` with ``I``
         the float64 pixel mean ``render_image`` rounds to float32 -- as a scalar, with its vertex gradient AND d loss / d (ior_int,
         ior_ext) computed alongside with a unit seed and scaled in the backward pass (drt_render_image_loss; csrc/drt_image_loss.h and
         DESIGN.md 10.3 state the law).  The gradient is the derivative of the whole law, Fresnel weights included, through the samples
         whose path completes and lands on the screen; a sample's class, its faces, the texel cell and the screen's border carry none,
-        and none reaches the texture, the screen or the camera.  ``target``: ``[height, width, C]`` (or ``[height, width]`` with a
+        and none reaches the camera; the screen's pose and the texture receive one through ``screen_param`` / ``texture_param`` (below).
+        ``target``: ``[height, width, C]`` (or ``[height, width]`` with a
         one-channel texture), float32, or uint8 read as value / 255; ``weight``: float32 ``[height, width]`` or None; numpy or device
         tensors.  ``ior_int`` / ``ior_ext``: None (this module's ``intIOR`` / ``extIOR``), floats, or 0-dim tensors (each is read to the
         host once per call, so such a call cannot be captured); the loss is differentiable w.r.t. whichever of them are tensors that
         require grad, and w.r.t. ``self.vertices`` unless ``vertices=False`` (a fixed mesh: no vertex gradient is computed, the kernel
         runs without its gradient table).  The law and band keywords are ``render_image``'s; the bands add into one set of
         accumulators.  ``want_image``: returns ``(loss, image)`` with ``render_image``'s bits.  Afterwards ``self.last_image_count`` is the
-        number of samples that carried a gradient (0-dim int64 tensor on the device)."""
+        number of through samples that carried a gradient (0-dim int64 tensor on the device).
+        ``screen_param``: a float64 tensor ``[3, 3]`` with rows p0, eu, ev on any device that supplies the screen INSTEAD of ``screen``
+        (which must then be None); its value is read to the host once per call, like a tensor IOR, and goes through ``Screen``'s checks;
+        the loss is differentiable w.r.t. it when it requires grad.  ``texture_param``: a float32 or float64 tensor ``[Th, Tw, C]`` (or
+        ``[Th, Tw]``) that supplies the texture instead of ``texture`` (then None); its gradient comes back in its own dtype, device and
+        shape.  For these two the DIRECT samples carry a gradient as well (drt_render_image_loss_screen; csrc/drt_image_screen.h and
+        DESIGN.md 10.4 state the law); the vertex and IOR gradients are the same with and without them.  Without either keyword the call
+        is what it was."""
         from . import render as _render
         a = _render.check_image_loss_args(camera_M, height, width, screen, texture, target, weight, ior_int, ior_ext, vertices, want_image, supersample,
-                                          max_bounces, tir, refraction, fresnel, void, invalid, max_samples)
+                                          max_bounces, tir, refraction, fresnel, void, invalid, max_samples, screen_param, texture_param)
         given = [intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext]
         ior = tuple(_ior_host(x, name) for x, name in zip(given, ("ior_int", "ior_ext")))
         tracked = tuple(x if isinstance(x, torch.Tensor) else None for x in given)
@@ -1142,7 +1208,11 @@ class Scene(StepwiseMixin):
             tgt = (tgt.to(torch.float32) / 255.0 if tgt.dtype == torch.uint8 else tgt).reshape(a["height"], a["width"], a["channels"]).contiguous()
             wgt = None if a["weight"] is None else torch.as_tensor(a["weight"], device=dev).contiguous()
         out = {}
-        loss = _ImageLossFused.apply(self.vertices if a["vertices"] else self.vertices.detach(), *tracked, self, a, ior, tex, tgt, wgt, out)
+        verts = self.vertices if a["vertices"] else self.vertices.detach()
+        if screen_param is None and texture_param is None:
+            loss = _ImageLossFused.apply(verts, *tracked, self, a, ior, tex, tgt, wgt, out)
+        else:
+            loss = _ImageLossScreenFused.apply(verts, *tracked, screen_param, texture_param, self, a, ior, tex, tgt, wgt, out)
         self.last_image_count = out["count"]
         return (loss, out["image"]) if a["want_image"] else loss
 

@@ -313,12 +313,66 @@ def _ior_arg(x, name):
     return float(x)
 
 
+def _is_tensor(x):
+    return hasattr(x, "detach") and hasattr(x, "requires_grad")
+
+
+def screen_of_param(screen_param):
+    """The ``Screen`` of a ``screen_param``: a float64 tensor [3, 3] with rows p0, eu, ev on any device, read to the host here, finite,
+    and with axes that pass the ``Screen`` constructor's checks."""
+    if not _is_tensor(screen_param):
+        raise ValueError(f"screen_param must be a float64 tensor of shape (3, 3) with rows p0, eu, ev, got {type(screen_param).__name__}")
+    if tuple(screen_param.shape) != (3, 3):
+        raise ValueError(f"screen_param must have shape (3, 3) with rows p0, eu, ev, got {tuple(screen_param.shape)}")
+    kind = str(screen_param.dtype).replace("torch.", "")
+    if kind != "float64":
+        raise ValueError(f"screen_param must be float64, got dtype {kind}")
+    rows = screen_param.detach().cpu().numpy()
+    if not np.isfinite(rows).all():
+        raise ValueError(f"screen_param must be finite, got {rows!r}")
+    try:
+        return Screen(rows[0], rows[1], rows[2])
+    except ValueError as e:
+        raise ValueError(f"screen_param: {e}") from None
+
+
+def check_texture_param(texture_param):
+    """A ``texture_param``: a float32 or float64 tensor [Th, Tw, C] or [Th, Tw], C in {1, 3}, at least 2 x 2 texels; finite where that
+    can be seen without a device (a host tensor)."""
+    if not _is_tensor(texture_param):
+        raise ValueError(f"texture_param must be a float32 or float64 tensor [Th, Tw, C] or [Th, Tw], got {type(texture_param).__name__}")
+    kind = str(texture_param.dtype).replace("torch.", "")
+    if kind not in ("float32", "float64"):
+        raise ValueError(f"texture_param must be float32 or float64, got dtype {kind}")
+    shape = tuple(texture_param.shape)
+    if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] not in (1, 3)):
+        raise ValueError(f"texture_param must be [Th, Tw], [Th, Tw, 1] or [Th, Tw, 3], got shape {shape}")
+    if shape[0] < 2 or shape[1] < 2:
+        raise ValueError(f"texture_param must be at least 2 x 2 texels, got {shape[:2]}")
+    if texture_param.device.type == "cpu" and not np.isfinite(texture_param.detach().numpy()).all():
+        raise ValueError("texture_param must be finite")
+    return texture_param
+
+
 def check_image_loss_args(camera_M, height, width, screen, texture, target, weight=None, ior_int=None, ior_ext=None, vertices=True,
                           want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
-                          invalid=0.0, max_samples=1 << 22):
+                          invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None):
     """Every argument check of ``Scene.image_loss_fused``, none of which needs a device: ``check_render_args``' dict plus target
     (float32 [H, W, C]; uint8 is read as value / 255; [H, W] with a one-channel texture), weight (float32 [H, W] or None), ior (the float
-    of each IOR given as a number, else None), vertices and want_image."""
+    of each IOR given as a number, else None), vertices and want_image.  ``screen_param`` / ``texture_param`` (tensors a gradient is
+    wanted for) take the place of ``screen`` / ``texture``, which must then be None: exactly one form of each is given."""
+    if screen_param is not None:
+        if screen is not None:
+            raise ValueError("screen_param is given: the positional screen must be None (one of the two supplies the screen)")
+        screen = screen_of_param(screen_param)
+    elif screen is None:
+        raise ValueError("screen is None and no screen_param is given: one of the two must supply the screen")
+    if texture_param is not None:
+        if texture is not None:
+            raise ValueError("texture_param is given: the positional texture must be None (one of the two supplies the texture)")
+        texture = check_texture_param(texture_param).detach()
+    elif texture is None:
+        raise ValueError("texture is None and no texture_param is given: one of the two must supply the texture")
     a = check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples)
     H, W, C = a["height"], a["width"], a["channels"]
     if target is not None and hasattr(target, "shape") and len(target.shape) == 2 and C == 1:

@@ -35,7 +35,7 @@ const char* drt_last_error(void);
 int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
                             * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused;
                             * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image; 9: drt_render_image_loss;
-                            * 10: drt_route_counts */
+                            * 10: drt_route_counts; 11: drt_render_image_loss_screen */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -689,6 +689,25 @@ int drt_render_image_loss(drt_scene_t* s, const double* d_verts, const double* c
                           const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
                           const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
                           int64_t* d_count, void* stream);
+
+/* ---- ... and its gradients w.r.t. the screen's pose and the texture (csrc/drt_image_screen.h states the law) --------
+ * drt_render_image_loss with two more accumulating targets, both nullable (with both NULL the call IS drt_render_image_loss):
+ *   d_grad_screen   nine accumulators += d loss / d (p0, eu, ev) in that order (addressed like d_grad_ior)
+ *   d_grad_texture  [tex_h, tex_w, channels] accumulators += d loss / d (double)texel, the array PADDED to a multiple of three values
+ * Here the DIRECT samples carry a gradient as well as the through ones: every sample of either class that lands on the screen has the
+ * colour c[ch] = T B[ch](u, v) (T = 1 on a direct sample and without `fresnel`) and the seed 2 w_p r_ch / s^2 of its pixel.  Texture: with
+ * B = ((t00 (1 - fx) + t01 fx) (1 - fy)) + ((t10 (1 - fx) + t11 fx) fy) the four texels of the cell receive seed T times (1 - fx)(1 - fy),
+ * fx (1 - fy), (1 - fx) fy, fx fy.  Screen: g_u = T sum_ch seed dB/dfx, g_v likewise, then the statements of `screen` above in reverse
+ * (torch's quotient rule, the cross product's adjoints; eu and ev are independent inputs).  The on-screen test, floor, the clamp of the
+ * cell, the orthogonality check, a sample's class and the fills carry no gradient; a sample's ray depends on neither target, so the vertex
+ * and IOR gradients are drt_render_image_loss's.  One more kernel over the pixels of the band; it also runs on a scene without triangles
+ * (every sample is direct).  No more workspace.  The targets are float64, or FxCell arrays under drt_deterministic.  DRT_E_INVALID as
+ * drt_render_image_loss, and for a texture gradient of more than 2^31 - 1 texels. */
+int drt_render_image_loss_screen(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                                 double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                                 const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                                 const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                                 int64_t* d_count, double* d_grad_screen, double* d_grad_texture, void* stream);
 
 /* ---- measurement (bench.py's live per-kernel timing) --------------------------------------------
  * When enabled (on = 1; on = 2 additionally collects the traversal statistics below, which perturbs
