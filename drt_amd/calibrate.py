@@ -10,7 +10,9 @@ derivative is right well away from it, and the fit bisects a bracket on that sig
 
 ``fit_screen`` fits the POSE of the textured screen behind the object -- placed by hand, calibrated separately -- to plain photographs:
 a rigid motion of the initial screen under the photometric loss of ``Scene.image_loss_fused(..., screen_param=)``,
-mesh and IORs fixed.  It has no command line.
+mesh and IORs fixed.  ``fit_camera`` does the same for the POSE of the camera of one photograph -- a rotation about the camera's own
+centre and a translation of the calibrated camera -- through ``Scene.image_loss_fused(..., camera_param=)``.  Neither has
+a command line.
 """
 from __future__ import annotations
 
@@ -97,10 +99,10 @@ def screen_pose(screen, tex_h, tex_w, six):
     return torch.stack([centre + R @ (p0 - centre) + shift, R @ eu, R @ ev])
 
 
-def fit_pose(loss_of, screen, tex_h, tex_w, steps, lr):
-    """The optimiser of ``fit_screen`` over any ``loss_of(rows)`` (rows: ``screen_pose``'s tensor, which requires grad; returns a scalar
-    tensor): Adam with step ``lr`` (in texels, see ``screen_pose``) on the six numbers from zero.  Returns (the six numbers of the smallest
-    loss seen, the loss history: one float per step, evaluated BEFORE that step's update)."""
+def _adam_from_zero(loss_of_six, steps, lr):
+    """Adam with step ``lr`` on six numbers from zero over ``loss_of_six(six)`` (six: a float64 tensor that requires grad; returns a scalar
+    tensor).  Returns (the six numbers of the smallest loss seen, the loss history: one float per step, evaluated BEFORE that step's
+    update)."""
     if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
         raise ValueError(f"steps must be a positive integer, got {steps!r}")
     if not (float(lr) > 0.0):
@@ -110,7 +112,7 @@ def fit_pose(loss_of, screen, tex_h, tex_w, steps, lr):
     history, best = [], (None, None)
     for _ in range(int(steps)):
         opt.zero_grad()
-        loss = loss_of(screen_pose(screen, tex_h, tex_w, six))
+        loss = loss_of_six(six)
         value = float(loss.detach())
         if best[0] is None or value < best[0]:
             best = (value, six.detach().clone())
@@ -118,6 +120,13 @@ def fit_pose(loss_of, screen, tex_h, tex_w, steps, lr):
         loss.backward()
         opt.step()
     return best[1], history
+
+
+def fit_pose(loss_of, screen, tex_h, tex_w, steps, lr):
+    """The optimiser of ``fit_screen`` over any ``loss_of(rows)`` (rows: ``screen_pose``'s tensor, which requires grad; returns a scalar
+    tensor): Adam with step ``lr`` (in texels, see ``screen_pose``) on the six numbers from zero.  Returns (the six numbers of the smallest
+    loss seen, the loss history: one float per step, evaluated BEFORE that step's update)."""
+    return _adam_from_zero(lambda six: loss_of(screen_pose(screen, tex_h, tex_w, six)), steps, lr)
 
 
 def fit_screen(scene, views, screen, texture, *, steps, lr, **law):
@@ -152,6 +161,59 @@ def fit_screen(scene, views, screen, texture, *, steps, lr, **law):
     six, history = fit_pose(loss_of, screen, tex_h, tex_w, steps, lr)
     rows = screen_pose(screen, tex_h, tex_w, six).numpy()
     return render.Screen(rows[0], rows[1], rows[2]), history
+
+
+def camera_pose(camera_M, six, centre=None, extent=1.0):
+    """(Rinv float64 [4, 4], Kinv float64 [3, 3]) -- a ``camera_param`` -- of ``camera_M`` = (R, K, R^-1, K^-1) moved rigidly by the six
+    numbers ``six`` (a float64 tensor; differentiable): turned about its OWN centre by the rotation vector ``six[3:]`` (in the camera's
+    axes, by the matrix exponential of its cross-product matrix) and moved by the translation ``six[:3]`` (in the camera's axes of the
+    input camera).  Both are scaled to pixels with the object's ``centre`` (default: the world origin) at depth z along the view axis,
+    its ``extent`` e and the focal length f = K[0, 0]: a unit of ``six[0]``, ``six[1]`` (z / f along the image axes) or ``six[3]``,
+    ``six[4]`` (1 / f radians about them) moves the image of the centre by about one pixel; the two motions along and about the view axis
+    leave the image of a centre on that axis where it is, so a unit of ``six[2]`` (z^2 / (f e)) or ``six[5]`` (z / (f e) radians) moves the
+    image of a point one extent to the centre's side by about one pixel.  ``Kinv`` passes through untouched; zero gives the camera
+    itself."""
+    import numpy as np
+    rinv0 = torch.as_tensor(np.asarray(camera_M[2], dtype=np.float64))
+    kinv = torch.as_tensor(np.asarray(camera_M[3], dtype=np.float64))
+    f = float(np.asarray(camera_M[1], dtype=np.float64)[0, 0])
+    axes, position = rinv0[:3, :3], rinv0[:3, 3]
+    c = torch.zeros(3, dtype=torch.float64) if centre is None else torch.as_tensor(np.asarray(centre, dtype=np.float64))
+    z = float(torch.dot(c - position, axes[:, 2]))
+    e = float(extent)
+    if not (f > 0.0 and z > 0.0 and e > 0.0):
+        raise ValueError(f"camera_pose: focal length {f!r}, depth of the centre {z!r} and extent {e!r} must be positive")
+    shift = six[:3] * torch.tensor([z / f, z / f, z * z / (f * e)], dtype=torch.float64)
+    w = six[3:] * torch.tensor([1.0 / f, 1.0 / f, z / (f * e)], dtype=torch.float64)
+    zero = torch.zeros((), dtype=torch.float64)
+    K = torch.stack([torch.stack([zero, -w[2], w[1]]), torch.stack([w[2], zero, -w[0]]), torch.stack([-w[1], w[0], zero])])
+    top = torch.cat([axes @ torch.linalg.matrix_exp(K), (position + axes @ shift).view(3, 1)], dim=1)
+    return torch.cat([top, rinv0[3:4, :]]), kinv
+
+
+def fit_camera(scene, camera_M, photograph, screen, texture, *, weight=None, steps, lr, **law):
+    """The pose of the camera of one ``photograph`` of the fixed mesh of ``scene`` in front of ``screen`` (a ``render.Screen``) and
+    ``texture``: the rigid motion of the calibrated ``camera_M`` (``camera_pose`` builds ``(Rinv, Kinv)`` from six numbers in torch, scaled
+    with ``views.mesh_frame`` of the scene's mesh) that minimises ``Scene.image_loss_fused(None, H, W, screen, texture, photograph,
+    weight=weight, camera_param=pose, vertices=False, **law)`` with H, W the photograph's.  The kernel hands back the 21 partials of the
+    camera; the chain from them to the six numbers is torch autograd.  ``steps`` Adam steps of ``lr`` pixels (``fit_screen``'s loop).
+    The intrinsics are not fitted.  ``law``: the law, IOR and band keywords of ``image_loss_fused``.  Returns (the ``camera_M`` 4-tuple
+    (R, K, R^-1, K^-1) of the smallest loss seen, as numpy arrays; the loss history)."""
+    import numpy as np
+    from . import views
+    for bad in ("camera_param", "screen_param", "texture_param", "vertices", "want_image"):
+        if bad in law:
+            raise ValueError(f"fit_camera sets {bad} itself")
+    centre, extent = views.mesh_frame(scene.mesh.vertices)
+    H, W = int(photograph.shape[0]), int(photograph.shape[1])
+
+    def loss_of(six):
+        pose = camera_pose(camera_M, six, centre, extent)
+        return scene.image_loss_fused(None, H, W, screen, texture, photograph, weight=weight, vertices=False, camera_param=pose, **law).to(six.device)
+
+    six, history = _adam_from_zero(loss_of, steps, lr)
+    rinv, kinv = (m.numpy() for m in camera_pose(camera_M, six, centre, extent))
+    return (np.linalg.inv(rinv), np.asarray(camera_M[1], dtype=np.float64), rinv, kinv), history
 
 
 def main(argv=None):

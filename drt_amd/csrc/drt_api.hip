@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(256) k_fx_from_limbs(const int64_t* __restrict
 extern "C" {
 
 const char* drt_last_error(void) { return g_err; }
-int drt_version(void) { return 11; }
+int drt_version(void) { return 12; }
 
 int drt_deterministic(int on) {
     const int was = det_mode() ? 1 : 0;

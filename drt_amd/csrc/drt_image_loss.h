@@ -121,10 +121,12 @@ DRT_HD void image_screen_uv_backward(const ImageScreen& sc, d3 o, d3 d, double g
 // (g_ori, g_dir) as the exit seeds -- that, FRESNEL, also reverses the throughput T = prod f_k with the seed g_T: a refracting interaction
 // receives g_T times the product of the other factors (those before it kept from the recompute, those after it gathered by the reverse
 // loop), hands it through image_transmittance_backward to the IORs and to ci, and bounce_ci_backward adds ci's share to the vertices
-// and to the incoming direction.  A mirrored interaction has no factor.  g_int / g_ext: set.
+// and to the incoming direction.  A mirrored interaction has no factor.  g_int / g_ext: set.  seed_o / seed_d (both or neither): receive
+// what the reverse loop ends with, the adjoint of the camera ray (o, d) -- the Fresnel share of the incoming direction included
+// (drt_image_camera.h carries it on to the camera).
 template <bool SNELL, bool FRESNEL, typename Add>
 DRT_HD void image_path_backward(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 g_ori, d3 g_dir, double g_T,
-                                Add add, double& g_int, double& g_ext) {
+                                Add add, double& g_int, double& g_ext, d3* seed_o = nullptr, d3* seed_d = nullptr) {
     d3 ro[kMaxBounces], rd[kMaxBounces];
     double before[kMaxBounces];                 // prod_{j < k} f_j
     d3 v0, v1, v2;
@@ -168,13 +170,16 @@ DRT_HD void image_path_backward(const PathCtx& c, d3 o, d3 d, const int32_t* fac
         add(vid[0], ga); add(vid[1], gb); add(vid[2], gc);
         g_o = g_o_in; g_d = g_d_in;
     }
+    if (seed_o) { *seed_o = g_o; *seed_d = g_d; }
 }
 
 // The whole adjoint of one THROUGH sample: camera ray (o, d), face tape, the exit ray and throughput the forward left behind, and the seed
 // g_c[0 .. tx.c) of its pixel.  False (nothing handed to `add`, g_int = g_ext = 0): the sample does not land on the screen.
+// seed_o / seed_d: image_path_backward's, written only when true is returned.
 template <bool SNELL, bool FRESNEL, typename Add>
 DRT_HD bool image_sample_backward(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 exit_o, d3 exit_d, double T,
-                                  const ImageScreen& sc, const ImageTex& tx, const double* g_c, Add add, double& g_int, double& g_ext) {
+                                  const ImageScreen& sc, const ImageTex& tx, const double* g_c, Add add, double& g_int, double& g_ext,
+                                  d3* seed_o = nullptr, d3* seed_d = nullptr) {
     g_int = 0.0; g_ext = 0.0;
     double u, v;
     if (!image_screen_uv(sc, tx.th, tx.tw, exit_o, exit_d, u, v)) return false;
@@ -188,7 +193,7 @@ DRT_HD bool image_sample_backward(const PathCtx& c, d3 o, d3 d, const int32_t* f
     }
     d3 g_o, g_d;
     image_screen_uv_backward(sc, exit_o, exit_d, T * s_x, T * s_y, g_o, g_d);
-    image_path_backward<SNELL, FRESNEL>(c, o, d, faces, face_stride, n_hits, g_o, g_d, g_T, add, g_int, g_ext);
+    image_path_backward<SNELL, FRESNEL>(c, o, d, faces, face_stride, n_hits, g_o, g_d, g_T, add, g_int, g_ext, seed_o, seed_d);
     return true;
 }
 

@@ -6,7 +6,7 @@
 //   k_image_screen_bwd  all pixels : image_pixel_walk's walk over the s x s samples of its pixel -- a direct sample's camera ray formed again,
 //                                    a through sample's exit ray and throughput from the parked rows -- and image_sample_backward_screen per
 //                                    sample that lands on the screen: the nine screen partials through nine LossAcc summed over the block
-//                                    (block_flush9: one atomic per block and partial), the four texel contributions through PathSink in
+//                                    (block_flush, drt_image_wave.h: one atomic per block and partial), the four texel contributions through PathSink in
 //                                    kImageScreenBatch-sized fills (sink_pass); TEXTURE = false: no table in LDS
 // The texture gradient in the sink: with three channels the texel number is the id and the channels are the d3; with one channel the id is
 // texel / 3 and one component is non-zero, which is why the accumulator is padded to a multiple of three values.  No tree is read and no
@@ -20,46 +20,6 @@
 // fill up sends the rest straight to memory (HashAdd3 / FxHashAdd3), so the batch only bounds the cost, never the result.
 constexpr int kImageScreenBatch = kPathsBwdBatch;
 constexpr int kImageScreenBpc = DRT_BWD_BPC;       // 56 KB of table per block
-
-// The nine screen sums of a block into their accumulators (whole block): a wave sum each, the four waves' sums added in LDS, then ONE atomic
-// (pair) per block and accumulator.  LossAcc::flush's one atomic per wave was measured first (profiles/render_image_loss_screen.txt): the
-// nine accumulators share a cache line, on which the 18 432 atomics of a launch are served one after the other -- 0.2 ms of a pass that
-// otherwise takes 0.1.  In either mode the sums are those LossAcc::flush would add: exact integers (DET), or float64 in a fixed order.
-template <bool DET>
-__device__ __forceinline__ void block_flush9(LossAcc<DET>* acc, double* grad_screen) {
-    constexpr int kWaves = 256 / 64;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, k = threadIdx.x;
-    if constexpr (DET) {
-        __shared__ long long part_hi[kWaves][9];
-        __shared__ unsigned long long part_lo[kWaves][9];
-        __shared__ unsigned part_flags[kWaves][9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const FxAcc a = fx_wave_sum(acc[j].a);
-            if (lane == 0) { part_hi[wave][j] = a.v.hi; part_lo[wave][j] = a.v.lo; part_flags[wave][j] = a.flags; }
-        }
-        __syncthreads();
-        if (k < 9) {
-            Fx128 v{part_hi[0][k], part_lo[0][k]};
-            unsigned flags = part_flags[0][k];
-            for (int w = 1; w < kWaves; ++w) { v = fx_add(v, Fx128{part_hi[w][k], part_lo[w][k]}); flags |= part_flags[w][k]; }
-            fx_atomic_add(reinterpret_cast<FxCell*>(grad_screen) + k, v, flags);
-        }
-    } else {
-        __shared__ double part[kWaves][9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const double v = wave_sum(acc[j].v);
-            if (lane == 0) part[wave][j] = v;
-        }
-        __syncthreads();
-        if (k < 9) {
-            double v = part[0][k];
-            for (int w = 1; w < kWaves; ++w) v += part[w][k];
-            if (v != 0.0) unsafeAtomicAdd(grad_screen + k, v);
-        }
-    }
-}
 
 // grad_screen (nine accumulators: p0, eu, ev) and grad_texture (TEXTURE) may each be null.
 template <bool DET, bool TEXTURE>
@@ -101,7 +61,7 @@ __global__ void __launch_bounds__(256) k_image_screen_bwd(ImageCam cam, ImageBan
             acc[6].add(g_ev.x); acc[7].add(g_ev.y); acc[8].add(g_ev.z);
         }
     });
-    if (grad_screen) block_flush9<DET>(acc, grad_screen);
+    if (grad_screen) block_flush<DET, 9>(acc, grad_screen);
 }
 
 int launch_image_screen_bwd(const drt_scene* s, const ImageCall& c, const double* g_c, double* d_grad_screen, double* d_grad_texture, hipStream_t st) {

@@ -51,6 +51,56 @@ int image_forward(drt_scene* s, const double* d_verts, const ImageCall& call, bo
 // ([tex_h, tex_w, C] accumulators, padded to a multiple of three values) are accumulated into; one of them may be null.
 int launch_image_screen_bwd(const drt_scene* s, const ImageCall& call, const double* g_c, double* d_grad_screen, double* d_grad_texture, hipStream_t st);
 
+// Defined in drt_image_camera.hip (drt_render_image_loss_camera).  launch_image_loss_bwd_camera: k_image_loss_bwd with
+// CAMERA on -- what image_loss_call launches over the list of through samples, which here also stores the camera-ray seeds
+// `seeds` [2, band.n, 3] float64 (g_o rows, then g_d rows, under the sample index); d_grad_verts, d_grad_ior and d_count may be null.
+// launch_image_camera_bwd: k_image_camera_bwd over the pixels of the band, behind the resolve kernel (g_c) and, on a scene with
+// triangles, behind launch_image_loss_bwd_camera (seeds; not read on a scene without); d_grad_camera: 21 accumulators, kinv then rinv.
+int launch_image_loss_bwd_camera(const drt_scene* s, const PathCtx& pc, const ImageCall& call, int grid, const int32_t* list, const unsigned* n_list,
+                                 const double* g_c, double* d_grad_verts, double* d_grad_ior, unsigned long long* d_count, double* seeds, hipStream_t st);
+int launch_image_camera_bwd(const drt_scene* s, const ImageCall& call, const double* g_c, const double* seeds, double* d_grad_camera, hipStream_t st);
+
+// The N sums of a block of 256 threads into their accumulators grad[0 .. N) (whole block): a wave sum each, the four waves' sums added in
+// LDS, then ONE atomic (pair) per block and accumulator.  LossAcc::flush's one atomic per wave was measured first
+// (profiles/render_image_loss_screen.txt): accumulators that share a cache line are served one after the other -- with nine of them,
+// 18 432 atomics of a launch, 0.2 ms of a pass that otherwise takes 0.1.  In either mode the sums are those LossAcc::flush would add:
+// exact integers (DET), or float64 in a fixed order.
+template <bool DET, int N>
+__device__ __forceinline__ void block_flush(LossAcc<DET>* acc, double* grad) {
+    constexpr int kWaves = 256 / 64;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, k = threadIdx.x;
+    if constexpr (DET) {
+        __shared__ long long part_hi[kWaves][N];
+        __shared__ unsigned long long part_lo[kWaves][N];
+        __shared__ unsigned part_flags[kWaves][N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const FxAcc a = fx_wave_sum(acc[j].a);
+            if (lane == 0) { part_hi[wave][j] = a.v.hi; part_lo[wave][j] = a.v.lo; part_flags[wave][j] = a.flags; }
+        }
+        __syncthreads();
+        if (k < N) {
+            Fx128 v{part_hi[0][k], part_lo[0][k]};
+            unsigned flags = part_flags[0][k];
+            for (int w = 1; w < kWaves; ++w) { v = fx_add(v, Fx128{part_hi[w][k], part_lo[w][k]}); flags |= part_flags[w][k]; }
+            fx_atomic_add(reinterpret_cast<FxCell*>(grad) + k, v, flags);
+        }
+    } else {
+        __shared__ double part[kWaves][N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const double v = wave_sum(acc[j].v);
+            if (lane == 0) part[wave][j] = v;
+        }
+        __syncthreads();
+        if (k < N) {
+            double v = part[0][k];
+            for (int w = 1; w < kWaves; ++w) v += part[w][k];
+            if (v != 0.0) unsafeAtomicAdd(grad + k, v);
+        }
+    }
+}
+
 // The context image_forward traced with (the same for the adjoint of the loss).
 inline PathCtx image_path_ctx(const drt_scene* s, const double* d_verts, const ImageCall& call) {
     PathCtx pc = path_ctx(s, d_verts, call.ior_int, call.ior_ext);

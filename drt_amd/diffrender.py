@@ -948,6 +948,83 @@ class _ImageLossScreenFused(torch.autograd.Function):
         return g_v, g_ior[0], g_ior[1], g_end[0], g_end[1], None, None, None, None, None, None, None
 
 
+class _ImageLossCameraFused(torch.autograd.Function):
+    """_ImageLossScreenFused that also differentiates the camera (drt_render_image_loss_camera): ``rinv_param`` /
+    ``kinv_param`` stand for the tensors of ``camera_param`` autograd tracks; ``a["camera"]`` carries their values.  The 21 camera partials
+    are computed here with a unit seed, band after band into one set of accumulators -- allocated only when one of the two requires grad
+    --; the backward scales them and hands them back in the two tensors' shapes: K^-1's nine, and R^-1's twelve as its top three rows (a
+    [4, 4] one gets a zero bottom row, which the renderer does not read)."""
+
+    @staticmethod
+    def forward(ctx, vertices, ior_int, ior_ext, screen_param, texture_param, rinv_param, kinv_param, scene, a, ior, tex, target, weight, out):
+        v = _f64c(vertices.detach(), "vertices")
+        dev = v.device
+        H, W, C = a["height"], a["width"], a["channels"]
+        loss = det.scalar(dev)
+        grad_v = det.acc(v) if a["vertices"] else None
+        tracked_ior = any(ctx.needs_input_grad[1:3])
+        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=dev)) if tracked_ior else None
+        n_tex = tex.numel()
+        like_s = torch.empty(9, dtype=torch.float64, device=dev)
+        like_t = torch.empty((n_tex + 2) // 3 * 3, dtype=torch.float64, device=dev)      # (a one-channel texture is scattered in threes)
+        like_c = torch.empty(21, dtype=torch.float64, device=dev)
+        grad_s = det.acc(like_s) if screen_param is not None and ctx.needs_input_grad[3] else None
+        grad_t = det.acc(like_t) if texture_param is not None and ctx.needs_input_grad[4] else None
+        grad_c = det.acc(like_c) if any(ctx.needs_input_grad[5:7]) else None
+        count = torch.zeros((), dtype=torch.int64, device=dev)
+        image = torch.empty((H, W, C), dtype=torch.float32, device=dev) if a["want_image"] else None
+        with _on(dev):
+            for y0, y1 in a["bands"]:
+                _lib.check(_lib.lib().drt_render_image_loss_camera(
+                    scene.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
+                    a["law_flags"], a["fresnel"], a["screen"].ctypes.data, tex.data_ptr(), tex.shape[0], tex.shape[1], C, a["void"].ctypes.data,
+                    a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss.data_ptr(), _lib.ptr(grad_v), _lib.ptr(grad_ior),
+                    _lib.ptr(image), count.data_ptr(), _lib.ptr(grad_s), _lib.ptr(grad_t), _lib.ptr(grad_c), _stream()))
+        out["image"], out["count"] = image, count
+        like = lambda x: (x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None      # noqa: E731
+        ctx.ior_like = (like(ior_int), like(ior_ext))
+        ctx.end_like = (like(screen_param), like(texture_param))
+        ctx.cam_like = (like(rinv_param), like(kinv_param))
+        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
+        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v),
+                              None if grad_ior is None else det.value(grad_ior, torch.empty(2, dtype=torch.float64)),
+                              None if grad_s is None else det.value(grad_s, like_s), None if grad_t is None else det.value(grad_t, like_t)[:n_tex],
+                              None if grad_c is None else det.value(grad_c, like_c))
+        return det.value(loss)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        grad_v, both, grad_s, grad_t, grad_c = ctx.saved_tensors
+        g_ior, g_end, g_cam = [None, None], [None, None], [None, None]
+        for k in (0, 1):
+            if both is not None and ctx.needs_input_grad[1 + k]:
+                shape, dtype, dev = ctx.ior_like[k]
+                g_ior[k] = (both[k] * g_loss).reshape(shape).to(dtype=dtype, device=dev)
+        for k, g in enumerate((grad_s, grad_t)):
+            if g is not None and ctx.needs_input_grad[3 + k]:
+                shape, dtype, dev = ctx.end_like[k]
+                g_end[k] = (g * g_loss).reshape(shape).to(dtype=dtype, device=dev)
+        if grad_c is not None:
+            scaled = grad_c * g_loss
+            if ctx.needs_input_grad[5]:
+                shape, dtype, dev = ctx.cam_like[0]
+                rows = scaled[9:].reshape(3, 4)
+                if tuple(shape) == (4, 4):
+                    rows = torch.cat([rows, torch.zeros((1, 4), dtype=rows.dtype, device=rows.device)])
+                g_cam[0] = rows.to(dtype=dtype, device=dev)
+            if ctx.needs_input_grad[6]:
+                shape, dtype, dev = ctx.cam_like[1]
+                g_cam[1] = scaled[:9].reshape(3, 3).to(dtype=dtype, device=dev)
+        if grad_v is None or not ctx.needs_input_grad[0]:
+            g_v = None
+        elif det.SINK is not None and ctx.wide is not None:
+            det.SINK.append((ctx.wide, g_loss))
+            g_v = None
+        else:
+            g_v = grad_v * g_loss
+        return g_v, g_ior[0], g_ior[1], g_end[0], g_end[1], g_cam[0], g_cam[1], None, None, None, None, None, None, None
+
+
 def ray_loss(out_ori, out_dir, mask, screen_pixel, valid):
     """sum over valid & mask rays of |out_dir - normalize(screen_pixel - out_ori.detach())|^2."""
     link = getattr(out_dir, "_drt_link", None) if SPARSE_LOSS_GRAD else None
@@ -1173,13 +1250,13 @@ class Scene(StepwiseMixin):
 
     def image_loss_fused(self, camera_M, height, width, screen, texture, target, *, weight=None, ior_int=None, ior_ext=None, vertices=True,
                          want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
-                         invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None):
+                         invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None):
         """The photometric loss of ``render_image`` against a photograph: sum over pixels and channels of ``w (I - target)^2`` with ``I``
         the float64 pixel mean ``render_image`` rounds to float32 -- as a scalar, with its vertex gradient AND d loss / d (ior_int,
         ior_ext) computed alongside with a unit seed and scaled in the backward pass (drt_render_image_loss; csrc/drt_image_loss.h and
         DESIGN.md 10.3 state the law).  The gradient is the derivative of the whole law, Fresnel weights included, through the samples
         whose path completes and lands on the screen; a sample's class, its faces, the texel cell and the screen's border carry none,
-        and none reaches the camera; the screen's pose and the texture receive one through ``screen_param`` / ``texture_param`` (below).
+        the screen's pose, the texture and the camera receive one through ``screen_param`` / ``texture_param`` / ``camera_param`` (below).
         ``target``: ``[height, width, C]`` (or ``[height, width]`` with a
         one-channel texture), float32, or uint8 read as value / 255; ``weight``: float32 ``[height, width]`` or None; numpy or device
         tensors.  ``ior_int`` / ``ior_ext``: None (this module's ``intIOR`` / ``extIOR``), floats, or 0-dim tensors (each is read to the
@@ -1193,11 +1270,17 @@ class Scene(StepwiseMixin):
         the loss is differentiable w.r.t. it when it requires grad.  ``texture_param``: a float32 or float64 tensor ``[Th, Tw, C]`` (or
         ``[Th, Tw]``) that supplies the texture instead of ``texture`` (then None); its gradient comes back in its own dtype, device and
         shape.  For these two the DIRECT samples carry a gradient as well (drt_render_image_loss_screen; csrc/drt_image_screen.h and
-        DESIGN.md 10.4 state the law); the vertex and IOR gradients are the same with and without them.  Without either keyword the call
-        is what it was."""
+        DESIGN.md 10.4 state the law); the vertex and IOR gradients are the same with and without them.
+        ``camera_param``: the pair ``(Rinv, Kinv)`` of float64 tensors on any device -- ``Rinv`` ``[4, 4]`` or ``[3, 4]`` (camera -> world;
+        its top three rows are read), ``Kinv`` ``[3, 3]`` -- that supplies the camera INSTEAD of ``camera_M`` (then None); the values are
+        read to the host once per call, and the loss is differentiable w.r.t. whichever of the two requires grad: all 21 numbers the
+        renderer reads are independent inputs, and the gradient comes back in the tensors' own shapes (a ``[4, 4]`` ``Rinv`` gets a zero
+        bottom row).  Direct and through samples both carry it (drt_render_image_loss_camera; csrc/drt_image_camera.h and DESIGN.md 10.5
+        state the law); silhouettes are not differentiated.  It composes with the other keywords, ``vertices`` and tensor IORs, whose
+        gradients are the same with and without it.  Without any of the three keywords the call is what it was."""
         from . import render as _render
         a = _render.check_image_loss_args(camera_M, height, width, screen, texture, target, weight, ior_int, ior_ext, vertices, want_image, supersample,
-                                          max_bounces, tir, refraction, fresnel, void, invalid, max_samples, screen_param, texture_param)
+                                          max_bounces, tir, refraction, fresnel, void, invalid, max_samples, screen_param, texture_param, camera_param)
         given = [intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext]
         ior = tuple(_ior_host(x, name) for x, name in zip(given, ("ior_int", "ior_ext")))
         tracked = tuple(x if isinstance(x, torch.Tensor) else None for x in given)
@@ -1209,7 +1292,9 @@ class Scene(StepwiseMixin):
             wgt = None if a["weight"] is None else torch.as_tensor(a["weight"], device=dev).contiguous()
         out = {}
         verts = self.vertices if a["vertices"] else self.vertices.detach()
-        if screen_param is None and texture_param is None:
+        if camera_param is not None:
+            loss = _ImageLossCameraFused.apply(verts, *tracked, screen_param, texture_param, camera_param[0], camera_param[1], self, a, ior, tex, tgt, wgt, out)
+        elif screen_param is None and texture_param is None:
             loss = _ImageLossFused.apply(verts, *tracked, self, a, ior, tex, tgt, wgt, out)
         else:
             loss = _ImageLossScreenFused.apply(verts, *tracked, screen_param, texture_param, self, a, ior, tex, tgt, wgt, out)

@@ -354,13 +354,49 @@ def check_texture_param(texture_param):
     return texture_param
 
 
+def camera_of_param(camera_param):
+    """The ``camera_M`` 4-tuple ``(None, None, R^-1 [4, 4], K^-1)`` of a ``camera_param`` = ``(Rinv, Kinv)``: float64 tensors on any device,
+    ``Rinv`` [4, 4] or [3, 4] (its top three rows are what the renderer reads; a [3, 4] one is completed by the row (0, 0, 0, 1)),
+    ``Kinv`` [3, 3]; read to the host here, finite."""
+    try:
+        n = len(camera_param)
+    except TypeError:
+        n = -1
+    if isinstance(camera_param, (str, bytes)) or _is_tensor(camera_param) or n != 2:
+        raise ValueError(f"camera_param must be the pair (Rinv, Kinv) of float64 tensors, got {type(camera_param).__name__}"
+                         + (f" of {n} entries" if n >= 0 and not _is_tensor(camera_param) else ""))
+    mats = []
+    for x, shapes, name in ((camera_param[0], ((4, 4), (3, 4)), "Rinv"), (camera_param[1], ((3, 3),), "Kinv")):
+        want = " or ".join(str(sh) for sh in shapes)
+        if not _is_tensor(x):
+            raise ValueError(f"camera_param: {name} must be a float64 tensor of shape {want}, got {type(x).__name__}")
+        if tuple(x.shape) not in shapes:
+            raise ValueError(f"camera_param: {name} must have shape {want}, got {tuple(x.shape)}")
+        kind = str(x.dtype).replace("torch.", "")
+        if kind != "float64":
+            raise ValueError(f"camera_param: {name} must be float64, got dtype {kind}")
+        m = x.detach().cpu().numpy()
+        if not np.isfinite(m).all():
+            raise ValueError(f"camera_param: {name} must be finite, got {m!r}")
+        mats.append(m)
+    rinv = mats[0] if mats[0].shape == (4, 4) else np.concatenate([mats[0], np.array([[0.0, 0.0, 0.0, 1.0]])])
+    return (None, None, rinv, mats[1])
+
+
 def check_image_loss_args(camera_M, height, width, screen, texture, target, weight=None, ior_int=None, ior_ext=None, vertices=True,
                           want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
-                          invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None):
+                          invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None):
     """Every argument check of ``Scene.image_loss_fused``, none of which needs a device: ``check_render_args``' dict plus target
     (float32 [H, W, C]; uint8 is read as value / 255; [H, W] with a one-channel texture), weight (float32 [H, W] or None), ior (the float
     of each IOR given as a number, else None), vertices and want_image.  ``screen_param`` / ``texture_param`` (tensors a gradient is
-    wanted for) take the place of ``screen`` / ``texture``, which must then be None: exactly one form of each is given."""
+    wanted for) take the place of ``screen`` / ``texture``, which must then be None: exactly one form of each is given; so does
+    ``camera_param`` = ``(Rinv, Kinv)`` for ``camera_M``."""
+    if camera_param is not None:
+        if camera_M is not None:
+            raise ValueError("camera_param is given: the positional camera_M must be None (one of the two supplies the camera)")
+        camera_M = camera_of_param(camera_param)
+    elif camera_M is None:
+        raise ValueError("camera_M is None and no camera_param is given: one of the two must supply the camera")
     if screen_param is not None:
         if screen is not None:
             raise ValueError("screen_param is given: the positional screen must be None (one of the two supplies the screen)")

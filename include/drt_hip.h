@@ -35,7 +35,7 @@ const char* drt_last_error(void);
 int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
                             * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused;
                             * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image; 9: drt_render_image_loss;
-                            * 10: drt_route_counts; 11: drt_render_image_loss_screen */
+                            * 10: drt_route_counts; 11: drt_render_image_loss_screen; 12: drt_render_image_loss_camera */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -708,6 +708,27 @@ int drt_render_image_loss_screen(drt_scene_t* s, const double* d_verts, const do
                                  const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
                                  const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
                                  int64_t* d_count, double* d_grad_screen, double* d_grad_texture, void* stream);
+
+/* ---- ... and its gradient w.r.t. the camera (csrc/drt_image_camera.h states the law) --------------------------------
+ * drt_render_image_loss_screen with one more accumulating target, nullable (with NULL the call IS drt_render_image_loss_screen):
+ *   d_grad_camera   21 accumulators += d loss / d camera21 in camera21's order, K^-1 [9] then the top 3 x 4 of R^-1 [12] (addressed like
+ *                   d_grad_ior)
+ * Every direct and every through sample that lands on the screen carries a gradient through its camera ray.  A through sample's seeds are
+ * the adjoint (g_o, g_d) of the camera ray that the reverse loop of drt_render_image_loss's path adjoint ends with, the Fresnel share of
+ * the incoming direction included; a direct sample's are the screen plane's adjoint on the camera ray itself (T = 1).  Then the
+ * statements of `camera21` above in reverse under torch's conventions: origin = R^-1[:, 3], dir = w / sqrt((w_x^2 + w_y^2) + w_z^2),
+ * w = R^-1[:3, :3] p, p = K^-1 (px, py, 1); all 21 numbers are independent inputs (no bottom row (0, 0, 1) is assumed).  A sample's
+ * class, the face tape, the TIR flags, the entering branch, floor, the clamp of the cell, the on-screen test and the fills carry no
+ * gradient; silhouettes are not differentiated.  The other gradients and *d_count are drt_render_image_loss_screen's, bit for bit
+ * under drt_deterministic.  The adjoint over the through samples runs whenever d_grad_camera is given (on a scene with triangles) and
+ * parks the seeds; one more kernel over the pixels of the band reduces them, and it also runs on a scene without triangles (every sample
+ * is direct).  Workspace: drt_render_image_loss's plus 48 bytes per sample of the band; the first call of a size allocates and cannot run
+ * inside a stream capture.  DRT_E_INVALID as drt_render_image_loss_screen. */
+int drt_render_image_loss_camera(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                                 double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                                 const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                                 const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                                 int64_t* d_count, double* d_grad_screen, double* d_grad_texture, double* d_grad_camera, void* stream);
 
 /* ---- measurement (bench.py's live per-kernel timing) --------------------------------------------
  * When enabled (on = 1; on = 2 additionally collects the traversal statistics below, which perturbs
