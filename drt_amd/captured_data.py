@@ -231,6 +231,75 @@ class SyntheticData(Data):
         self._resident = dict(self.Views)
 
 
+class PhotoData(Data):
+    """A capture of plain photographs of a known background for the photometric loop (optim.PhotoIteration): per view a
+    camera ``(R, K, R^-1, K^-1)`` and a ``render.Screen``, ONE background ``texture`` float32 ``[Th, Tw, C]`` for all of them, the
+    photograph stack ``photos`` ``[n, resy, resx, C]`` (float32, or uint8 read as value / 255; numpy or a device tensor) with optional
+    ``weights`` ``[n, resy, resx]``, and the soft silhouette masks ``soft_masks`` float64 ``[n, resy, resx]`` of the silhouette term.
+    ``get_view`` keeps the tuple layout of ``Data.get_view`` for that term -- (None, None, soft mask [P], eye point [1, 3], None,
+    camera_M): a photograph has no per-pixel correspondences, so those fields are None.  ``binding(scene)`` is the capture as a
+    ``render.ImageViews`` of that scene."""
+
+    def __init__(self, cameras, screens, texture, photos, soft_masks, resx, resy, weights=None, device="cuda", seed=0, name="photo"):
+        self.cameras, self.screens, self.texture = list(cameras), list(screens), texture
+        self.photos, self.weights = photos, weights
+        self.resx, self.resy = int(resx), int(resy)
+        self.num_view = self.n_total = len(self.cameras)
+        self.name, self.device = name, device
+        self.rng = np.random.RandomState(seed)
+        self.Views = []
+        for cam, soft in zip(self.cameras, soft_masks):
+            camera_M = tuple(torch.as_tensor(np.asarray(m.cpu() if hasattr(m, "cpu") else m), dtype=Float) for m in cam)
+            eye = camera_M[2][:3, 3].reshape(1, 3).clone()
+            self.Views.append((None, None, torch.as_tensor(np.asarray(soft.cpu() if hasattr(soft, "cpu") else soft), dtype=Float).reshape(-1), eye, None, camera_M))
+
+    def get_view(self, V_index):
+        cache = self.__dict__.setdefault("_resident", {})
+        V_index = int(V_index)
+        hit = cache.get(V_index)
+        if hit is None:
+            _, _, mask, eye, _, camera_M = self.Views[V_index]
+            dev = self.device
+            hit = cache[V_index] = (None, None, mask.to(dev), eye.to(dev), None, tuple(m.to(dev) for m in camera_M))
+        return hit
+
+    def binding(self, scene):
+        """The capture's views bound to ``scene`` (``Scene.bind_image_views``), made once per scene."""
+        import weakref
+        held = self.__dict__.get("_image_views")
+        if held is None or held[0]() is not scene:
+            b = scene.bind_image_views(self.cameras, self.resy, self.resx, self.screens, self.photos, self.weights)
+            held = self._image_views = (weakref.ref(scene), b)
+        return held[1]
+
+
+class SyntheticPhotoData(PhotoData):
+    """Turntable photographs of a ground-truth mesh in front of a textured screen, rendered by ``scene_gt.render_image`` under
+    ``path_law`` = (max_bounces, tir[, refraction]) with ``supersample``^2 samples per pixel: per view the screen is
+    ``render.Screen.behind`` the object, the photograph the rendered image, and the silhouette mask the pixels with an interaction (the
+    ``hit`` plane > 0) through ``views.process_mask``.  ``view_ids``: keep only these views of the turntable of ``n_total``."""
+
+    def __init__(self, scene_gt, center, extent, resx, resy, texture, num_view=8, device="cuda", n_total=None, view_ids=None, seed=0,
+                 name="synthetic-photo", path_law=(6, "reflect", "snell"), supersample=2, fresnel=True, span=2.0, void=0.0, invalid=0.0):
+        from . import render
+        tex = render.check_texture(texture)
+        n_total = num_view if n_total is None else n_total
+        cams = views.turntable_cameras(center, extent, n_total, resx, resy)
+        ids = list(range(n_total)) if view_ids is None else list(view_ids)
+        law = tuple(path_law) + ("reference",) * (3 - len(path_law))
+        cameras, screens, photos, soft = [], [], [], []
+        for k in ids:
+            screen = render.Screen.behind(cams[k], center, extent, tex.shape[1], tex.shape[0], span=span)
+            image, hit, _ = scene_gt.render_image(cams[k], resy, resx, screen, tex, supersample=supersample, max_bounces=law[0], tir=law[1],
+                                                  refraction=law[2], fresnel=fresnel, void=void, invalid=invalid, want_planes=True)
+            cameras.append(cams[k])
+            screens.append(screen)
+            photos.append(image)
+            soft.append(views.process_mask((hit > 0).cpu().numpy()))
+        super().__init__(cameras, screens, tex, torch.stack(photos), soft, resx, resy, device=device, seed=seed, name=name)
+        self.path_law, self.supersample, self.fresnel, self.void, self.invalid = law, supersample, fresnel, void, invalid
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # writing a capture file (the reference only reads them; its captures are not distributed).  The arrays follow the
 # schema its loaders index (captured_data.py:94-108 PointGrey, 136-149 Redmi): per-view world->camera matrices

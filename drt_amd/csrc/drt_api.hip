@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(256) k_fx_from_limbs(const int64_t* __restrict
 extern "C" {
 
 const char* drt_last_error(void) { return g_err; }
-int drt_version(void) { return 12; }
+int drt_version(void) { return 13; }
 
 int drt_deterministic(int on) {
     const int was = det_mode() ? 1 : 0;
@@ -218,6 +218,7 @@ void drt_destroy(drt_scene_t* s) {
         if (w.fill_join) (void)hipEventDestroy(w.fill_join);
         if (w.stream) (void)hipStreamDestroy(w.stream);
     }
+    image_views_free(s);
     image_loss_free(s);
     paths_free(s);
     (void)hipFree(s->vcount);

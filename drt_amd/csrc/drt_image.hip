@@ -169,7 +169,18 @@ int image_call_check(const double* camera21, int height, int width, int y0, int 
     return DRT_OK;
 }
 
-int image_forward(drt_scene* s, const double* d_verts, const ImageCall& c, bool keep_tape, hipStream_t st, const char* who) {
+namespace {
+
+// image_forward's own start: k_image_start with the camera of the call (`src`)
+void image_start_one(const ImageStartArgs& a, const void* src) {
+    const ImageCall& c = *static_cast<const ImageCall*>(src);
+    k_image_start<<<a.grid, kPathBlock, 0, a.st>>>(a.nodes, a.n_tris, c.cam, c.band, a.park_ori, a.park_dir, a.thr, a.state, a.hits, a.out, a.count);
+}
+
+}  // namespace
+
+int image_forward_from(drt_scene* s, const double* d_verts, const ImageCall& c, bool keep_tape, hipStream_t st, const char* who, ImageStartFn start,
+                       const void* src) {
     { int rc = ensure_paths_ws(s, c.n, st, who); if (rc) return rc; }
     { int rc = ensure_paths_fused_ws(s, c.n, st, who); if (rc) return rc; }
     { int rc = ensure_image_thr(s, c.n, st, who); if (rc) return rc; }
@@ -181,7 +192,7 @@ int image_forward(drt_scene* s, const double* d_verts, const ImageCall& c, bool 
     double* const park_dir = w.park + 3 * w.fused_cap;
     HIP_TRY(hipMemsetAsync(w.cnt, 0, sizeof(unsigned) * kCntWords, st));
     const RayList l0{w.idx[0], w.ray[0], w.face[0]};
-    k_image_start<<<gs, kPathBlock, 0, st>>>(pc.tc.nodes, pc.tc.n_tris, c.cam, c.band, park_ori, park_dir, w.thr, w.state, w.hits, l0, w.cnt + kCntList);
+    start(ImageStartArgs{pc.tc.nodes, pc.tc.n_tris, park_ori, park_dir, w.thr, w.state, w.hits, l0, w.cnt + kCntList, gs, st}, src);
     if (s->n_faces > 0) {
         const ImageShade shade = image_shade_kernel(c.snell, c.fresnel, keep_tape);
         int32_t* const tape = keep_tape ? w.tape : nullptr;
@@ -190,6 +201,10 @@ int image_forward(drt_scene* s, const double* d_verts, const ImageCall& c, bool 
         });
     }
     return DRT_OK;
+}
+
+int image_forward(drt_scene* s, const double* d_verts, const ImageCall& c, bool keep_tape, hipStream_t st, const char* who) {
+    return image_forward_from(s, d_verts, c, keep_tape, st, who, image_start_one, &c);
 }
 
 extern "C" {

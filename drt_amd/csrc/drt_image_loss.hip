@@ -19,15 +19,6 @@
 // Everything runs on the caller's stream, nothing is read back, every list size stays on the device.
 #include "drt_image_loss_bwd.h"
 
-struct ImageLossWs {
-    int64_t cap = 0;               // doubles of g_c
-    double* g_c = nullptr;         // [n_pix, C] of the band in flight
-    int64_t seed_cap = 0;          // doubles of seeds
-    double* seeds = nullptr;       // [2, n, 3] of the band in flight: the camera-ray seeds of drt_render_image_loss_camera
-};
-
-constexpr int kImageLossBpc = 4;           // blocks per CU of the kernel without the table (registers bound it: DESIGN.md 10.3)
-
 // One thread per pixel of the band.  weight / image may be null.
 template <bool DET>
 __global__ void __launch_bounds__(kPathBlock) k_image_loss_resolve(ImageCam cam, ImageBand band, int64_t n_pix, ImageScreen sc, ImageTex tx, ImageFill fill,
@@ -72,6 +63,8 @@ int grow_image_loss_buffer(double*& buf, int64_t& cap, int64_t n, hipStream_t st
     return DRT_OK;
 }
 
+}  // namespace
+
 // the pixel seeds [n_seed], grown like the throughputs they sit beside (drt_image.hip); the camera-ray seeds [n_cam] (0: none wanted) likewise
 int ensure_image_loss_ws(drt_scene* s, int64_t n_seed, int64_t n_cam, hipStream_t st, const char* who) {
     ImageLossWs* lw = static_cast<ImageLossWs*>(s->image_loss_ws);
@@ -83,8 +76,6 @@ int ensure_image_loss_ws(drt_scene* s, int64_t n_seed, int64_t n_cam, hipStream_
     { int rc = grow_image_loss_buffer(lw->g_c, lw->cap, n_seed, st, who, "pixel seeds"); if (rc) return rc; }
     return grow_image_loss_buffer(lw->seeds, lw->seed_cap, n_cam, st, who, "camera-ray seeds");
 }
-
-}  // namespace
 
 void image_loss_free(drt_scene* s) {
     ImageLossWs* lw = static_cast<ImageLossWs*>(s->image_loss_ws);

@@ -46,6 +46,35 @@ int image_call_check(const double* camera21, int height, int width, int y0, int 
 // [K, n] -- without it the tape is left untouched.  `who`: the entry point, for messages.
 int image_forward(drt_scene* s, const double* d_verts, const ImageCall& call, bool keep_tape, hipStream_t st, const char* who);
 
+// image_forward with the start kernel of the caller's choice (drt_image_views.hip: the samples of several views in one band): `start`
+// launches on a.st, with a.grid blocks of kPathBlock threads, a kernel that does for every sample of the band what k_image_start does;
+// `src` is handed through to it.  image_forward is this with k_image_start and the camera of the call.
+struct ImageStartArgs {
+    const Node4Q* nodes;
+    int n_tris;
+    double *park_ori, *park_dir, *thr;
+    uint8_t *state, *hits;
+    RayList out;
+    unsigned* count;
+    int grid;
+    hipStream_t st;
+};
+using ImageStartFn = void (*)(const ImageStartArgs& a, const void* src);
+int image_forward_from(drt_scene* s, const double* d_verts, const ImageCall& call, bool keep_tape, hipStream_t st, const char* who, ImageStartFn start,
+                       const void* src);
+
+// The workspace of the loss calls behind drt_scene::image_loss_ws (drt_image_loss.hip; drt_image_views.hip shares the pixel seeds), and its
+// growth to n_seed doubles of pixel seeds and n_cam doubles of camera-ray seeds (0: none wanted) -- never inside a stream capture.
+struct ImageLossWs {
+    int64_t cap = 0;               // doubles of g_c
+    double* g_c = nullptr;         // [n_pix, C] of the band in flight
+    int64_t seed_cap = 0;          // doubles of seeds
+    double* seeds = nullptr;       // [2, n, 3] of the band in flight: the camera-ray seeds of drt_render_image_loss_camera
+};
+int ensure_image_loss_ws(drt_scene* s, int64_t n_seed, int64_t n_cam, hipStream_t st, const char* who);
+
+constexpr int kImageLossBpc = 4;           // blocks per CU of the adjoint without the table (registers bound it: DESIGN.md 10.3)
+
 // Defined in drt_image_screen.hip: k_image_screen_bwd on `st` over the pixels of the band, behind image_forward and the resolve kernel
 // of the loss, whose pixel seeds g_c [n_pix, C] it reads.  d_grad_screen (nine accumulators: p0, eu, ev) and d_grad_texture
 // ([tex_h, tex_w, C] accumulators, padded to a multiple of three values) are accumulated into; one of them may be null.

@@ -207,6 +207,7 @@ struct drt_scene {
     bool built = false;
     void* paths_ws = nullptr;      // ray lists and counters of drt_render_paths_forward (drt_paths.hip), allocated on first use
     void* image_loss_ws = nullptr; // pixel seeds of drt_render_image_loss (drt_image_loss.hip), allocated on first use
+    void* image_views = nullptr;   // the view tables made for this scene (drt_image_views.hip), a list: freed with the scene
 };
 
 
@@ -224,6 +225,8 @@ int launch_raster(drt_scene* s, drt_scene::Sub& w, hipStream_t st, const double*
 void paths_free(drt_scene* s);
 // defined in drt_image_loss.hip
 void image_loss_free(drt_scene* s);
+// defined in drt_image_views.hip
+void image_views_free(drt_scene* s);
 
 // defined in drt_api.hip
 int ensure_slow_stack(drt_scene* s, hipStream_t st);

@@ -890,6 +890,53 @@ class _ImageLossFused(torch.autograd.Function):
         return g_v, g_ior[0], g_ior[1], None, None, None, None, None, None, None
 
 
+def enqueue_image_views_term(scene, vertices, binding, view_ids, texture, law, supersample, fresnel, void, invalid, ior, loss_ptr, grad_ptr,
+                             grad_ior_ptr=None, count_ptr=None, bands=None):
+    """Enqueues the photometric image term of the listed views of ``binding`` (a ``render.ImageViews``) -- the SUM over ``view_ids`` of one
+    view's loss and d loss / d vertices (unit seed), as one forward wavefront and one adjoint pass per band -- on the current stream; the
+    one place that packs the arguments of drt_render_image_loss_views.  ``law``: a normalised law tuple (K, tir[, refraction]);
+    ``texture``: a contiguous float32 device tensor [Th, Tw, C]; ``void`` / ``invalid``: float64 numpy arrays of C values; ``ior``:
+    (interior, exterior) floats; ``bands``: rows [r0, r1) of the tall image of ``len(view_ids) * H`` rows (``render.plan_bands``), the
+    whole of it without.  ``loss_ptr`` / ``grad_ptr`` / ``grad_ior_ptr`` / ``count_ptr`` are raw device addresses the kernels ADD into
+    (float64, or fixed-point cells in deterministic mode; int64 count); all but the first may be None.  Nothing is checked here but what
+    the library checks.  The caller is inside ``_on(device)``.  Returns what the enqueued kernels read, for the caller to keep alive."""
+    ids = (ctypes.c_int * len(view_ids))(*view_ids)
+    flags = _law_flags(law[1], law[2] if len(law) > 2 else "reference")
+    for r0, r1 in (bands if bands is not None else [(0, len(view_ids) * binding.height)]):
+        _lib.check(_lib.lib().drt_render_image_loss_views(
+            scene.optix_mesh._h, vertices.data_ptr(), binding._h, ids, len(view_ids), r0, r1, supersample, ior[0], ior[1], law[0], flags, int(fresnel),
+            texture.data_ptr(), texture.shape[0], texture.shape[1], texture.shape[2], void.ctypes.data, invalid.ctypes.data, binding.targets.data_ptr(),
+            _lib.ptr(binding.weights), loss_ptr, grad_ptr, grad_ior_ptr, count_ptr, _stream()))
+    return [vertices, texture, binding]
+
+
+class _ImageLossViewsFused(torch.autograd.Function):
+    """_ImageLossFused over several views of a binding (drt_render_image_loss_views): unit seed in the forward, scaling
+    in the backward, the deterministic sink honoured; ``out`` receives the count."""
+
+    @staticmethod
+    def forward(ctx, vertices, ior_int, ior_ext, scene, binding, a, ior, tex, out):
+        v = _f64c(vertices.detach(), "vertices")
+        dev = v.device
+        loss = det.scalar(dev)
+        grad_v = det.acc(v) if a["vertices"] else None
+        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=dev))
+        count = torch.zeros((), dtype=torch.int64, device=dev)
+        law = (a["max_bounces"], "reflect" if a["law_flags"] & 1 else "drop", "snell" if a["law_flags"] & 2 else "reference")
+        with _on(dev):
+            enqueue_image_views_term(scene, v, binding, a["ids"], tex, law, a["supersample"], a["fresnel"], a["void"], a["invalid"], ior, loss.data_ptr(),
+                                     _lib.ptr(grad_v), grad_ior.data_ptr(), count.data_ptr(), a["bands"])
+        out["count"] = count
+        ctx.ior_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
+        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
+        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v), det.value(grad_ior, torch.empty(2, dtype=torch.float64)))
+        return det.value(loss)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        return _ImageLossFused.backward(ctx, g_loss)[:3] + (None,) * 6
+
+
 class _ImageLossScreenFused(torch.autograd.Function):
     """_ImageLossFused that also differentiates the screen's pose and the texture (drt_render_image_loss_screen):
     ``screen_param`` / ``texture_param`` stand for the tensors autograd tracks (or None); ``a["screen"]`` and ``tex`` carry their values.
@@ -1300,6 +1347,39 @@ class Scene(StepwiseMixin):
             loss = _ImageLossScreenFused.apply(verts, *tracked, screen_param, texture_param, self, a, ior, tex, tgt, wgt, out)
         self.last_image_count = out["count"]
         return (loss, out["image"]) if a["want_image"] else loss
+
+    def bind_image_views(self, cameras, height, width, screens, targets, weights=None):
+        """A handle for the views of a capture of photographs (``render.ImageViews``) for ``image_loss_views_fused``: ``cameras`` a list of
+        ``camera_M`` tuples, ``screens`` a list of ``render.Screen`` (one per camera), ``targets`` ``[n, height, width(, C)]`` float32, or
+        uint8 read as value / 255, ``weights`` float32 ``[n, height, width]`` or None; numpy or device tensors.  The cameras and screens
+        go to a device table once; the target and weight stacks stay resident.  Every argument error is raised before the device is
+        touched (``render.check_image_views_args``)."""
+        from . import render as _render
+        return _render.ImageViews(self, _render.check_image_views_args(cameras, height, width, screens, targets, weights))
+
+    def image_loss_views_fused(self, binding, view_ids, texture, *, ior_int=None, ior_ext=None, vertices=True, supersample=1, max_bounces=2,
+                               tir="drop", refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22):
+        """The SUM over ``view_ids`` (1..16 views of ``binding``, repeats allowed) of ``image_loss_fused`` of each view against its target
+        (and weight plane) of the binding -- loss, vertex gradient, IOR partials, ``last_image_count`` -- evaluated as ONE forward
+        wavefront and ONE adjoint pass instead of one chain of launches per view (drt_render_image_loss_views).  The views
+        share ``texture``, the law and band keywords, the fills and the IORs, all as in ``image_loss_fused``; the listed views are stacked
+        into an image of ``len(view_ids) * H`` rows, which is evaluated in bands of at most ``max_samples`` samples (a band may straddle
+        a view border) into one set of accumulators.  No image output and no screen, texture or camera gradients:
+        ``image_loss_fused`` has those."""
+        from . import render as _render
+        a = _render.check_image_views_law(binding, view_ids, texture, ior_int, ior_ext, vertices, supersample, max_bounces, tir, refraction, fresnel,
+                                          void, invalid, max_samples)
+        if binding.scene is not self:
+            raise ValueError("binding was made by another scene's bind_image_views")
+        given = [intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext]
+        ior = tuple(_ior_host(x, name) for x, name in zip(given, ("ior_int", "ior_ext")))
+        tracked = tuple(x if isinstance(x, torch.Tensor) else None for x in given)
+        with _on(self._dev):
+            tex = torch.as_tensor(a["texture"], device=self._dev).to(torch.float32).contiguous()
+        out = {}
+        loss = _ImageLossViewsFused.apply(self.vertices if a["vertices"] else self.vertices.detach(), *tracked, self, binding, a, ior, tex, out)
+        self.last_image_count = out["count"]
+        return loss
 
     @staticmethod
     def _check_law(max_bounces, tir, refraction):

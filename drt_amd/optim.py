@@ -28,7 +28,7 @@ import torch
 from . import diffrender as Render
 from . import dist as ddist
 from . import mesh_io, views
-from .captured_data import Data, Data_Pointgray, Data_Redmi, SyntheticData, get_data  # noqa: F401  (reference optim.py:7, 132-143)
+from .captured_data import Data, Data_Pointgray, Data_Redmi, PhotoData, SyntheticData, SyntheticPhotoData, get_data  # noqa: F401  (reference optim.py:7, 132-143)
 
 Float = torch.float64
 
@@ -402,10 +402,7 @@ class FusedIteration:
             main = torch.cuda.current_stream()
             if self.side is not None:
                 self.side.wait_stream(main)
-            keep = []
-            for v in ray_ids:
-                target, valid, _, origin, ray_dir, _ = data.get_view(v)
-                keep += Render.enqueue_ray_term(scene, vertices, origin, ray_dir, target, valid, self.law, l_ptr[0], g_ptr[0])
+            keep = self._enqueue_first_term(vertices, ray_ids)
             with torch.cuda.stream(self.side) if self.side is not None else torch.no_grad():
                 # (the smoothness term first: it needs no tree, so it runs while the build finishes; the silhouette probes wait for the tree.
                 # On one rank only: the sum over ranks is the term itself, not world times it)
@@ -421,7 +418,7 @@ class FusedIteration:
                 main.wait_stream(self.side)
             # 3. the tail: d total / d vertices (= d total / d parameter) = the weighted sum of the three terms' gradients, limit_hook,
             # SGD(nesterov) -- one kernel, or two around the exchange
-            w = sharded_loss_weights(hp, data.resy, scene.mean_len, self.k)
+            w = self._weights()
             if self._w is None or self._w[0] != w:
                 self._w = (w, torch.tensor(w, dtype=Float, device=dev))
             wv = self._w[1]
@@ -444,6 +441,19 @@ class FusedIteration:
             self.first = False
             self._vertices, self._keep = vertices, keep      # (alive until the next step: kernels enqueued above read them)
         return self.total, self.losses
+
+    def _enqueue_first_term(self, vertices, ray_ids):
+        """Enqueues the term of slot 0 of the accumulator block for the drawn views -- here the refraction term, one call per view -- on
+        the current stream; returns what the enqueued kernels read."""
+        keep = []
+        for v in ray_ids:
+            target, valid, _, origin, ray_dir, _ = self.data.get_view(v)
+            keep += Render.enqueue_ray_term(self.scene, vertices, origin, ray_dir, target, valid, self.law, self._l_ptr[0], self._g_ptr[0])
+        return keep
+
+    def _weights(self):
+        """The weights of the block's three terms in this iteration."""
+        return sharded_loss_weights(self.hp, self.data.resy, self.scene.mean_len, self.k)
 
     def _exchange(self, t):
         """The iteration's one collective (a sum over ranks; nothing to do for a single process)."""
@@ -484,6 +494,95 @@ class ShardedIteration(FusedIteration):
 
     def __init__(self, scene, data, HyperParams, lr, views_per_step=1, concurrent=True, path_law=None, schedule=None):
         self._init(scene, data, HyperParams, lr, views_per_step, concurrent, path_law, schedule)
+
+
+class PhotoIteration(FusedIteration):
+    """FusedIteration for a capture of plain photographs (captured_data.PhotoData): slot 0 of the accumulator block, where the
+    refraction term goes, holds the photometric image term of ``views_per_step`` drawn views, evaluated as ONE forward wavefront and ONE
+    adjoint pass (diffrender.enqueue_image_views_term) with the weight ``HyperParams["image_w"] / (views_per_step H W)``
+    -- the mean squared residual per pixel.  The silhouette and smoothness terms, the side stream and the tail are FusedIteration's.
+    ``path_law`` = (max_bounces, tir[, refraction]), ``fresnel`` and ``supersample`` are the image's law (``Scene.render_image``);
+    ``HyperParams["IOR"]`` is the object's index of refraction.  One process only."""
+
+    def __init__(self, scene, data, HyperParams, lr, views_per_step=8, path_law=(6, "reflect", "snell"), fresnel=True, supersample=1, concurrent=True,
+                 schedule=None, max_samples=1 << 22):
+        import torch.distributed as tdist
+        if tdist.is_available() and tdist.is_initialized():
+            raise NotImplementedError("PhotoIteration runs in one process: under an initialised torch.distributed group the photometric term "
+                                      "has no exchange (optimize_sharded shards the refraction term of captures with correspondences)")
+        from . import render
+        hp = dict(HyperParams)
+        hp.setdefault("ray_w", 0)
+        if "image_w" not in hp:
+            raise ValueError("PhotoIteration needs HyperParams['image_w'], the weight of the photometric term")
+        k = render._int(views_per_step, "views_per_step")
+        if not 1 <= k <= render.MAX_VIEWS_PER_CALL:
+            raise ValueError(f"views_per_step must be in 1..{render.MAX_VIEWS_PER_CALL}, got {k}")
+        law = path_law_keyword(path_law, hp, "PhotoIteration") or (2, "drop")
+        self.image_law = (tuple(law) + ("reference",))[:3]
+        if not isinstance(fresnel, (bool, np.bool_)):
+            raise ValueError(f"fresnel must be True or False, got {fresnel!r}")
+        self.fresnel, self.supersample = bool(fresnel), supersample
+        self.bands_of = lambda n: render.plan_bands(n * data.resy, data.resx, supersample, max_samples)
+        self._init(scene, data, hp, lr, k, concurrent, None, schedule)
+        self.binding = data.binding(scene)
+        dev = scene.vertices.device
+        with torch.cuda.device(dev):
+            self.texture = torch.as_tensor(render.check_texture(data.texture), device=dev).to(torch.float32).contiguous()
+        c = self.binding.channels
+        self.fills = (render._fill(getattr(data, "void", 0.0), c, "void"), render._fill(getattr(data, "invalid", 0.0), c, "invalid"))
+        self.ior = (Render._ior_host(hp["IOR"], "HyperParams['IOR']"), Render._ior_host(Render.extIOR, "extIOR"))
+        self.last_views = []
+
+    def draw(self):
+        """(image view ids, silhouette view ids) of this iteration, from the capture's two generators."""
+        hp = self.hp
+        image = [next(self.ray_view) for _ in range(self.k)] if hp["image_w"] != 0 else []
+        silh = [next(self.silh_view) for _ in range(self.N_SILHOUETTE_VIEWS)] if hp["vh_w"] != 0 else []
+        return image, silh
+
+    def _enqueue_first_term(self, vertices, image_ids):
+        self.last_views = list(image_ids)
+        if not image_ids:
+            return []
+        return Render.enqueue_image_views_term(self.scene, vertices, self.binding, image_ids, self.texture, self.image_law, self.supersample, self.fresnel,
+                                               *self.fills, self.ior, self._l_ptr[0], self._g_ptr[0], bands=self.bands_of(len(image_ids)))
+
+    def _weights(self):
+        hp, data = self.hp, self.data
+        _, w_vh, w_sm = loss_weights(hp, data.resy, self.scene.mean_len)
+        return hp["image_w"] / (self.k * data.resy * data.resx), w_vh, w_sm
+
+
+def optimize_photometric(scene, data, HyperParams, views_per_step=8, remesh="isotropic", output=True, path_law=(6, "reflect", "snell"), fresnel=True,
+                         supersample=1):
+    """The pass / iteration loop of ``optimize_sharded`` on one rank with PhotoIteration steps: fits ``scene``'s mesh to the photographs of
+    ``data`` (captured_data.PhotoData) under ``HyperParams`` (``image_w`` in the place of ``ray_w``; the other keys as in ``optimize``).
+    ``remesh`` as in ``optimize``.  Returns (scene, history, stats): history = the weighted loss every 100 iterations, stats the passes,
+    iterations and ``step_seconds`` (the iterations without the remesh, device-synchronised at the end of each pass)."""
+    remesh = resolve_remesh(remesh)
+    hp = dict(HyperParams)
+    hp.setdefault("ray_w", 0)
+    check_loop_config(hp, None, "optimize_photometric", one_pass=True, loop=True)
+    Render.intIOR = hp["IOR"]
+    Render.resy, Render.resx = data.resy, data.resx
+    schedule = (data.ray_view_generator(), data.silh_view_generator())      # one view schedule across passes
+    stats = {"views_per_step": int(views_per_step), "passes": 0, "iterations": 0, "step_seconds": 0.0}
+    history = []
+    for i_pass, remesh_len, lr in pass_schedule(hp):
+        if output:
+            print(f"remesh_len {remesh_len:g} lr {lr:g}")
+        if remesh is not None:
+            remesh(scene, remesh_len)
+        stepper = PhotoIteration(scene, data, hp, lr, views_per_step, path_law=path_law, fresnel=fresnel, supersample=supersample, schedule=schedule)
+        torch.cuda.synchronize(scene.vertices.device)
+        t0 = time.perf_counter()
+        run_steps(stepper, hp["Iters"], history, output)
+        torch.cuda.synchronize(scene.vertices.device)
+        stats["step_seconds"] += time.perf_counter() - t0
+        stats["iterations"] += hp["Iters"]
+        stats["passes"] += 1
+    return scene, history, stats
 
 
 def pass_schedule(hp):

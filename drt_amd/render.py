@@ -423,6 +423,137 @@ def check_image_loss_args(camera_M, height, width, screen, texture, target, weig
     return a
 
 
+# ---- several views in one call (Scene.bind_image_views / image_loss_views_fused) ---------------------------------------
+MAX_VIEWS_PER_CALL = 16
+
+
+def _camera21(camera_M, name):
+    try:
+        n_cam = len(camera_M)
+    except TypeError:
+        raise ValueError(f"{name} must be the tuple (R, K, R^-1, K^-1), got {type(camera_M).__name__}") from None
+    if n_cam != 4:
+        raise ValueError(f"{name} must be the tuple (R, K, R^-1, K^-1), got {n_cam} entries")
+    rinv, kinv = _mat(camera_M[2], (4, 4), f"{name}[2] (R^-1)"), _mat(camera_M[3], (3, 3), f"{name}[3] (K^-1)")
+    return np.concatenate([kinv.reshape(-1), rinv[:3, :].reshape(-1)])
+
+
+def check_image_views_args(cameras, height, width, screens, targets, weights=None):
+    """Every argument check of ``Scene.bind_image_views``, none of which needs a device.  Returns a dict: n, height, width, channels,
+    cameras (float64 [n, 21]: K^-1, then the top 3 x 4 of R^-1, per view), screens (float64 [n, 9]), targets (float32 [n, H, W, C];
+    uint8 is read as value / 255; [n, H, W] is one channel) and weights (float32 [n, H, W] or None) -- numpy arrays made contiguous, or
+    device tensors as they are after the shape and dtype checks."""
+    height, width = _int(height, "height"), _int(width, "width")
+    if height < 1 or width < 1:
+        raise ValueError(f"height, width must be at least 1, got {(height, width)}")
+    try:
+        cameras, screens = list(cameras), list(screens)
+    except TypeError:
+        raise ValueError("cameras must be a list of camera_M tuples and screens a list of Screen objects") from None
+    n = len(cameras)
+    if n < 1:
+        raise ValueError("cameras must list at least one view")
+    if len(screens) != n:
+        raise ValueError(f"screens must list one Screen per camera: {len(screens)} screens for {n} cameras")
+    cams = np.ascontiguousarray(np.stack([_camera21(c, f"cameras[{k}]") for k, c in enumerate(cameras)]), dtype=np.float64)
+    rows = []
+    for k, sc in enumerate(screens):
+        if not isinstance(sc, Screen):
+            raise ValueError(f"screens[{k}] must be a drt_amd.render.Screen, got {type(sc).__name__}")
+        try:
+            rows.append(Screen(sc.p0, sc.eu, sc.ev).packed())          # (checked again: the attributes of a Screen can be assigned)
+        except ValueError as e:
+            raise ValueError(f"screens[{k}]: {e}") from None
+    if targets is None or not (hasattr(targets, "shape") and hasattr(targets, "dtype")):
+        try:
+            targets = None if targets is None else np.asarray(targets)
+        except (TypeError, ValueError):
+            targets = None
+        if targets is None or targets.dtype == object:
+            raise ValueError(f"targets must be an array of shape ({n}, {height}, {width}, C)")
+    if len(targets.shape) == 3:
+        targets = targets[:, :, :, None]
+    if len(targets.shape) != 4 or targets.shape[3] not in (1, 3):
+        raise ValueError(f"targets must be [n, H, W], [n, H, W, 1] or [n, H, W, 3], got shape {tuple(targets.shape)}")
+    channels = int(targets.shape[3])
+    return dict(n=n, height=height, width=width, channels=channels, cameras=cams, screens=np.ascontiguousarray(np.stack(rows), dtype=np.float64),
+                targets=_plane(targets, (n, height, width, channels), "targets", True),
+                weights=None if weights is None else _plane(weights, (n, height, width), "weights", False))
+
+
+def check_view_ids(view_ids, n_views):
+    """The view list of one ``image_loss_views_fused`` call as a list of ints: 1 .. 16 ids, each in [0, n_views), repeats allowed."""
+    try:
+        ids = [_int(v, "view_ids entry") for v in view_ids]
+    except TypeError:
+        raise ValueError(f"view_ids must be a list of view numbers, got {view_ids!r}") from None
+    if not 1 <= len(ids) <= MAX_VIEWS_PER_CALL:
+        raise ValueError(f"view_ids must list 1..{MAX_VIEWS_PER_CALL} views, got {len(ids)}")
+    for v in ids:
+        if not 0 <= v < n_views:
+            raise ValueError(f"view_ids: view {v} is outside the binding's views 0..{n_views - 1}")
+    return ids
+
+
+def check_image_views_law(binding, view_ids, texture, ior_int=None, ior_ext=None, vertices=True, supersample=1, max_bounces=2, tir="drop",
+                          refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22):
+    """Every argument check of ``Scene.image_loss_views_fused`` behind the binding: ``check_render_args``' dict for the tall image of
+    ``len(view_ids) * H`` rows (camera and screen are the first listed view's and stand for nothing), plus ids, ior and vertices."""
+    if not isinstance(binding, ImageViews):
+        raise ValueError(f"binding must be a drt_amd.render.ImageViews (Scene.bind_image_views), got {type(binding).__name__}")
+    ids = check_view_ids(view_ids, binding.n)
+    cam = binding.args["cameras"][ids[0]]
+    rinv = np.concatenate([cam[9:].reshape(3, 4), np.array([[0.0, 0.0, 0.0, 1.0]])])
+    sc = binding.args["screens"][ids[0]]
+    a = check_render_args((None, None, rinv, cam[:9].reshape(3, 3)), len(ids) * binding.height, binding.width, Screen(sc[0:3], sc[3:6], sc[6:9]), texture,
+                          supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples)
+    if a["channels"] != binding.channels:
+        raise ValueError(f"texture has {a['channels']} channels, the binding's targets have {binding.channels}")
+    a["ids"] = ids
+    a["ior"] = (_ior_arg(ior_int, "ior_int"), _ior_arg(ior_ext, "ior_ext"))
+    if not isinstance(vertices, (bool, np.bool_)):
+        raise ValueError(f"vertices must be True or False, got {vertices!r}")
+    a["vertices"] = bool(vertices)
+    return a
+
+
+class ImageViews:
+    """The views of a capture for ``Scene.image_loss_views_fused``, made by ``Scene.bind_image_views``: the device table of cameras and
+    screens (drt_image_views_create; owned here, freed with this object or with the scene, whichever goes first) and the resident
+    target and weight stacks.  ``n`` views of ``height`` x ``width`` pixels and ``channels`` channels."""
+
+    def __init__(self, scene, args):
+        import ctypes
+        import torch
+        from . import _lib
+        from .optix_mesh import _on
+        self.scene, self.args = scene, args
+        self.n, self.height, self.width, self.channels = args["n"], args["height"], args["width"], args["channels"]
+        dev = scene._dev
+        h = ctypes.c_void_p()
+        with _on(dev):
+            t = torch.as_tensor(args["targets"], device=dev)
+            self.targets = (t.to(torch.float32) / 255.0 if t.dtype == torch.uint8 else t).reshape(self.n, self.height, self.width, self.channels).contiguous()
+            self.weights = None if args["weights"] is None else torch.as_tensor(args["weights"], device=dev).contiguous()
+            _lib.check(_lib.lib().drt_image_views_create(scene.optix_mesh._h, self.n, args["cameras"].ctypes.data, args["screens"].ctypes.data,
+                                                         self.height, self.width, ctypes.byref(h)))
+        self._h = h.value
+        self._mesh = scene.optix_mesh          # (the scene handle outlives the table)
+
+    def release(self):
+        """Frees the device table now; the object cannot be used afterwards."""
+        h, self._h = self._h, None
+        if h and getattr(self._mesh, "_h", None):
+            from . import _lib
+            _lib.lib().drt_image_views_destroy(h)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------------------
 def _background(spec, tex):
     if spec == "checker":

@@ -35,7 +35,8 @@ const char* drt_last_error(void);
 int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_render_paths_forward / _backward; 4: drt_render_paths_ray_loss_fused;
                             * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused;
                             * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image; 9: drt_render_image_loss;
-                            * 10: drt_route_counts; 11: drt_render_image_loss_screen; 12: drt_render_image_loss_camera */
+                            * 10: drt_route_counts; 11: drt_render_image_loss_screen; 12: drt_render_image_loss_camera;
+                            * 13: drt_image_views_create / drt_render_image_loss_views */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -729,6 +730,33 @@ int drt_render_image_loss_camera(drt_scene_t* s, const double* d_verts, const do
                                  const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
                                  const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
                                  int64_t* d_count, double* d_grad_screen, double* d_grad_texture, double* d_grad_camera, void* stream);
+
+/* ---- the image term of several views in one call (csrc/drt_image_views.h states the mapping) -----------------------
+ * A view table holds the cameras and screens of a capture whose views all have height x width pixels: cameras21 [n_views, 21] and
+ * screens9 [n_views, 9], host arrays in drt_render_image's layouts.  drt_image_views_create checks every screen as drt_render_image
+ * checks its one (DRT_E_INVALID names the row), uploads the table once (a synchronous copy: not inside a stream capture) and returns a
+ * handle.  drt_image_views_destroy frees it; a table still alive when its scene is destroyed is freed with the scene, and its handle
+ * must not be used afterwards. */
+typedef struct drt_image_views drt_image_views_t;
+ /* (drt_image_views_check: the argument checks alone -- host only, no device call) */
+int drt_image_views_check(int n_views, const double* cameras21, const double* screens9, int height, int width);
+int drt_image_views_create(drt_scene_t* s, int n_views, const double* cameras21, const double* screens9, int height, int width, drt_image_views_t** out);
+void drt_image_views_destroy(drt_image_views_t* views);
+/* The SUM over the listed views view_ids[0 .. k) (a HOST array; 1 <= k <= 16, each id in [0, n_views), repeats allowed) of what
+ * drt_render_image_loss adds for each of them: *d_loss, d_grad_verts, d_grad_ior, *d_count, all accumulated into, the last three
+ * nullable -- as ONE forward wavefront and ONE adjoint pass.  The listed views are stacked into a tall image of k * height rows (row r is
+ * row r % height of list slot r / height); the call covers its rows [r0, r1), which may straddle a view border, and bands add into the
+ * same accumulators.  Path law, supersampling, texture, fills and IORs are shared by the views; d_targets float32 [n_views, height,
+ * width, channels] and d_weights float32 [n_views, height, width] (may be NULL) are the capture's stacks, indexed by view id.  The ids
+ * reach the kernels by value: nothing is copied per call, and the call can be captured once a call of its size has grown the workspace
+ * (drt_render_image_loss's, shared with it).  No image output and no screen, texture or camera gradients: those are
+ * drt_render_image_loss_camera's.  Everything is enqueued on `stream`, nothing is read back.  DRT_E_INVALID (nothing enqueued, no output
+ * touched): a NULL table or one of another scene, a bad k or id, then everything drt_render_image_loss refuses, with [r0, r1) inside
+ * [0, k * height) and at most 2^31 - 1 samples. */
+int drt_render_image_loss_views(drt_scene_t* s, const double* d_verts, const drt_image_views_t* views, const int* view_ids, int k, int r0, int r1,
+                                int supersample, double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const float* d_texture,
+                                int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid, const float* d_targets,
+                                const float* d_weights, double* d_loss, double* d_grad_verts, double* d_grad_ior, int64_t* d_count, void* stream);
 
 /* ---- measurement (bench.py's live per-kernel timing) --------------------------------------------
  * When enabled (on = 1; on = 2 additionally collects the traversal statistics below, which perturbs
