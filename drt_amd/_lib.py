@@ -54,6 +54,8 @@ SIGNATURES = {
     "drt_outputs_clean": (_c.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P]),
     "drt_outputs_cancel": (_c.c_int, [_P]),
     "drt_render_seed": (_c.c_int, [_P, _P, _I64]),
+    "drt_render_loss_arm": (_c.c_int, [_P, _P, _P, _P, _P, _I64]),
+    "drt_render_loss_taken": (_c.c_int, [_P]),
     "drt_ray_loss_listed_grad": (_c.c_int, [_P, _P, _P, _P, _I64, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drt_ray_loss_listed_grad_split": (_c.c_int, [_P, _P, _P, _P, _I64, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drt_scale_rows3": (_c.c_int, [_P, _P, _P, _P, _P]),

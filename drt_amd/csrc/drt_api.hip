@@ -151,6 +151,7 @@ int drt_create(int device, drt_scene_t** out) {
     if (const char* ev = getenv("DRT_STREAMS")) { const int v = atoi(ev); if (v >= 1 && v <= drt_scene::kMaxSub) s->n_sub = v; }
     if (const char* ev = getenv("DRT_RASTER")) s->use_raster = atoi(ev) != 0;
     if (const char* ev = getenv("DRT_HIT_SEED")) s->hit_seed = atoi(ev) != 0;
+    if (const char* ev = getenv("DRT_ARM_FINISH_BESIDE")) s->arm_finish_beside = atoi(ev) != 0;
     if (const char* ev = getenv("DRT_SEED_TILED")) s->seed_tiled = atoi(ev) != 0;
     if (const char* ev = getenv("DRT_GRID_CANARY")) s->grid_canary = atoi(ev) != 0;
     if (const char* ev = getenv("DRT_FILL_OVERLAP")) s->fill_overlap = atoi(ev) != 0;
@@ -161,6 +162,7 @@ int drt_create(int device, drt_scene_t** out) {
         drt_scene::Sub& w = s->sub[k];
         e = hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&w.done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&w.tail, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&w.fill_fork, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&w.fill_join, hipEventDisableTiming);
         if (e == hipSuccess) e = hipMalloc(&w.qcount, sizeof(unsigned) * kQCount);
@@ -216,6 +218,7 @@ void drt_destroy(drt_scene_t* s) {
         if (w.done) (void)hipEventDestroy(w.done);
         if (w.fill_fork) (void)hipEventDestroy(w.fill_fork);
         if (w.fill_join) (void)hipEventDestroy(w.fill_join);
+        if (w.tail) (void)hipEventDestroy(w.tail);
         if (w.stream) (void)hipStreamDestroy(w.stream);
     }
     image_views_free(s);

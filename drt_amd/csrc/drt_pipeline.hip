@@ -1127,6 +1127,31 @@ __global__ void __launch_bounds__(256) k_loss_bwd_listed(PathCtx c, const double
     acc.flush(loss);
 }
 
+// The same pass for a render call armed with its loss (drt_render_loss_arm), over ONE sub-batch's list R2 behind its last traversal, as
+// k_loss_bwd_fused walks it: the entries the occlusion test left alone are the paths the sub-batch completed -- exactly its segment of the
+// list of completed paths.  Every pointer is the sub-batch's own (offset by its first ray), indices are R2's local ones.  The drop-in
+// route traces rays whose target is invalid (the fused one culls them), so valid[i] is honoured here.
+template <bool DET>
+__global__ void __launch_bounds__(256) k_loss_bwd_armed(PathCtx c, const double* __restrict__ origin, const double* __restrict__ dir,
+                                                        const double* __restrict__ screen_pixel, const uint8_t* __restrict__ valid,
+                                                        const int32_t* __restrict__ face1, const int32_t* __restrict__ face2, Pipe p,
+                                                        double* loss, double* grad_verts) {
+    const unsigned n2 = p.count[2];
+    LossAcc<DET> acc;
+    sink_pass<DET, kBwdBatch>(n2, grad_verts, [&](unsigned k, const PathSink<DET>& add) {
+        if (p.r2.face[k] >= 0) return;   // occluded exit ray
+        const int64_t i = p.r2.idx[k];
+        if (!valid[i]) return;
+        int32_t vid1[3], vid2[3];
+        Bounce b1, b2;
+        path_recompute(c, load_d3(origin, i), load_d3(dir, i), face1[i], face2[i], b1, b2, vid1, vid2);
+        d3 g_dir;
+        acc.add(ray_loss_term(b2.new_o, b2.wt, load_d3(screen_pixel, i), g_dir));
+        path_backward(b1, b2, vid1, vid2, d3{0.0, 0.0, 0.0}, g_dir, add);
+    });
+    acc.flush(loss);
+}
+
 __global__ void k_prof_counts(const unsigned* __restrict__ qcount, unsigned long long n_rays, unsigned long long* __restrict__ tot, int fused, int raster, bool mega) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     // sub-batches on different streams may report concurrently: atomics
@@ -1456,6 +1481,13 @@ static int32_t* take_seed(drt_scene* s, int64_t n_rays) {
     s->seed = drt_scene::Seed{};
     return p;
 }
+// The loss registered for the next render call (drt_render_loss_arm): one shot too, and empty for a call of another size.
+static drt_scene::LossArm take_loss_arm(drt_scene* s, int64_t n_rays) {
+    const drt_scene::LossArm a = s->loss_arm.loss && s->loss_arm.n == n_rays ? s->loss_arm : drt_scene::LossArm{};
+    s->loss_arm = drt_scene::LossArm{};
+    s->loss_taken = false;
+    return a;
+}
 
 extern "C" {
 
@@ -1464,6 +1496,17 @@ int drt_render_seed(drt_scene_t* s, int32_t* d_seed_face2, int64_t n_rays) {
     if (n_rays < 0 || (d_seed_face2 == nullptr && n_rays != 0)) return fail(DRT_E_INVALID, "bad seed buffer");
     s->seed = drt_scene::Seed{d_seed_face2, n_rays};
     return DRT_OK;
+}
+
+int drt_render_loss_arm(drt_scene_t* s, const double* d_screen_pixel, const uint8_t* d_valid, double* d_loss, double* d_grad_verts, int64_t n_rays) {
+    CHECK_SCENE(s);
+    if (n_rays <= 0 || !d_screen_pixel || !d_valid || !d_loss || !d_grad_verts) return fail(DRT_E_INVALID, "drt_render_loss_arm: bad arguments");
+    s->loss_arm = drt_scene::LossArm{d_screen_pixel, d_valid, d_loss, d_grad_verts, n_rays};
+    return DRT_OK;
+}
+
+int drt_render_loss_taken(drt_scene_t* s) {
+    return s && s->loss_taken ? 1 : 0;
 }
 
 static int flush_clean(drt_scene* s, hipStream_t st);
@@ -1490,6 +1533,8 @@ int drt_render_forward(drt_scene_t* s, const double* d_verts, const double* d_or
         s->n_prefill = 0;
         s->seed = drt_scene::Seed{};
         s->segs = drt_scene::Segs{};
+        s->loss_arm = drt_scene::LossArm{};
+        s->loss_taken = false;      // (accumulators a failed call half filled are the caller's to discard)
     }
     return rc;
 }
@@ -1498,6 +1543,7 @@ static int render_forward_impl(drt_scene_t* s, const double* d_verts, const doub
                                int32_t* d_face1, int32_t* d_face2, int32_t* d_valid_idx, int64_t* d_n_valid, int tile_w, int tile_h,
                                int grid_mode, void* d_grid_cache, void* stream) {
     CHECK_BUILT(s);
+    drt_scene::LossArm arm = take_loss_arm(s, n_rays);       // (in front of every early return: an arm never outlives the call behind it)
     if (n_rays < 0 || n_rays > INT32_MAX) return fail(DRT_E_INVALID, "ray count out of range");
     hipStream_t st = (hipStream_t)stream;
     if (n_rays == 0) {
@@ -1517,6 +1563,11 @@ static int render_forward_impl(drt_scene_t* s, const double* d_verts, const doub
     grid_mode &= ~kIntMask;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cap);
+    // The armed loss (drt_render_loss_arm) is served by the whole call or declined by the whole call.  Declined: under capture (replays
+    // would add into accumulators nobody zeroes again) and when a sub-batch -- the last, smallest one decides -- would run its back
+    // half as ONE kernel, which keeps no list R2 to walk.
+    if (arm.loss && (cap != hipStreamCaptureStatusNone || (s->mega_max_rays > 0 && n_rays - (pl.count - 1) * pl.size <= s->mega_max_rays)))
+        arm = drt_scene::LossArm{};
     // (while a graph is being captured the buffers zeroed ahead of time stay registered: the capturing call brings its own outputs, and
     // nothing outside the capture may be waited for inside it)
     if (s->n_prefill && (cap == hipStreamCaptureStatusNone || (s->clean.rows && s->clean.captured))) {       // buffers zeroed ahead of time (drt_prefill_zero) / offered again (drt_outputs_clean): which of this call's outputs are they?
@@ -1547,6 +1598,7 @@ static int render_forward_impl(drt_scene_t* s, const double* d_verts, const doub
     rc = fork_streams(s, st, pl.streams);
     if (rc) return rc;
     if (s->clean.rows) { rc = flush_clean(s, st); if (rc) return rc; }
+    bool finish_moved = false;      // a k_finish ran on the caller's stream: the list's segments are then NOT ordered on the internal streams
     for (int j = 0; j < pl.count; ++j) {
         drt_scene::Sub& w = s->sub[j % pl.streams];
         const int64_t b = j * pl.size;
@@ -1562,8 +1614,26 @@ static int render_forward_impl(drt_scene_t* s, const double* d_verts, const doub
                                  st, b, vlist, &finished, seed2 ? seed2 + b : nullptr);
         if (rc) return rc;
         if (!finished) {
-            StageTimer t(s, w.stream, kStageFinish);
-            k_finish<<<8 * s->n_cu, kPathBlock, 0, w.stream>>>(d_out_ori + 3 * b, d_out_dir + 3 * b, d_mask + 3 * b, d_face2 + b, p, b, vlist);
+            // An armed call's LAST sub-batch on a stream: k_finish goes to the caller's stream (idle between the fork and the join), beside the
+            // loss pass instead of in front of it -- the two write disjoint rows (below), and nothing on this internal stream reuses R2
+            // before the next call's fork, which is ordered behind the caller's stream.
+            hipStream_t fin = w.stream;
+            if (arm.loss && s->arm_finish_beside && !s->prof_serial && j + pl.streams >= pl.count) {
+                HIP_TRY(hipEventRecord(w.tail, w.stream));
+                HIP_TRY(hipStreamWaitEvent(st, w.tail, 0));
+                fin = st;
+                finish_moved = true;
+            }
+            StageTimer t(s, fin, kStageFinish);
+            k_finish<<<8 * s->n_cu, kPathBlock, 0, fin>>>(d_out_ori + 3 * b, d_out_dir + 3 * b, d_mask + 3 * b, d_face2 + b, p, b, vlist);
+        }
+        if (arm.loss) {
+            // the loss + unit-seed gradient of this sub-batch's completed paths, on its own stream: R2 stays as k_trace<any> left it until
+            // the stream's next sub-batch resets its counters, and k_finish only writes rows this pass skips (the occluded ones)
+            if (finished) return fail(DRT_E_INVALID, "armed loss: a sub-batch took the one-kernel path");      // (ruled out above)
+            StageTimer t(s, w.stream, kStageBackward);
+            DET_LAUNCH(k_loss_bwd_armed, DRT_BWD_BPC * s->n_cu, 256, w.stream, pc, d_origin + 3 * b, d_dir + 3 * b, arm.screen_pixel + 3 * b, arm.valid + b,
+                                                                 d_face1 + b, d_face2 + b, p, arm.loss, arm.grad_verts);
         }
         if (s->prof_on) k_prof_counts<<<1, 64, 0, w.stream>>>(w.qcount, (unsigned long long)n, s->prof_counts, 0, raster_on(s, n, tile_w, tile_h), finished);
     }
@@ -1574,12 +1644,14 @@ static int render_forward_impl(drt_scene_t* s, const double* d_verts, const doub
             k_join_lists<<<2 * s->n_cu, 256, 0, st>>>(d_valid_idx, s->seg_counts, j, (int64_t)j * pl.size, j + 1 == pl.count, s->vcount, d_n_valid);
         // (not while a graph is being captured: a later EAGER drt_ray_loss_listed_grad_split on the same list would start on internal stream 0
         // with no ordering against the replayed graph that fills the list)
-        if (cap == hipStreamCaptureStatusNone) s->segs = drt_scene::Segs{d_valid_idx, pl.count, 0};      // (sub-batch 0 runs on internal stream 0)
+        // (nor when segment 0 was appended on the caller's stream: internal stream 0 is not ordered behind that)
+        if (cap == hipStreamCaptureStatusNone && !finish_moved) s->segs = drt_scene::Segs{d_valid_idx, pl.count, 0};      // (sub-batch 0 runs on internal stream 0)
     } else if (d_n_valid) {
         k_store_count<<<1, 64, 0, st>>>(s->vcount, d_n_valid);
     }
     if (s->prof_on) s->prof_stream = st;
     HIP_TRY(hipGetLastError());
+    s->loss_taken = arm.loss != nullptr;
     return DRT_OK;
 }
 
@@ -1845,6 +1917,7 @@ int drt_render_ray_loss_fused(drt_scene_t* s, const double* d_verts, const doubl
     if (!d_verts || !d_origin || !d_dir || !d_screen_pixel || !d_valid || !d_loss || !d_grad_verts) return fail(DRT_E_INVALID, "null pointer argument");
     hipStream_t st = (hipStream_t)stream;
     int32_t* const seed2 = take_seed(s, n_rays);
+    (void)take_loss_arm(s, -1);       // (an arm is for a drt_render_forward: any other pipeline call drops it)
     const Plan pl = plan_call(s, n_rays, tile_w, tile_h);
     for (int k = 0; k < pl.streams; ++k) { int rc = ensure_queues(s->sub[k], pl.size, true, s->mega_max_rays > 0 && pl.size <= s->mega_max_rays); if (rc) return rc; }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;

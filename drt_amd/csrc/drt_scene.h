@@ -90,6 +90,11 @@ struct drt_scene {
     // drt_render_seed: per camera ray, the face id the refracted ray of that pixel hit in an earlier call (TraceSeed); one shot, consumed by
     // the next drt_render_forward / drt_render_ray_loss_fused of exactly `n` rays
     struct Seed { int32_t* face2 = nullptr; int64_t n = 0; } seed;
+    // drt_render_loss_arm: targets and accumulators of the ray loss of the NEXT drt_render_forward of exactly `n` rays; one shot like the
+    // seeds.  A call that takes it enqueues, per sub-batch and on that sub-batch's own stream, the loss + unit-seed vertex gradient of the
+    // paths the sub-batch completed (a walk over its list R2, in front of the join); `loss_taken` says whether the LAST render call did.
+    struct LossArm { const double* screen_pixel = nullptr; const uint8_t* valid = nullptr; double* loss = nullptr; double* grad_verts = nullptr; int64_t n = 0; } loss_arm;
+    bool loss_taken = false;
     hipStream_t build_stream = nullptr;   // the LBVH build runs here, beside the caller's next fills / projection pass
     hipEvent_t build_fork = nullptr, build_done = nullptr;
     bool build_pending = false;    // a build was enqueued on build_stream: consumers of the tree wait for build_done
@@ -125,6 +130,7 @@ struct drt_scene {
     struct Sub {
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
+        hipEvent_t tail = nullptr;                           // "the last traversal of the sub-batch is through": k_finish of an armed call's last sub-batch waits for it on the caller's stream
         hipEvent_t fill_fork = nullptr, fill_join = nullptr; // around the dense-output memsets of a DRT_GRID_TRUST call, issued beside the traversal
         int32_t* q_idx[3] = {nullptr, nullptr, nullptr};     // ray lists R0..R2: index,
         float* q_ray[3] = {nullptr, nullptr, nullptr};       //   float32 ray [cap,6],
@@ -202,6 +208,7 @@ struct drt_scene {
     bool grid_canary = true;       // DRT_GRID_CANARY=0: a trusted image is re-checked on its fixed 8x8 lattice only (k_check_views)
     unsigned canary_salt = 0;      // changes with every trusted projection pass
     bool seed_tiled = true;        // DRT_SEED_TILED=0: the seed buffer of a whole-image call is indexed by ray number instead of by 4x4-pixel tile
+    bool arm_finish_beside = true; // DRT_ARM_FINISH_BESIDE=0: k_finish of an armed call stays on the sub-batch's stream, in front of its loss pass (A/B measurement)
     bool hit_seed = true;          // DRT_HIT_SEED=0: drt_render_seed's seeds are ignored (A/B measurement)
     bool use_raster = true;        // DRT_RASTER=0: every primary ray takes the BVH path (A/B measurement)
     bool built = false;

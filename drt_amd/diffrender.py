@@ -40,7 +40,8 @@ def cache_report(reset=False):
     calls that read and verified every ray, `grid_off` calls without whole-image hints / with GRID_CACHE off, `grid_unattachable` ray tensors
     that take no attributes), output recycling (`recycle_take` calls that rendered into pooled buffers; `recycle_miss_held` the pool had an
     entry of that size but the caller still holds, or wrote, its outputs; `recycle_miss_empty` nothing pooled yet; `recycle_off_capture` inside
-    a graph capture; `recycle_off_small` below RECYCLE_MIN_RAYS), hit seeds (`seed_armed`), the one-pass K-interaction term (`paths_fused_calls`; with the IOR gradient `paths_ior_fused_calls`), and the
+    a graph capture; `recycle_off_small` below RECYCLE_MIN_RAYS), hit seeds (`seed_armed`), the loss done by the render call (`loss_armed` calls that took
+    it, `loss_arm_declined`, `loss_arm_used` ray_loss calls that issued no native call, `loss_arm_dropped` that could not use it), the one-pass K-interaction term (`paths_fused_calls`; with the IOR gradient `paths_ior_fused_calls`), and the
     switches in force."""
     out = dict(_stats)
     out["switches"] = {"GRID_CACHE": GRID_CACHE, "RECYCLE_OUTPUTS": RECYCLE_OUTPUTS, "storage_use_count_available": hasattr(torch._C, "_storage_Use_Count"),
@@ -331,8 +332,16 @@ class _OutputPool:
 SPLIT_LOSS = os.environ.get("DRT_SPLIT_LOSS", "1") != "0"
 SPLIT_LOSS_MIN_RAYS = int(os.environ.get("DRT_SPLIT_LOSS_MIN_RAYS", 1 << 25))          # below, a call is not cut into sub-batches (DRT_MIN_SUB_LOG2 = 24 per sub-batch); zeroing the accumulators
                                                                                  # in front of the render call anyway (two launches off the tail, two more in front of the fork) measured +1 % at 9 and 18 views
+# ARMED_LOSS: a render call on a RayBinding that carries targets does the loss pass ITSELF (drt_render_loss_arm): every sub-batch adds the
+# loss + unit-seed vertex gradient of the paths it completed on its own internal stream, in front of the join, and a ray_loss on the
+# call's untouched outputs with the BOUND targets issues no native call at all -- its results are `_GradLink.pre`.  Every other ray_loss
+# (other targets, outputs written in place, ...) takes the routes below with fresh accumulators, and an armed result nobody asks for is
+# dropped with the link.  Carries no work of its own: what it saves is the chain of dependent dispatches behind the join.
+ARMED_LOSS = os.environ.get("DRT_ARMED_LOSS", "1") != "0"
+ARMED_LOSS_MIN_RAYS = int(os.environ.get("DRT_ARMED_LOSS_MIN_RAYS", 1 << 24))         # measured with the arm forced on (profiles/armed_loss.txt): 18 views x 1024^2, one sub-batch,
+                                                                                     # 0.805 -> 0.784 ms; 9 views 0.664 -> 0.665, nothing either way: off below 2^24 rays
 _seen_targets = {}
-_render_seq = [0]          # render_transparent calls enqueued so far (any scene): a clock for "was complete before THAT call"
+_render_seq = [0]         # render_transparent calls enqueued so far (any scene): a clock for "was complete before THAT call"
 
 
 def _targets_seen_before(sp, valid, render_seq):
@@ -354,9 +363,23 @@ def _targets_seen_before(sp, valid, render_seq):
     return ok
 
 
+def _arm_targets(targets, n, device):
+    """(screen_pixel, valid bytes) of a RayBinding's targets when the render call can read them as they are (float64 [n, 3] and n flags,
+    contiguous, on the rays' device: the very memory ray_loss would pass on), else None -- ray_loss then reports what is wrong with them."""
+    sp, valid = targets
+    if not (isinstance(sp, torch.Tensor) and isinstance(valid, torch.Tensor)):
+        return None
+    if not (sp.dtype == torch.float64 and sp.device == device and tuple(sp.shape) == (n, 3) and sp.is_contiguous()):
+        return None
+    if not (valid.dtype in (torch.bool, torch.uint8) and valid.device == device and valid.numel() == n and valid.is_contiguous()):
+        return None
+    return sp, valid.view(torch.uint8)
+
+
 class _GradLink:
     def __init__(self):
-        self.pre = None        # (stash zeros_like(vertices), loss zeros(())) created before the render call was enqueued (SPLIT_LOSS)
+        self.armed = False     # the render call took the loss with it (ARMED_LOSS): `pre` holds the loss and the stash of the BOUND targets
+        self.pre = None       # (stash zeros_like(vertices), loss zeros(())) created before the render call was enqueued (SPLIT_LOSS)
         self.seq = 0           # _render_seq of the render call this link belongs to
         self.pending = []
         self._token = None
@@ -467,8 +490,12 @@ class _RenderTransparent(torch.autograd.Function):
             counts = tuple(_use_count(t) for t in bases)          # with nobody but these three names holding them
         face1 = torch.empty(n, dtype=torch.int32, device=o.device)
         face2 = torch.empty(n, dtype=torch.int32, device=o.device)
-        if (SPLIT_LOSS and need_bwd and not need_inputs and EAGER_LOSS_GRAD and link is not None and not capturing and n >= SPLIT_LOSS_MIN_RAYS):
-            link.pre = (det.acc(v), det.scalar(o.device))
+        arm = None
+        if need_bwd and not need_inputs and EAGER_LOSS_GRAD and link is not None and not capturing:
+            if ARMED_LOSS and link.targets is not None and n >= ARMED_LOSS_MIN_RAYS:
+                arm = _arm_targets(link.targets, n, o.device)
+            if arm is not None or (SPLIT_LOSS and n >= SPLIT_LOSS_MIN_RAYS):
+                link.pre = (det.acc(v), det.scalar(o.device))
         _render_seq[0] += 1
         if link is not None:
             link.seq = _render_seq[0]
@@ -487,10 +514,18 @@ class _RenderTransparent(torch.autograd.Function):
                     _lib.check(_lib.lib().drt_outputs_clean(om._h, bases_in[0].data_ptr(), bases_in[1].data_ptr(), bases_in[2].data_ptr(), n,
                                                             took[5].data_ptr(), took[6].data_ptr(), stream_id))
                 _arm_seed(scene.optix_mesh._h, grid, n)
+                if arm is not None:       # (registered last: only a failing drt_render_forward sits between this and its consumer, and that clears it)
+                    _lib.check(_lib.lib().drt_render_loss_arm(scene.optix_mesh._h, arm[0].data_ptr(), arm[1].data_ptr(), link.pre[1].data_ptr(),
+                                                              link.pre[0].data_ptr(), n))
                 _lib.check(_lib.lib().drt_render_forward(
                     scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), n, ior[0], ior[1],
                     out_ori.data_ptr(), out_dir.data_ptr(), mask.data_ptr(), face1.data_ptr(), face2.data_ptr(),
                     _lib.ptr(valid_idx), _lib.ptr(n_valid), *_tile_hint(n), grid[0] | (0 if DENSE_FACE_IDS else 16), _lib.ptr(grid[1]), stream_id))
+                if arm is not None:
+                    link.armed = bool(_lib.lib().drt_render_loss_taken(scene.optix_mesh._h))
+                    _stats["loss_armed" if link.armed else "loss_arm_declined"] += 1
+                    if not link.armed and not (SPLIT_LOSS and n >= SPLIT_LOSS_MIN_RAYS):
+                        link.pre = None
             except BaseException:
                 _lib.lib().drt_outputs_cancel(om._h)
                 if graph_set is not None and binding is None:      # the capture failed: the set goes back to the pool, the caller falls back to eager calls
@@ -686,14 +721,20 @@ class _RayLoss(torch.autograd.Function):
                 pre, link.pre = link.pre, None
                 bound = link.targets is not None and link.targets[0] is screen_pixel and link.targets[1] is valid
                 early = pre is not None and (bound or _targets_seen_before(screen_pixel, valid, link.seq)) and sp.data_ptr() == screen_pixel.data_ptr() and va.data_ptr() == valid.data_ptr()
-                if early:      # accumulators zeroed before the render call: the head of the list can be processed beside the pipelines (SPLIT_LOSS)
+                armed, link.armed = link.armed, False
+                if armed:      # `pre` already holds the loss and the stash of the bound targets (ARMED_LOSS): this is them, or they are of no use here
+                    early = False
+                    armed = pre is not None and bound
+                    _stats["loss_arm_used" if armed else "loss_arm_dropped"] += 1
+                if armed or early:      # accumulators zeroed before the render call: the head of the list can be processed beside the pipelines (SPLIT_LOSS)
                     ctx.stash, loss = pre
                 else:
                     ctx.stash = det.acc(v)
-                fn = _lib.lib().drt_ray_loss_listed_grad_split if early else _lib.lib().drt_ray_loss_listed_grad
-                _lib.check(fn(
-                    scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), n, ior[0], ior[1], face1.data_ptr(), face2.data_ptr(),
-                    sp.data_ptr(), va.data_ptr(), link.paths[0].data_ptr(), link.paths[1].data_ptr(), loss.data_ptr(), ctx.stash.data_ptr(), _stream()))
+                if not armed:
+                    fn = _lib.lib().drt_ray_loss_listed_grad_split if early else _lib.lib().drt_ray_loss_listed_grad
+                    _lib.check(fn(
+                        scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), n, ior[0], ior[1], face1.data_ptr(), face2.data_ptr(),
+                        sp.data_ptr(), va.data_ptr(), link.paths[0].data_ptr(), link.paths[1].data_ptr(), loss.data_ptr(), ctx.stash.data_ptr(), _stream()))
                 ctx.stash_wide = ctx.stash if ctx.stash.dtype == torch.int64 else None      # (deterministic mode: the cells themselves, for det.SINK)
                 ctx.stash = det.value(ctx.stash, v)
             elif own:

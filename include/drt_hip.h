@@ -36,7 +36,8 @@ int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_r
                             * 5: drt_render_paths_law_* (law_flags: Snell refraction); 6: drt_render_paths_law_ray_loss_ior_fused;
                             * 7: drt_hull_field / drt_hull_mark / drt_hull_emit; 8: drt_render_image; 9: drt_render_image_loss;
                             * 10: drt_route_counts; 11: drt_render_image_loss_screen; 12: drt_render_image_loss_camera;
-                            * 13: drt_image_views_create / drt_render_image_loss_views */
+                            * 13: drt_image_views_create / drt_render_image_loss_views; drt_render_loss_arm / drt_render_loss_taken came
+                            * later under the same number (a library that lacks them lacks the symbols) */
 
 /* ---- deterministic accumulation ("race detection / sanitizers"; reference optim.py:155-171 clamps the SUM) --------
  * Every vertex gradient and loss of this library is a sum of contributions scattered with float64 atomics: the same inputs give results
@@ -49,8 +50,9 @@ int drt_version(void);       /* 2: drt_deterministic / drt_fx_finalize; 3: drt_r
  * are truncated at 8e-25 absolute; |x| >= 7e13, +-inf and NaN set sticky flags and give +-inf / NaN).  drt_fx_finalize converts n cells to
  * float64 with ONE rounding (nearest-even) of the exact sum: d_out[i] = value, or d_out[i] += value with `accumulate`.  Inputs that are
  * READ as gradients (d_grad_out_dir, d_grad_cos, ...) and per-ray outputs stay plain float64.  Same result for eager launches and graph
- * replays, any stream interleaving, any sub-batch split.  The price: no LDS pre-aggregation in the path kernels and two 64-bit integer
- * atomics per component (DESIGN.md section 7 has the measured cost).  drt_deterministic(-1) only queries; returns the previous mode. */
+ * replays, any stream interleaving, any sub-batch split.  The price: two 64-bit integer atomics per component, in the LDS table
+ * of the path kernels (half as many slots as the float64 table, drt_amd/csrc/drt_pathsink.h) and again when a slot goes to memory
+ * (DESIGN.md section 7 has the measured cost).  drt_deterministic(-1) only queries; returns the previous mode. */
 #define DRT_FX_BYTES_PER_VALUE 24
 int drt_deterministic(int on);
 int drt_fx_finalize(const void* d_cells, int64_t n, double* d_out, int accumulate, void* stream);
@@ -351,6 +353,25 @@ int drt_ray_loss_listed_grad_split(drt_scene_t* s, const double* d_verts, const 
                                    double ior_int, double ior_ext, const int32_t* d_face1, const int32_t* d_face2,
                                    const double* d_screen_pixel, const uint8_t* d_valid, const int32_t* d_paths, const int64_t* d_n_paths,
                                    double* d_loss, double* d_grad_verts, void* stream);
+/* Arms the NEXT drt_render_forward on this scene of exactly `n_rays` rays with its ray loss (one shot, like drt_render_seed: a call of
+ * another size drops the registration, a call that fails clears it).  d_screen_pixel float64 [n_rays,3] and d_valid uint8 [n_rays] are the
+ * targets of drt_ray_loss_listed_grad; d_loss and d_grad_verts its two accumulation targets (float64, or cells in deterministic mode).
+ * The armed call does drt_ray_loss_listed_grad's work itself: every sub-batch enqueues, on its own internal stream behind its last
+ * traversal and in front of the join, the loss + unit-seed vertex gradient of the paths IT completed (a walk over its list of exit rays,
+ * the arithmetic of drt_ray_loss_listed_grad; rays with d_valid[i] = 0 are traced and written like any other and add nothing).  When the
+ * call returns, `*d_loss` and `d_grad_verts` are ordered on `stream` like its other outputs, and no pass over the list of completed
+ * paths is needed any more; that list, the dense outputs and the face ids are written as without the arm.
+ * PRECONDITIONS (the caller's, those of drt_ray_loss_listed_grad_split): the accumulators were zeroed on `stream` BEFORE the render call is
+ * enqueued, the targets are complete by then, and all four stay valid until the call has finished on its stream.
+ * The call DECLINES the arm -- nothing is added to the accumulators, the caller takes drt_ray_loss_listed_grad afterwards -- while a
+ * graph is being captured on `stream` and when any of its sub-batches would take the one-kernel path (DRT_MEGA_MAX_LOG2), which keeps no
+ * list of exit rays.  Every other route serves it, the establishing and the untrusted (k_cull) calls included: they leave the same list.
+ * An armed call cut into sub-batches appends part of its list of completed paths on `stream` itself, so a drt_ray_loss_listed_grad_split on
+ * that list runs as the plain form.
+ * drt_render_loss_taken: 1 when the LAST drt_render_forward on this scene took an arm, 0 when it had none or declined it. */
+int drt_render_loss_arm(drt_scene_t* s, const double* d_screen_pixel, const uint8_t* d_valid, double* d_loss, double* d_grad_verts,
+                        int64_t n_rays);
+int drt_render_loss_taken(drt_scene_t* s);
 /* Adjoint of drt_render_forward followed by drt_ray_loss, for the rays drt_ray_loss listed (d_rows / *d_n_rows):
  * grad_verts [V,3] += *d_scale * d ray_loss / d vertices.  Equivalent to drt_scale_rows3 + drt_render_backward with the
  * dense d loss / d out_dir, without that [N,3] tensor (zero in all but the listed rows) ever being written or read:
