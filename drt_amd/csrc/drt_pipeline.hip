@@ -248,12 +248,46 @@ __global__ void __launch_bounds__(kPathBlock, 8) k_cull(const Node4Q* __restrict
 
 // DRT_GRID_TRUST: only the patches k_patch_list selected -- those on which a projected triangle wrote a key, and all
 // patches of images that are not trusted -- with the dense outputs pre-filled by memsets: the other nine tenths of the
-// rays are never touched by a thread.  The hits of a trusted patch go to R0 through an LDS stage (index, float32 ray, face)
-// that reserves list space once per ~600 entries: one returning atomic per patch -- ~15 000 per launch on ONE counter word,
-// served at ~90 per microsecond -- was most of this kernel's time.
-struct StageFace {
-    StageMem m;
-    int32_t face[kStageCap];
+// rays are never touched by a thread.
+//
+// The kernel is a chain of dependent loads (patch -> key -> face -> vertex ids -> float64 vertices), so it is built to pay that chain
+// once per RUN of kCullRun list entries instead of once per patch, with nothing but the chain between its barriers:
+//   work   a block takes the run of its own number first and every further one from a cursor word of the sub-batch's counter block
+//          (kCullCursor, a cache line of its own, zeroed with the block by the memset in front of every sub-batch -- also under a graph).
+//          The grid is what is resident, so no block starts late; the fetch of the next run is in flight while this one is worked on;
+//          no block ever waits for another.
+//   A      gather: wave w reads the keys of the 16x4 tile w of each patch of the run in the key buffer's own 4x4-tile order (four
+//          128-byte lines, lane-consecutive; all patches' loads in flight together), resets the keys it found and appends (ray, face)
+//          of the pixels with a key to a work list in LDS: one ballot and one LDS atomic per wave and tile, so a tile's entries stay
+//          contiguous and the 64 rays a traversal wave picks up later still come from one 16x4 screen tile.  One barrier ends the phase;
+//          the group bits are cleared behind it (every wave has read them by then).
+//   B      the work list is taken densely, kCullPer entries per thread: `direct` does bounce #1 right here on full waves -- the float64
+//          ray, Moeller-Trumbore and the refraction on the face the projection pass found, as k_shade1 does it -- otherwise the ray is
+//          loaded and rounded.  The results wait in registers (the 24 KB LDS stage they went through before is gone; registers are
+//          what bounds the residency, before and now) for ONE block scan of the push flags and ONE returning atomic on the list counter per run, and go straight
+//          to their places in R1 / R0.
+// A run is a batch: kCullRun * 256 entries at most, which is what kCullPer registers' worth per thread holds, so a batch cannot
+// overflow and is never split.  A patch of an image that is not trusted takes cull_patch, one patch at a time, as a block-uniform
+// branch of phase A: cull_patch has its own LDS and list pushes and touches nothing of the batch, so the batch stays open around it.
+constexpr int kCullRun = 4;                           // list entries per cursor fetch
+constexpr int kCullPer = kCullRun;                    // work-list entries per thread and batch
+constexpr int kCullCap = kCullRun * kPathBlock;       // entries of the work list
+constexpr int kCullCursor = 32;                       // word of the counter block: first word of its second 128-byte line
+// How many blocks work a list.  The kernel holds its results in registers (146 VGPRs): three blocks per CU are resident and all but fill
+// the register file, and while they run nothing of the OTHER sub-batch's stream -- its projection pass, or the two short launches
+// between its cull and its first traversal -- gets a wave in.  A short list (the headline: ~15 000 entries per sub-batch) is a chain of
+// latencies that two blocks per CU, or one, work off as fast as three, so the third stays out and leaves a third of the registers to
+// the other stream (measured, profiles/cull_batched.txt: 3 per CU +0.7 %, 2 per CU +1.4..1.9 %, 1 per CU +1.6 % on the step).  From
+// kCullLongRuns runs per block on (the object filling the image) the kernel is bound by its float64 arithmetic and takes every block
+// it can have (2 per CU: -2.4 % there).  The blocks that stay out return before their first barrier.
+constexpr int kCullFewPerCu = 2;
+constexpr int kCullLongRuns = 16;
+static_assert(kCullCursor < kQCount, "the cursor word lies inside the counter block");
+struct CullBatch {
+    int32_t idx[kCullCap];
+    int32_t face[kCullCap];
+    unsigned n, base, next[2];
+    unsigned wtot[kCullPer][kPathWaves];
 };
 template <bool FUSED>
 __global__ void __launch_bounds__(kPathBlock) k_cull_listed(const uint32_t* __restrict__ patches, const unsigned* __restrict__ n_patches,
@@ -261,104 +295,181 @@ __global__ void __launch_bounds__(kPathBlock) k_cull_listed(const uint32_t* __re
                                                            const uint8_t* __restrict__ valid, int64_t n, double* __restrict__ out_ori,
                                                            double* __restrict__ out_dir, uint8_t* __restrict__ mask,
                                                            int32_t* __restrict__ face1, int32_t* __restrict__ face2, Pipe p, int tile_w, RasterIn rz,
-                                                           PathCtx c, bool direct, bool prefilled, Ray64 park) {
-    // `direct` (round 4): a pixel of a trusted image with a key does bounce #1 RIGHT HERE -- the float64 ray is being loaded anyway -- and goes
-    // straight to list R1; list R0 then only holds what the untrusted images contribute (cull_patch below), and k_shade1, a pass of its own
-    // over 1.5 M entries before, has next to nothing to do (it is not even launched when every image of the call is a verified one).  The
-    // number of primary hits is still counted (count[17]: the stage statistics and the bench line's `paths` read it).
+                                                           PathCtx c, bool direct, bool prefilled, Ray64 park, unsigned few, unsigned long_list) {
+    // `direct` (round 4): a pixel of a trusted image with a key does bounce #1 RIGHT HERE and goes straight to list R1; list R0 then only
+    // holds what the untrusted images contribute (cull_patch below), and k_shade1, a pass of its own over 1.5 M entries before, has next
+    // to nothing to do (it is not even launched when every image of the call is a verified one).  The number of primary hits is still
+    // counted (count[17]: the stage statistics and the bench line's `paths` read it).
     __shared__ CullShared sh;
-    __shared__ StageFace st;
-    stage_init(st.m);
+    __shared__ CullBatch sb;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int vt = ((tid & 63) >> 4) * 64 + (tid >> 6) * 16 + (tid & 15);   // position of this thread's pixel in tile order
     const unsigned ppr = (unsigned)tile_w / 64u;
     const RayList dst = direct ? p.r1 : p.r0;
     unsigned* const dst_count = direct ? &p.count[1] : &p.count[0];
-    auto flush = [&]() {                                    // whole block; st.m.n stable
-        const unsigned cnt = st.m.n;
-        if (tid == 0) st.m.base = cnt ? atomicAdd(dst_count, cnt) : 0u;
-        __syncthreads();
-        const unsigned base = st.m.base;
-        for (unsigned k = tid; k < cnt; k += kPathBlock) { dst.idx[base + k] = st.m.idx[k]; if (!direct) dst.face[base + k] = st.face[k]; }
-        for (unsigned k = tid; k < 6u * cnt; k += kPathBlock) dst.ray[6 * (int64_t)base + k] = st.m.ray[k];
-        __syncthreads();
-        if (tid == 0) st.m.n = 0u;
-        __syncthreads();
-    };
+    unsigned* const cursor = &p.count[kCullCursor];
     unsigned n_hits = 0;                                    // primary hits this thread saw (direct mode: they are not listed anywhere)
     const unsigned count = *n_patches;
-    for (unsigned k = blockIdx.x; k < count; k += gridDim.x) {
-        const unsigned patch = patches[k];
-        const unsigned prow = patch / ppr;
-        const unsigned y = 4u * prow + (unsigned)wave, x = 64u * (patch - prow * ppr) + (unsigned)lane;
-        const unsigned view = y / (unsigned)rz.img_h;
-        if (!(rz.views[view].ok && rz.views[view].all)) {   // an image that is not trusted (block-uniform): the general per-ray path
-            cull_patch<FUSED>(patch, true, sh, nodes, n_tris, origin, dir, valid, n, out_ori, out_dir, mask, face1, face2, p, tile_w, rz);
-            __syncthreads();
-            continue;
+    const unsigned active = count >= long_list ? gridDim.x : min(few, gridDim.x);     // (kCullFewPerCu: every block computes the same)
+    if (blockIdx.x >= active) return;
+    unsigned first = blockIdx.x * (unsigned)kCullRun;
+    if (tid == 0) {
+        sb.n = 0u;
+        if (first < count) sb.next[0] = active * (unsigned)kCullRun + atomicAdd(cursor, (unsigned)kCullRun);
+    }
+    __syncthreads();
+
+    // phases B and the write-out of the entries appended so far; whole block, behind a barrier that follows the last append
+    auto close_batch = [&]() {
+        const unsigned cnt = sb.n;
+        if (cnt == 0u) { __syncthreads(); return; }         // (the barrier: no wave appends again before every wave has read `n`)
+        int32_t ei[kCullPer], ef[kCullPer];
+        f3 eo[kCullPer], ed[kCullPer];
+        bool push[kCullPer];
+        unsigned rank[kCullPer];
+#pragma unroll
+        for (int j = 0; j < kCullPer; ++j) {
+            const unsigned k = (unsigned)(j * kPathBlock + tid);
+            push[j] = false;
+            ei[j] = 0; ef[j] = -1;
+            eo[j] = f3{0.f, 0.f, 0.f}; ed[j] = f3{0.f, 0.f, 1.f};
+            if (k < cnt) {
+                const int64_t i = sb.idx[k];
+                const int32_t f1 = sb.face[k];
+                ei[j] = (int32_t)i; ef[j] = f1;
+                if (direct) {
+                    // bounce #1 (what k_shade1 does with an R0 entry): float64 Moeller-Trumbore + refraction on the face the projection pass found
+                    face1[i] = f1;
+                    d3 v0, v1, v2;
+                    int32_t vid[3];
+                    Bounce b;
+                    load_tri64(c, f1, v0, v1, v2, vid);
+                    bounce_forward(load_d3(origin, i), load_d3(dir, i), v0, v1, v2, c.ior_ext, c.ior_int, b);
+                    push[j] = !b.tir;
+                    eo[j] = to_f32(b.new_o); ed[j] = to_f32(b.wt);
+                    // (the float64 refracted ray parked in the ray's rows of the dense outputs -- already zeroed, rewritten by k_shade2 whatever
+                    // becomes of the path -- so that k_shade2 does bounce #2 only: what k_shade1 does for the one-kernel path)
+                    if (push[j] && park.o) { store_d3(park.o, i, b.new_o); store_d3(park.d, i, b.wt); }
+                    if (!push[j] && !FUSED) { if (prefilled) face2[i] = -1; else write_dead(i, out_ori, out_dir, mask, face2); }
+                    ++n_hits;
+                } else {
+                    eo[j] = to_f32(load_d3(origin, i)); ed[j] = to_f32(load_d3(dir, i));
+                    push[j] = true;
+                }
+            }
+            const unsigned long long bm = __ballot(push[j]);
+            if (lane == 0) sb.wtot[j][wave] = (unsigned)__popcll(bm);
+            rank[j] = (unsigned)__popcll(bm & ((1ull << lane) - 1ull));
         }
-        const int64_t i = (int64_t)y * tile_w + x;
-        unsigned long long key = kRasterEmpty;
-        const unsigned word = rz.zmask[i >> 11], bit = 1u << ((i >> 6) & 31);
-        if (word & bit) {
-            const int64_t zs = raster_slot(x, y, (unsigned)tile_w);
-            key = rz.zbuf[zs];
-            if (key != kRasterEmpty) rz.zbuf[zs] = kRasterEmpty;           // consumed: the buffer is empty again for the next call
+        __syncthreads();
+        // ranks in work-list order: batch slice j, then wave, then lane
+        unsigned tot = 0;
+#pragma unroll
+        for (int j = 0; j < kCullPer; ++j) {
+            unsigned before = tot;
+#pragma unroll
+            for (int w = 0; w < kPathWaves; ++w) { const unsigned cw = sb.wtot[j][w]; if (w < wave) before += cw; tot += cw; }
+            rank[j] += before;
         }
-        const bool cand = key != kRasterEmpty && (!FUSED || valid[i]);
-        bool push = cand;                                   // contributes a list entry
-        f3 o{0.f, 0.f, 0.f}, d{0.f, 0.f, 1.f};
-        if (cand) {
-            if (direct) {
-                // bounce #1 (what k_shade1 does with an R0 entry): float64 Moeller-Trumbore + refraction on the face the projection pass found
-                const int32_t f1 = (int32_t)(uint32_t)key;
-                face1[i] = f1;
-                d3 v0, v1, v2;
-                int32_t vid[3];
-                Bounce b;
-                load_tri64(c, f1, v0, v1, v2, vid);
-                bounce_forward(load_d3(origin, i), load_d3(dir, i), v0, v1, v2, c.ior_ext, c.ior_int, b);
-                push = !b.tir;
-                o = to_f32(b.new_o); d = to_f32(b.wt);
-                // (the float64 refracted ray parked in the ray's rows of the dense outputs -- already zeroed, rewritten by k_shade2 whatever
-                // becomes of the path -- so that k_shade2 does bounce #2 only: what k_shade1 does for the one-kernel path)
-                if (push && park.o) { store_d3(park.o, i, b.new_o); store_d3(park.d, i, b.wt); }
-                if (!push && !FUSED) { if (prefilled) face2[i] = -1; else write_dead(i, out_ori, out_dir, mask, face2); }
-                ++n_hits;
-            } else {
-                o = to_f32(load_d3(origin, i)); d = to_f32(load_d3(dir, i));
+        if (tid == 0) { sb.base = tot ? atomicAdd(dst_count, tot) : 0u; sb.n = 0u; }
+        __syncthreads();
+        const unsigned base = sb.base;
+#pragma unroll
+        for (int j = 0; j < kCullPer; ++j) {
+            if (!push[j]) continue;
+            const unsigned slot = base + rank[j];
+            dst.idx[slot] = ei[j];
+            float2* e = reinterpret_cast<float2*>(dst.ray + 6 * (int64_t)slot);      // (24-byte entries of an aligned array: three 8-byte stores)
+            e[0] = float2{eo[j].x, eo[j].y}; e[1] = float2{eo[j].z, ed[j].x}; e[2] = float2{ed[j].y, ed[j].z};
+            if (!direct) dst.face[slot] = ef[j];
+        }
+    };
+
+    for (unsigned it = 0; first < count; ++it) {
+        const unsigned cnt = min((unsigned)kCullRun, count - first);
+        // phase A, loads: list entries, verdicts, group words and keys of every patch of the run (a key is read whether or not its group
+        // bit is set -- and counts only if it is -- so that it does not wait for the word)
+        uint32_t pt[kCullRun];
+        bool ok[kCullRun];
+        unsigned word[kCullRun];
+        unsigned long long key[kCullRun];
+        int64_t zs[kCullRun], ri[kCullRun];
+#pragma unroll
+        for (int j = 0; j < kCullRun; ++j) pt[j] = (unsigned)j < cnt ? patches[first + j] : 0u;
+#pragma unroll
+        for (int j = 0; j < kCullRun; ++j) {
+            const unsigned prow = pt[j] / ppr;
+            const unsigned x = 64u * (pt[j] - prow * ppr) + 16u * (unsigned)wave + 4u * ((unsigned)lane >> 4) + ((unsigned)lane & 3u);
+            const unsigned y = 4u * prow + (((unsigned)lane >> 2) & 3u);
+            const unsigned view = (4u * prow) / (unsigned)rz.img_h;
+            ri[j] = (int64_t)y * tile_w + x;
+            zs[j] = raster_slot(x, y, (unsigned)tile_w);
+            ok[j] = false; word[j] = 0u; key[j] = kRasterEmpty;
+            if ((unsigned)j < cnt) {
+                ok[j] = rz.views[view].ok && rz.views[view].all;   // (block-uniform; a verdict does not rise inside a call, and falls only where it is not trusted already)
+                word[j] = rz.zmask[ri[j] >> 11];
+                key[j] = rz.zbuf[zs[j]];
             }
         }
-        // rank of this thread's entry among the patch's entries, in 16x4-tile order
-        sh.flag[vt] = push ? 1 : 0;
-        __syncthreads();
-        if ((word & bit) && lane == 0) atomicAnd(&rz.zmask[i >> 11], ~bit);  // (after the barrier: every wave has read its bit)
-        const bool mine = sh.flag[tid] != 0;
-        const unsigned long long bm = __ballot(mine);
-        if (lane == 0) sh.tmp[wave] = (unsigned)__popcll(bm);
-        __syncthreads();
-        unsigned before = 0, tot = 0;
-        for (int w = 0; w < kPathWaves; ++w) { const unsigned cw = sh.tmp[w]; if (w < wave) before += cw; tot += cw; }
-        sh.slot[tid] = mine ? (int)(before + (unsigned)__popcll(bm & ((1ull << lane) - 1ull))) : -1;
-        __syncthreads();
-        if (push) {
-            const unsigned slot = st.m.n + (unsigned)sh.slot[vt];
-            st.m.idx[slot] = (int32_t)i;
-            float* e = st.m.ray + 6 * slot;
-            e[0] = o.x; e[1] = o.y; e[2] = o.z; e[3] = d.x; e[4] = d.y; e[5] = d.z;
-            st.face[slot] = (int32_t)(uint32_t)key;
+        // phase A, appends
+#pragma unroll
+        for (int j = 0; j < kCullRun; ++j) {
+            if ((unsigned)j >= cnt) continue;
+            if (!ok[j]) {
+                // an image that is not trusted (block-uniform): the general per-ray path.  It pushes to R0 / gen_list through `sh` and
+                // the list counters and touches nothing of the batch, whose entries so far simply wait in the work list
+                cull_patch<FUSED>(pt[j], true, sh, nodes, n_tris, origin, dir, valid, n, out_ori, out_dir, mask, face1, face2, p, tile_w, rz);
+                __syncthreads();
+                continue;
+            }
+            const int64_t i = ri[j];
+            const bool has = ((word[j] >> ((i >> 6) & 31)) & 1u) != 0u && key[j] != kRasterEmpty;
+            if (has) rz.zbuf[zs[j]] = kRasterEmpty;          // consumed: the buffer is empty again for the next call
+            const bool take = has && (!FUSED || valid[i]);
+            const unsigned long long bm = __ballot(take);
+            if (bm != 0ull) {                               // (wave-uniform)
+                unsigned at = 0u;
+                if (lane == 0) at = atomicAdd(&sb.n, (unsigned)__popcll(bm));
+                at = (unsigned)__shfl((int)at, 0);
+                if (take) {
+                    const unsigned k = at + (unsigned)__popcll(bm & ((1ull << lane) - 1ull));
+                    sb.idx[k] = (int32_t)i;
+                    sb.face[k] = (int32_t)(uint32_t)key[j];
+                }
+            }
         }
         __syncthreads();
-        if (tid == 0) st.m.n += tot;
-        __syncthreads();
-        if (st.m.n > kStageCap - kPathBlock) flush();
+        // the group bits of the run's patches, cleared only now: every wave has read them (those of a patch that took cull_patch are
+        // cleared already)
+        if (tid < 4 * (int)cnt) {
+            const unsigned q = patches[first + ((unsigned)tid >> 2)], prow = q / ppr;
+            const int64_t i0 = (int64_t)(4u * prow + ((unsigned)tid & 3u)) * tile_w + 64u * (q - prow * ppr);
+            const unsigned bit = 1u << ((i0 >> 6) & 31);
+            if (rz.zmask[i0 >> 11] & bit) atomicAnd(&rz.zmask[i0 >> 11], ~bit);
+        }
+        // the next run: fetched one iteration ahead
+        const unsigned nxt = sb.next[it & 1u];
+        if (tid == 0 && nxt < count) sb.next[(it + 1u) & 1u] = active * (unsigned)kCullRun + atomicAdd(cursor, (unsigned)kCullRun);
+        close_batch();
+        first = nxt;
     }
-    flush();
     if (direct) {
         unsigned h = n_hits;
         for (int off = 32; off >= 1; off >>= 1) h += __shfl_xor(h, off);
         if (lane == 0 && h) atomicAdd(&p.count[17], h);
     }
+}
+// resident 256-thread blocks of k_cull_listed per CU: the occupancy query, held to what the hardware admits (it admits one block fewer
+// than the query says for kernels of 81 to 112 scalar registers; kCullSgprBlocks is that bound for the larger of the two
+// instantiations, from the compiler's resource report)
+constexpr int kCullSgprBlocks = 6;
+int cull_blocks_per_cu() {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cull_listed<false>, kPathBlock, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+    int f = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&f, k_cull_listed<true>, kPathBlock, 0) == hipSuccess && f >= 1 && f < per_cu) per_cu = f;
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu > kCullSgprBlocks) per_cu = kCullSgprBlocks;
+    return per_cu;
 }
 
 // Which patches k_cull_listed has to visit: one thread per patch.
@@ -1341,10 +1452,10 @@ static int launch_chunk(drt_scene* s, drt_scene::Sub& w, hipStream_t st, const P
     const bool tree_late = all_verified && rz.views != nullptr;
     if (!tree_late) { int rc = wait_build(s, st); if (rc) return rc; }
     // bounce #1 inside the cull of the listed patches (k_cull_listed's `direct`); the one-kernel path parks float64 rays in k_shade1: not there
-    // Only for large sub-batches: the listed patches are handled one after the other by each block, a few hits per patch, so the float64
-    // bounce runs at low lane use and with the patch loop's barriers around it -- cheaper than a pass of its own over list R0 once the chip
-    // is saturated (72 views: -1.3 %, the object filling the image: -4.3 %), dearer when the call is a chain of latencies (36 views in two
-    // sub-batches +3.5 %, 9 views +6.5 %).
+    // Only for large sub-batches.  Measured on the kernel that handled the listed patches one after the other, the float64 bounce on the
+    // lanes that held a key and the patch loop's barriers around it: cheaper than a pass of its own over list R0 once the chip is
+    // saturated (72 views: -1.3 %, the object filling the image: -4.3 %), dearer when the call is a chain of latencies (36 views in two
+    // sub-batches +3.5 %, 9 views +6.5 %).  (The threshold has not been measured again since the bounce runs on dense lanes.)
     const bool direct = s->cull_direct && rz.views && grid_mode == DRT_GRID_TRUST && !mega && n >= s->cull_direct_min_rays;
     // ... and parks the float64 refracted rays in the rows of the dense outputs when those are zeroed already (recycled / zeroed ahead of
     // time: no fill of this call can run over them) and the zeroing is through (prefill_done)
@@ -1368,8 +1479,10 @@ static int launch_chunk(drt_scene* s, drt_scene::Sub& w, hipStream_t st, const P
           // (the dense outputs were pre-filled with the dead values above, before the projection pass)
           uint32_t* list = reinterpret_cast<uint32_t*>(p.redo);          // free until the first k_trace of this sub-batch
           k_patch_list<<<(n_patches + kPathBlock - 1) / kPathBlock, kPathBlock, 0, st>>>(n_patches, tile_w, rz, list, p.count + 7);
-          k_cull_listed<FUSED><<<gs, kPathBlock, 0, st>>>(list, p.count + 7, pc.tc.nodes, pc.tc.n_tris, o, d, valid, n, out_ori, out_dir, mask, face1, face2, p, tile_w, rz,
-                                                          pc, direct, late_fill, park ? Ray64{out_ori, out_dir} : Ray64{nullptr, nullptr});
+          static const int cull_per_cu = cull_blocks_per_cu();           // (the grid is what is resident: work is dealt by the cursor p.count[kCullCursor])
+          const unsigned few = (unsigned)(kCullFewPerCu * s->n_cu), long_list = few * (unsigned)(kCullRun * kCullLongRuns);
+          k_cull_listed<FUSED><<<cull_per_cu * s->n_cu, kPathBlock, 0, st>>>(list, p.count + 7, pc.tc.nodes, pc.tc.n_tris, o, d, valid, n, out_ori, out_dir, mask, face1, face2, p, tile_w, rz,
+                                                          pc, direct, late_fill, park ? Ray64{out_ori, out_dir} : Ray64{nullptr, nullptr}, few, long_list);
       } else {
           // (every ray is read and decided here; with all three outputs already zero -- recycled -- and face ids only promised where mask = 1,
           // the dead ones, nine in ten, need not be written again: 56 B read per ray instead of 56 read + 59 written)

@@ -54,7 +54,7 @@ constexpr int kStackFast = DRT_STACK_FAST;         // LDS stack entries per lane
 static_assert(kStackFast >= 3, "FastStack keeps four spare entries (kStackFast + 1 rows) above its usable depth");
 constexpr int kStackTotal = 192;
 constexpr int kStackSlowDev = kStackTotal - kStackFast;   // global overflow entries per thread
-constexpr int kQCount = 24;            // words of a pipeline's counter block ([16]: k_trace's retired-workgroup counter)
+constexpr int kQCount = 64;            // words of a pipeline's counter block ([16]: k_trace's retired-workgroup counter; [32]: k_cull_listed's work cursor, on the second 128-byte line)
 constexpr int kRedoGrid = 64;          // blocks of the one-thread-per-item second-pass kernels (k_path_redo, k_gen_late); sizes the overflow areas
 constexpr int kTraceGridMax = 4096;    // blocks per traversal launch (persistent, grid-stride)
 constexpr int64_t kChunkRays = 1 << 26; // max rays per pipeline pass; bounds the list workspace (96 B per ray of the largest pass)
