@@ -72,6 +72,11 @@ def _ior_host(x, what):
     return float(x.detach())
 
 
+def _ior_args(ior_int, ior_ext):
+    """(float values, the tensors among them or None -- what autograd may track) of a call's ``ior_int`` / ``ior_ext`` arguments."""
+    return (_ior_host(ior_int, "ior_int"), _ior_host(ior_ext, "ior_ext")), tuple(x if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
+
+
 def _wants_input_grads(*xs):
     """True when autograd would need d / d x for one of these render inputs (rays, IORs): tensors that require grad, grad mode on."""
     return torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in xs)
@@ -811,124 +816,32 @@ def enqueue_ray_term(scene, vertices, origin, ray_dir, target, valid, law, loss_
     return [o, d, sp, va]
 
 
-class _RenderRayLossFused(torch.autograd.Function):
-    """render_transparent + ray_loss + d/d vertices in ONE kernel pass (nothing dense written): ``enqueue_ray_term`` into accumulators of
-    its own -- with ``law`` (a normalised law tuple) under the K-interaction law of ``render_paths``, and ``scene.last_path_count`` is
-    then the call's number of contributing rays.  The gradient is computed in the forward pass; the backward only scales it."""
-
-    @staticmethod
-    def forward(ctx, vertices, origin, ray_dir, screen_pixel, valid, scene, ior, law, grid):
-        v = _f64c(vertices.detach(), "vertices")
-        loss = det.scalar(v.device)
-        grad_v = det.acc(v)
-        count = torch.zeros((), dtype=torch.int64, device=v.device) if law is not None else None
-        with _on(v.device):
-            enqueue_ray_term(scene, v, origin, ray_dir, screen_pixel, valid, law, loss.data_ptr(), grad_v.data_ptr(), _lib.ptr(count), ior, grid)
-        if law is not None:
-            scene.last_path_count = count
-        ctx.wide = grad_v if grad_v.dtype == torch.int64 else None
-        ctx.save_for_backward(det.value(grad_v, v))
-        return det.value(loss)
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        (grad_v,) = ctx.saved_tensors
-        if det.SINK is not None and ctx.wide is not None:
-            det.SINK.append((ctx.wide, g_loss))
-            return None, None, None, None, None, None, None, None, None
-        return grad_v * g_loss, None, None, None, None, None, None, None, None
+_IMAGE_ENTRIES = {"plain": ("drt_render_image_loss", 0), "screen": ("drt_render_image_loss_screen", 2), "camera": ("drt_render_image_loss_camera", 3)}
 
 
-class _PathsRayLossIorFused(torch.autograd.Function):
-    """_RenderRayLossFused under a law that also differentiates the indices of refraction (drt_render_paths_law_ray_loss_ior_fused):
-    the vertex gradient -- unless ``want_verts`` is off: no array is handed over and the library runs its kernel without the gradient
-    table -- and the two IOR partials are computed here with a unit seed; the backward only scales them.  ``ior_int`` / ``ior_ext``
-    stand for the tensors autograd tracks (or None); ``ior`` carries their float values."""
-
-    @staticmethod
-    def forward(ctx, vertices, ior_int, ior_ext, origin, ray_dir, screen_pixel, valid, scene, ior, max_bounces, law_flags, want_verts):
-        v = _f64c(vertices.detach(), "vertices")
-        o = _f64c(origin, "origin")
-        d = _f64c(ray_dir, "ray_dir")
-        sp = _f64c(screen_pixel, "screen_pixel")
-        va = _flag_bytes(valid, "valid", o.shape[0])
-        loss = det.scalar(o.device)
-        grad_v = det.acc(v) if want_verts else None
-        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=o.device))
-        count = torch.zeros((), dtype=torch.int64, device=o.device)
-        with _on(o.device):
-            _lib.check(_lib.lib().drt_render_paths_law_ray_loss_ior_fused(
-                scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), o.shape[0],
-                ior[0], ior[1], max_bounces, law_flags, loss.data_ptr(), _lib.ptr(grad_v), grad_ior.data_ptr(), count.data_ptr(), _stream()))
-        scene.last_path_count = count
-        ctx.ior_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
-        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
-        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v), det.value(grad_ior, torch.empty(2, dtype=torch.float64)))
-        return det.value(loss)
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        grad_v, both = ctx.saved_tensors
-        g_ior = [None, None]
-        for k in (0, 1):
-            if ctx.needs_input_grad[1 + k]:
-                shape, dtype, dev = ctx.ior_like[k]
-                g_ior[k] = (both[k] * g_loss).reshape(shape).to(dtype=dtype, device=dev)
-        if grad_v is None or not ctx.needs_input_grad[0]:
-            g_v = None
-        elif det.SINK is not None and ctx.wide is not None:
-            det.SINK.append((ctx.wide, g_loss))
-            g_v = None
-        else:
-            g_v = grad_v * g_loss
-        return g_v, g_ior[0], g_ior[1], None, None, None, None, None, None, None, None, None
-
-
-class _ImageLossFused(torch.autograd.Function):
-    """The photometric loss of the refracted image (drt_render_image_loss) in the mould of _PathsRayLossIorFused: the
-    vertex gradient (unless ``a["vertices"]`` is off) and the two IOR partials are computed here with a unit seed, band after band into one
-    set of accumulators; the backward only scales them.  ``ior_int`` / ``ior_ext`` stand for the tensors autograd tracks (or None);
-    ``ior`` carries their float values; ``out`` receives the image and the count."""
-
-    @staticmethod
-    def forward(ctx, vertices, ior_int, ior_ext, scene, a, ior, tex, target, weight, out):
-        v = _f64c(vertices.detach(), "vertices")
-        dev = v.device
-        H, W, C = a["height"], a["width"], a["channels"]
-        loss = det.scalar(dev)
-        grad_v = det.acc(v) if a["vertices"] else None
-        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=dev))
-        count = torch.zeros((), dtype=torch.int64, device=dev)
-        image = torch.empty((H, W, C), dtype=torch.float32, device=dev) if a["want_image"] else None
-        with _on(dev):
-            for y0, y1 in a["bands"]:
-                _lib.check(_lib.lib().drt_render_image_loss(
-                    scene.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
-                    a["law_flags"], a["fresnel"], a["screen"].ctypes.data, tex.data_ptr(), tex.shape[0], tex.shape[1], C, a["void"].ctypes.data,
-                    a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss.data_ptr(), _lib.ptr(grad_v), grad_ior.data_ptr(),
-                    _lib.ptr(image), count.data_ptr(), _stream()))
-        out["image"], out["count"] = image, count
-        ctx.ior_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
-        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
-        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v), det.value(grad_ior, torch.empty(2, dtype=torch.float64)))
-        return det.value(loss)
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        grad_v, both = ctx.saved_tensors
-        g_ior = [None, None]
-        for k in (0, 1):
-            if ctx.needs_input_grad[1 + k]:
-                shape, dtype, dev = ctx.ior_like[k]
-                g_ior[k] = (both[k] * g_loss).reshape(shape).to(dtype=dtype, device=dev)
-        if grad_v is None or not ctx.needs_input_grad[0]:
-            g_v = None
-        elif det.SINK is not None and ctx.wide is not None:
-            det.SINK.append((ctx.wide, g_loss))
-            g_v = None
-        else:
-            g_v = grad_v * g_loss
-        return g_v, g_ior[0], g_ior[1], None, None, None, None, None, None, None
+def enqueue_image_term(scene, vertices, a, ior, texture, target, weight, loss_ptr, grad_ptr=None, grad_ior_ptr=None, image_ptr=None, count_ptr=None,
+                       screen_ptr=None, texture_ptr=None, camera_ptr=None, entry=None):
+    """Enqueues ONE view's photometric image term -- loss and its unit-seed gradients, band after band of ``a["bands"]`` into one set of
+    accumulators -- on the current stream; the one place that packs the arguments of drt_render_image_loss, drt_render_image_loss_screen
+    and drt_render_image_loss_camera.  ``a``: the checked arguments (``render.check_image_loss_args``); ``ior``: (interior, exterior)
+    floats; ``texture`` / ``target`` / ``weight``: contiguous float32 device tensors (weight may be None).  ``loss_ptr`` and the other
+    ``*_ptr`` are raw device addresses the kernels ADD into (float64, or fixed-point cells in deterministic mode; float32 image, int64
+    count); all but the first may be None.  The call goes to the narrowest entry point that has a parameter for every accumulator given
+    -- plain, then screen (screen 9, texture), then camera (21) --; ``entry`` ("plain" / "screen" / "camera") names a wider one, whose
+    extra parameters are then null.  The caller is inside ``_on(device)``.  Returns what the enqueued kernels read, for the caller to
+    keep alive."""
+    extra = (screen_ptr, texture_ptr, camera_ptr)
+    needed = 3 if camera_ptr is not None else 2 if screen_ptr is not None or texture_ptr is not None else 0
+    name, n_extra = _IMAGE_ENTRIES[entry] if entry is not None else next(e for e in _IMAGE_ENTRIES.values() if e[1] >= needed)
+    if n_extra < needed:
+        raise ValueError(f"entry {entry!r} has no parameter for an accumulator that was given")
+    fn, H, W, C = getattr(_lib.lib(), name), a["height"], a["width"], a["channels"]
+    for y0, y1 in a["bands"]:
+        _lib.check(fn(
+            scene.optix_mesh._h, vertices.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
+            a["law_flags"], a["fresnel"], a["screen"].ctypes.data, texture.data_ptr(), texture.shape[0], texture.shape[1], C, a["void"].ctypes.data,
+            a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss_ptr, grad_ptr, grad_ior_ptr, image_ptr, count_ptr, *extra[:n_extra], _stream()))
+    return [vertices, texture, target, weight]
 
 
 def enqueue_image_views_term(scene, vertices, binding, view_ids, texture, law, supersample, fresnel, void, invalid, ior, loss_ptr, grad_ptr,
@@ -951,166 +864,140 @@ def enqueue_image_views_term(scene, vertices, binding, view_ids, texture, law, s
     return [vertices, texture, binding]
 
 
-class _ImageLossViewsFused(torch.autograd.Function):
-    """_ImageLossFused over several views of a binding (drt_render_image_loss_views): unit seed in the forward, scaling
-    in the backward, the deterministic sink honoured; ``out`` receives the count."""
+# What a ``Scene`` method states about one loss term for ``_UnitSeedTerm.apply(term, *inputs)``:
+#   device   where the loss accumulator lives;
+#   accs     {name: (like, users)}: the accumulators the call may want, each for a float64 tensor shaped ``like``; ``users`` None: always
+#            allocated, else the positions in ``inputs`` of which one must need a gradient.  An accumulator that is not allocated reaches
+#            the library as a null pointer, which selects another kernel instantiation: these rules are each route's own;
+#   enqueue  callable(loss, cells) that enqueues the native work into the raw pointers of ``loss`` and ``cells`` = {name: the zeroed
+#            accumulators that were allocated}; tensor conversions, ``_on`` and ``_stream`` are its business;
+#   feeds    per input, (name, pick): the accumulator that holds its gradient and, where the gradient is not the whole of it, ``pick(scaled
+#            values, the input's shape)``;
+#   count, image   what the call publishes afterwards: tensors the enqueued work writes, or None.
+_Term = collections.namedtuple("_Term", "device accs enqueue feeds count image", defaults=(None, None))
+_VERTS = "vertices"                 # the accumulator whose wide cells the deterministic sink takes
+_IOR_FEEDS = (("ior", lambda s, shape: s[0]), ("ior", lambda s, shape: s[1]))
+
+
+def _verts_ior_accs(v, want_verts, ior_users=None):
+    """The vertex accumulator (like ``v``) unless ``want_verts`` is off, and the IOR pair on its device."""
+    accs = {_VERTS: (v, None)} if want_verts else {}
+    accs["ior"] = (torch.empty(2, dtype=torch.float64, device=v.device), ior_users)
+    return accs
+
+
+def _rinv_rows(s, shape):
+    """d / d R^-1 of the 21 camera partials [K^-1's nine, R^-1's top three rows]: a [4, 4] R^-1 gets a zero bottom row (the renderer does not read it)."""
+    rows = s[9:].reshape(3, 4)
+    return torch.cat([rows, rows.new_zeros((1, 4))]) if tuple(shape) == (4, 4) else rows
+
+
+class _UnitSeedTerm(torch.autograd.Function):
+    """Every one-pass loss term of ``Scene`` (ray_loss_fused, paths_ray_loss[_ior]_fused, image_loss[_views]_fused; DESIGN.md 7.4,
+    10.3-10.6) as a function of ``inputs`` -- the tensors autograd may track for it, or None: vertices, IORs, screen, texture, R^-1,
+    K^-1, whichever the ``term`` (a ``_Term``) has.  The forward allocates the accumulators the term asks for and has it enqueue the
+    native work, which computes every gradient with a unit seed; the backward only scales them by the incoming gradient and hands each
+    back in its input's own shape, dtype and device.  While ``det.SINK`` is armed the vertex gradient's wide cells go there instead."""
 
     @staticmethod
-    def forward(ctx, vertices, ior_int, ior_ext, scene, binding, a, ior, tex, out):
-        v = _f64c(vertices.detach(), "vertices")
-        dev = v.device
-        loss = det.scalar(dev)
-        grad_v = det.acc(v) if a["vertices"] else None
-        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=dev))
-        count = torch.zeros((), dtype=torch.int64, device=dev)
-        law = (a["max_bounces"], "reflect" if a["law_flags"] & 1 else "drop", "snell" if a["law_flags"] & 2 else "reference")
+    def forward(ctx, term, *inputs):
+        nig = ctx.needs_input_grad[1:]
+        loss = det.scalar(term.device)
+        cells = {name: det.acc(like) for name, (like, users) in term.accs.items() if users is None or any(nig[k] for k in users)}
+        term.enqueue(loss, cells)
+        wide = cells.get(_VERTS)
+        ctx.wide = wide if wide is not None and wide.dtype == torch.int64 else None      # (deterministic mode: the cells themselves, for det.SINK)
+        ctx.names, ctx.feeds = tuple(cells), term.feeds
+        ctx.like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in inputs)
+        ctx.save_for_backward(*(det.value(c, term.accs[name][0]) for name, c in cells.items()))
+        return det.value(loss)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        stored, scaled, grads = dict(zip(ctx.names, ctx.saved_tensors)), {}, [None]
+        for k, feed in enumerate(ctx.feeds):
+            grads.append(None)
+            if feed is None or feed[0] not in stored or not ctx.needs_input_grad[1 + k]:
+                continue
+            name, pick = feed
+            if name == _VERTS and det.SINK is not None and ctx.wide is not None:
+                det.SINK.append((ctx.wide, g_loss))          # full_batch_step sums the cells of all calls and ranks exactly, then converts once
+                continue
+            if name not in scaled:
+                scaled[name] = stored[name] * g_loss
+            shape, dtype, dev = ctx.like[k]
+            g = scaled[name] if pick is None else pick(scaled[name], shape)
+            grads[-1] = g.reshape(shape).to(dtype=dtype, device=dev)
+        return tuple(grads)
+
+
+def _ray_term(scene, origin, ray_dir, screen_pixel, valid, ior, law, grid):
+    """The term of ray_loss_fused (``law`` None: the two-bounce kernel with ``grid``) and paths_ray_loss_fused (a normalised law tuple):
+    ``enqueue_ray_term`` into a vertex accumulator that is always there; the count of contributing rays only under a law."""
+    v = _f64c(scene.vertices.detach(), "vertices")
+    count = torch.zeros((), dtype=torch.int64, device=v.device) if law is not None else None
+
+    def enqueue(loss, cells):
+        with _on(v.device):
+            enqueue_ray_term(scene, v, origin, ray_dir, screen_pixel, valid, law, loss.data_ptr(), cells[_VERTS].data_ptr(), _lib.ptr(count), ior, grid)
+    return _Term(v.device, {_VERTS: (v, None)}, enqueue, ((_VERTS, None),), count)
+
+
+def _paths_ior_term(scene, origin, ray_dir, screen_pixel, valid, ior, max_bounces, law_flags, want_verts):
+    """The term of paths_ray_loss_ior_fused (drt_render_paths_law_ray_loss_ior_fused) for the inputs (vertices, ior_int,
+    ior_ext): the IOR pair always, the vertex accumulator unless ``want_verts`` is off -- no array is handed over and the library runs
+    its kernel without the gradient table."""
+    v = _f64c(scene.vertices.detach(), "vertices")
+    count = torch.zeros((), dtype=torch.int64, device=v.device)
+
+    def enqueue(loss, cells):
+        o, d, sp = _f64c(origin, "origin"), _f64c(ray_dir, "ray_dir"), _f64c(screen_pixel, "screen_pixel")
+        va = _flag_bytes(valid, "valid", o.shape[0])
+        with _on(v.device):
+            _lib.check(_lib.lib().drt_render_paths_law_ray_loss_ior_fused(
+                scene.optix_mesh._h, v.data_ptr(), o.data_ptr(), d.data_ptr(), sp.data_ptr(), va.data_ptr(), o.shape[0], ior[0], ior[1], max_bounces,
+                law_flags, loss.data_ptr(), _lib.ptr(cells.get(_VERTS)), cells["ior"].data_ptr(), count.data_ptr(), _stream()))
+    return _Term(v.device, _verts_ior_accs(v, want_verts), enqueue, ((_VERTS, None),) + _IOR_FEEDS, count)
+
+
+def _image_term(scene, a, ior, tex, target, weight, entry="plain"):
+    """The term of image_loss_fused on the checked arguments ``a`` for the inputs (vertices, ior_int, ior_ext), then (screen_param,
+    texture_param) from ``entry`` "screen" on, then (Rinv, Kinv) at "camera"; ``entry`` is also the native entry point the call reaches
+    (``enqueue_image_term``).  The vertex accumulator follows ``a["vertices"]``; the IOR pair is always there at "plain" and "screen",
+    at "camera" only when an IOR needs a gradient; screen 9, texture (scattered in threes: padded to a multiple of three, sliced back)
+    and camera 21 only when such an input needs one."""
+    v = _f64c(scene.vertices.detach(), "vertices")
+    dev, n_tex = v.device, tex.numel()
+    like = lambda n: torch.empty(n, dtype=torch.float64, device=dev)      # noqa: E731
+    accs = _verts_ior_accs(v, a["vertices"], (1, 2) if entry == "camera" else None)
+    feeds = ((_VERTS, None),) + _IOR_FEEDS
+    if entry != "plain":
+        accs["screen"], accs["texture"] = (like(9), (3,)), (like((n_tex + 2) // 3 * 3), (4,))
+        feeds += (("screen", None), ("texture", lambda s, shape: s[:n_tex]))
+    if entry == "camera":
+        accs["camera"] = (like(21), (5, 6))
+        feeds += (("camera", _rinv_rows), ("camera", lambda s, shape: s[:9]))
+    count = torch.zeros((), dtype=torch.int64, device=dev)
+    image = torch.empty((a["height"], a["width"], a["channels"]), dtype=torch.float32, device=dev) if a["want_image"] else None
+
+    def enqueue(loss, cells):
         with _on(dev):
+            enqueue_image_term(scene, v, a, ior, tex, target, weight, loss.data_ptr(), _lib.ptr(cells.get(_VERTS)), _lib.ptr(cells.get("ior")), _lib.ptr(image),
+                               count.data_ptr(), *(_lib.ptr(cells.get(k)) for k in ("screen", "texture", "camera")), entry=entry)
+    return _Term(dev, accs, enqueue, feeds, count, image)
+
+
+def _image_views_term(scene, binding, a, ior, tex, law):
+    """The term of image_loss_views_fused (``enqueue_image_views_term``) for the inputs (vertices, ior_int, ior_ext):
+    the vertex accumulator follows ``a["vertices"]``, the IOR pair and the count are always there."""
+    v = _f64c(scene.vertices.detach(), "vertices")
+    count = torch.zeros((), dtype=torch.int64, device=v.device)
+
+    def enqueue(loss, cells):
+        with _on(v.device):
             enqueue_image_views_term(scene, v, binding, a["ids"], tex, law, a["supersample"], a["fresnel"], a["void"], a["invalid"], ior, loss.data_ptr(),
-                                     _lib.ptr(grad_v), grad_ior.data_ptr(), count.data_ptr(), a["bands"])
-        out["count"] = count
-        ctx.ior_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
-        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
-        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v), det.value(grad_ior, torch.empty(2, dtype=torch.float64)))
-        return det.value(loss)
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        return _ImageLossFused.backward(ctx, g_loss)[:3] + (None,) * 6
-
-
-class _ImageLossScreenFused(torch.autograd.Function):
-    """_ImageLossFused that also differentiates the screen's pose and the texture (drt_render_image_loss_screen):
-    ``screen_param`` / ``texture_param`` stand for the tensors autograd tracks (or None); ``a["screen"]`` and ``tex`` carry their values.
-    The nine screen partials and the texture gradient are computed here with a unit seed, band after band into one set of accumulators --
-    each allocated only when its input requires grad --; the backward only scales them."""
-
-    @staticmethod
-    def forward(ctx, vertices, ior_int, ior_ext, screen_param, texture_param, scene, a, ior, tex, target, weight, out):
-        v = _f64c(vertices.detach(), "vertices")
-        dev = v.device
-        H, W, C = a["height"], a["width"], a["channels"]
-        loss = det.scalar(dev)
-        grad_v = det.acc(v) if a["vertices"] else None
-        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=dev))
-        n_tex = tex.numel()
-        like_s = torch.empty(9, dtype=torch.float64, device=dev)
-        like_t = torch.empty((n_tex + 2) // 3 * 3, dtype=torch.float64, device=dev)      # (a one-channel texture is scattered in threes)
-        grad_s = det.acc(like_s) if screen_param is not None and ctx.needs_input_grad[3] else None
-        grad_t = det.acc(like_t) if texture_param is not None and ctx.needs_input_grad[4] else None
-        count = torch.zeros((), dtype=torch.int64, device=dev)
-        image = torch.empty((H, W, C), dtype=torch.float32, device=dev) if a["want_image"] else None
-        with _on(dev):
-            for y0, y1 in a["bands"]:
-                _lib.check(_lib.lib().drt_render_image_loss_screen(
-                    scene.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
-                    a["law_flags"], a["fresnel"], a["screen"].ctypes.data, tex.data_ptr(), tex.shape[0], tex.shape[1], C, a["void"].ctypes.data,
-                    a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss.data_ptr(), _lib.ptr(grad_v), grad_ior.data_ptr(),
-                    _lib.ptr(image), count.data_ptr(), _lib.ptr(grad_s), _lib.ptr(grad_t), _stream()))
-        out["image"], out["count"] = image, count
-        ctx.ior_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
-        ctx.end_like = tuple((x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (screen_param, texture_param))
-        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
-        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v), det.value(grad_ior, torch.empty(2, dtype=torch.float64)),
-                              None if grad_s is None else det.value(grad_s, like_s), None if grad_t is None else det.value(grad_t, like_t)[:n_tex])
-        return det.value(loss)
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        grad_v, both, grad_s, grad_t = ctx.saved_tensors
-        g_ior, g_end = [None, None], [None, None]
-        for k in (0, 1):
-            if ctx.needs_input_grad[1 + k]:
-                shape, dtype, dev = ctx.ior_like[k]
-                g_ior[k] = (both[k] * g_loss).reshape(shape).to(dtype=dtype, device=dev)
-        for k, g in enumerate((grad_s, grad_t)):
-            if g is not None and ctx.needs_input_grad[3 + k]:
-                shape, dtype, dev = ctx.end_like[k]
-                g_end[k] = (g * g_loss).reshape(shape).to(dtype=dtype, device=dev)
-        if grad_v is None or not ctx.needs_input_grad[0]:
-            g_v = None
-        elif det.SINK is not None and ctx.wide is not None:
-            det.SINK.append((ctx.wide, g_loss))
-            g_v = None
-        else:
-            g_v = grad_v * g_loss
-        return g_v, g_ior[0], g_ior[1], g_end[0], g_end[1], None, None, None, None, None, None, None
-
-
-class _ImageLossCameraFused(torch.autograd.Function):
-    """_ImageLossScreenFused that also differentiates the camera (drt_render_image_loss_camera): ``rinv_param`` /
-    ``kinv_param`` stand for the tensors of ``camera_param`` autograd tracks; ``a["camera"]`` carries their values.  The 21 camera partials
-    are computed here with a unit seed, band after band into one set of accumulators -- allocated only when one of the two requires grad
-    --; the backward scales them and hands them back in the two tensors' shapes: K^-1's nine, and R^-1's twelve as its top three rows (a
-    [4, 4] one gets a zero bottom row, which the renderer does not read)."""
-
-    @staticmethod
-    def forward(ctx, vertices, ior_int, ior_ext, screen_param, texture_param, rinv_param, kinv_param, scene, a, ior, tex, target, weight, out):
-        v = _f64c(vertices.detach(), "vertices")
-        dev = v.device
-        H, W, C = a["height"], a["width"], a["channels"]
-        loss = det.scalar(dev)
-        grad_v = det.acc(v) if a["vertices"] else None
-        tracked_ior = any(ctx.needs_input_grad[1:3])
-        grad_ior = det.acc(torch.empty(2, dtype=torch.float64, device=dev)) if tracked_ior else None
-        n_tex = tex.numel()
-        like_s = torch.empty(9, dtype=torch.float64, device=dev)
-        like_t = torch.empty((n_tex + 2) // 3 * 3, dtype=torch.float64, device=dev)      # (a one-channel texture is scattered in threes)
-        like_c = torch.empty(21, dtype=torch.float64, device=dev)
-        grad_s = det.acc(like_s) if screen_param is not None and ctx.needs_input_grad[3] else None
-        grad_t = det.acc(like_t) if texture_param is not None and ctx.needs_input_grad[4] else None
-        grad_c = det.acc(like_c) if any(ctx.needs_input_grad[5:7]) else None
-        count = torch.zeros((), dtype=torch.int64, device=dev)
-        image = torch.empty((H, W, C), dtype=torch.float32, device=dev) if a["want_image"] else None
-        with _on(dev):
-            for y0, y1 in a["bands"]:
-                _lib.check(_lib.lib().drt_render_image_loss_camera(
-                    scene.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
-                    a["law_flags"], a["fresnel"], a["screen"].ctypes.data, tex.data_ptr(), tex.shape[0], tex.shape[1], C, a["void"].ctypes.data,
-                    a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss.data_ptr(), _lib.ptr(grad_v), _lib.ptr(grad_ior),
-                    _lib.ptr(image), count.data_ptr(), _lib.ptr(grad_s), _lib.ptr(grad_t), _lib.ptr(grad_c), _stream()))
-        out["image"], out["count"] = image, count
-        like = lambda x: (x.shape, x.dtype, x.device) if isinstance(x, torch.Tensor) else None      # noqa: E731
-        ctx.ior_like = (like(ior_int), like(ior_ext))
-        ctx.end_like = (like(screen_param), like(texture_param))
-        ctx.cam_like = (like(rinv_param), like(kinv_param))
-        ctx.wide = grad_v if grad_v is not None and grad_v.dtype == torch.int64 else None
-        ctx.save_for_backward(None if grad_v is None else det.value(grad_v, v),
-                              None if grad_ior is None else det.value(grad_ior, torch.empty(2, dtype=torch.float64)),
-                              None if grad_s is None else det.value(grad_s, like_s), None if grad_t is None else det.value(grad_t, like_t)[:n_tex],
-                              None if grad_c is None else det.value(grad_c, like_c))
-        return det.value(loss)
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        grad_v, both, grad_s, grad_t, grad_c = ctx.saved_tensors
-        g_ior, g_end, g_cam = [None, None], [None, None], [None, None]
-        for k in (0, 1):
-            if both is not None and ctx.needs_input_grad[1 + k]:
-                shape, dtype, dev = ctx.ior_like[k]
-                g_ior[k] = (both[k] * g_loss).reshape(shape).to(dtype=dtype, device=dev)
-        for k, g in enumerate((grad_s, grad_t)):
-            if g is not None and ctx.needs_input_grad[3 + k]:
-                shape, dtype, dev = ctx.end_like[k]
-                g_end[k] = (g * g_loss).reshape(shape).to(dtype=dtype, device=dev)
-        if grad_c is not None:
-            scaled = grad_c * g_loss
-            if ctx.needs_input_grad[5]:
-                shape, dtype, dev = ctx.cam_like[0]
-                rows = scaled[9:].reshape(3, 4)
-                if tuple(shape) == (4, 4):
-                    rows = torch.cat([rows, torch.zeros((1, 4), dtype=rows.dtype, device=rows.device)])
-                g_cam[0] = rows.to(dtype=dtype, device=dev)
-            if ctx.needs_input_grad[6]:
-                shape, dtype, dev = ctx.cam_like[1]
-                g_cam[1] = scaled[:9].reshape(3, 3).to(dtype=dtype, device=dev)
-        if grad_v is None or not ctx.needs_input_grad[0]:
-            g_v = None
-        elif det.SINK is not None and ctx.wide is not None:
-            det.SINK.append((ctx.wide, g_loss))
-            g_v = None
-        else:
-            g_v = grad_v * g_loss
-        return g_v, g_ior[0], g_ior[1], g_end[0], g_end[1], g_cam[0], g_cam[1], None, None, None, None, None, None, None
+                                     _lib.ptr(cells.get(_VERTS)), cells["ior"].data_ptr(), count.data_ptr(), a["bands"])
+    return _Term(v.device, _verts_ior_accs(v, a["vertices"]), enqueue, ((_VERTS, None),) + _IOR_FEEDS, count)
 
 
 def ray_loss(out_ori, out_dir, mask, screen_pixel, valid):
@@ -1369,25 +1256,24 @@ class Scene(StepwiseMixin):
         from . import render as _render
         a = _render.check_image_loss_args(camera_M, height, width, screen, texture, target, weight, ior_int, ior_ext, vertices, want_image, supersample,
                                           max_bounces, tir, refraction, fresnel, void, invalid, max_samples, screen_param, texture_param, camera_param)
-        given = [intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext]
-        ior = tuple(_ior_host(x, name) for x, name in zip(given, ("ior_int", "ior_ext")))
-        tracked = tuple(x if isinstance(x, torch.Tensor) else None for x in given)
+        ior, tracked = _ior_args(intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext)
         dev = self._dev
         with _on(dev):
             tex = torch.as_tensor(a["texture"], device=dev).to(torch.float32).contiguous()
             tgt = torch.as_tensor(a["target"], device=dev)
             tgt = (tgt.to(torch.float32) / 255.0 if tgt.dtype == torch.uint8 else tgt).reshape(a["height"], a["width"], a["channels"]).contiguous()
             wgt = None if a["weight"] is None else torch.as_tensor(a["weight"], device=dev).contiguous()
-        out = {}
-        verts = self.vertices if a["vertices"] else self.vertices.detach()
-        if camera_param is not None:
-            loss = _ImageLossCameraFused.apply(verts, *tracked, screen_param, texture_param, camera_param[0], camera_param[1], self, a, ior, tex, tgt, wgt, out)
-        elif screen_param is None and texture_param is None:
-            loss = _ImageLossFused.apply(verts, *tracked, self, a, ior, tex, tgt, wgt, out)
+        inputs = (self.vertices if a["vertices"] else self.vertices.detach(),) + tracked
+        if camera_param is not None:         # (a keyword that is given takes its entry point, whether or not its tensor requires grad)
+            entry, inputs = "camera", inputs + (screen_param, texture_param, camera_param[0], camera_param[1])
+        elif screen_param is not None or texture_param is not None:
+            entry, inputs = "screen", inputs + (screen_param, texture_param)
         else:
-            loss = _ImageLossScreenFused.apply(verts, *tracked, screen_param, texture_param, self, a, ior, tex, tgt, wgt, out)
-        self.last_image_count = out["count"]
-        return (loss, out["image"]) if a["want_image"] else loss
+            entry = "plain"
+        term = _image_term(self, a, ior, tex, tgt, wgt, entry)
+        loss = _UnitSeedTerm.apply(term, *inputs)
+        self.last_image_count = term.count
+        return (loss, term.image) if a["want_image"] else loss
 
     def bind_image_views(self, cameras, height, width, screens, targets, weights=None):
         """A handle for the views of a capture of photographs (``render.ImageViews``) for ``image_loss_views_fused``: ``cameras`` a list of
@@ -1412,14 +1298,12 @@ class Scene(StepwiseMixin):
                                           void, invalid, max_samples)
         if binding.scene is not self:
             raise ValueError("binding was made by another scene's bind_image_views")
-        given = [intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext]
-        ior = tuple(_ior_host(x, name) for x, name in zip(given, ("ior_int", "ior_ext")))
-        tracked = tuple(x if isinstance(x, torch.Tensor) else None for x in given)
+        ior, tracked = _ior_args(intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext)
         with _on(self._dev):
             tex = torch.as_tensor(a["texture"], device=self._dev).to(torch.float32).contiguous()
-        out = {}
-        loss = _ImageLossViewsFused.apply(self.vertices if a["vertices"] else self.vertices.detach(), *tracked, self, binding, a, ior, tex, out)
-        self.last_image_count = out["count"]
+        term = _image_views_term(self, binding, a, ior, tex, (a["max_bounces"], tir, refraction))
+        loss = _UnitSeedTerm.apply(term, self.vertices if a["vertices"] else self.vertices.detach(), *tracked)
+        self.last_image_count = term.count
         return loss
 
     @staticmethod
@@ -1452,7 +1336,10 @@ class Scene(StepwiseMixin):
             origin, ray_dir = origin.origin, origin.ray_dir
         ior = self._check_paths_call("paths_ray_loss_fused", origin, ray_dir, max_bounces, tir, refraction)
         _stats["paths_fused_calls"] += 1
-        return _RenderRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, (int(max_bounces), tir, refraction), None)
+        term = _ray_term(self, origin, ray_dir, screen_pixel, valid, ior, (int(max_bounces), tir, refraction), None)
+        loss = _UnitSeedTerm.apply(term, self.vertices)
+        self.last_path_count = term.count
+        return loss
 
     def paths_ray_loss_ior_fused(self, origin, ray_dir, screen_pixel, valid, ior_int, ior_ext=None, max_bounces=4, tir="reflect",
                                  refraction="reference", vertices=True):
@@ -1471,13 +1358,12 @@ class Scene(StepwiseMixin):
         if _wants_input_grads(origin, ray_dir):
             raise NotImplementedError("paths_ray_loss_ior_fused differentiates the vertices and the IORs: origin and ray_dir must not require "
                                       "grad (render_transparent has those gradients for the two-bounce path)")
-        if ior_ext is None:
-            ior_ext = _ior_host(extIOR, "extIOR")
-        ior = (_ior_host(ior_int, "ior_int"), _ior_host(ior_ext, "ior_ext"))
-        tracked = tuple(x if isinstance(x, torch.Tensor) else None for x in (ior_int, ior_ext))
+        ior, tracked = _ior_args(ior_int, _ior_host(extIOR, "extIOR") if ior_ext is None else ior_ext)
         _stats["paths_ior_fused_calls"] += 1
-        return _PathsRayLossIorFused.apply(self.vertices if vertices else self.vertices.detach(), *tracked, origin, ray_dir, screen_pixel, valid,
-                                           self, ior, int(max_bounces), _law_flags(tir, refraction), bool(vertices))
+        term = _paths_ior_term(self, origin, ray_dir, screen_pixel, valid, ior, int(max_bounces), _law_flags(tir, refraction), bool(vertices))
+        loss = _UnitSeedTerm.apply(term, self.vertices if vertices else self.vertices.detach(), *tracked)
+        self.last_path_count = term.count
+        return loss
 
     def ray_loss_fused(self, origin, ray_dir, screen_pixel, valid):
         """ray_loss of this view without materialising out_ori/out_dir/mask.  The fused kernel differentiates the vertices only: when
@@ -1488,10 +1374,10 @@ class Scene(StepwiseMixin):
             out_ori, out_dir, mask = self.render_transparent(origin, ray_dir)
             return ray_loss(out_ori, out_dir, mask, screen_pixel, valid)
         ior = _ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR")
+        grid = None
         if isinstance(origin, RayBinding):
-            b = origin
-            return _RenderRayLossFused.apply(self.vertices, b.origin, b.ray_dir, screen_pixel, valid, self, ior, None, b._grid())
-        return _RenderRayLossFused.apply(self.vertices, origin, ray_dir, screen_pixel, valid, self, ior, None, None)
+            origin, ray_dir, grid = origin.origin, origin.ray_dir, origin._grid()
+        return _UnitSeedTerm.apply(_ray_term(self, origin, ray_dir, screen_pixel, valid, ior, None, grid), self.vertices)
 
     # ------------------------------------------------------------------ smoothness branch
     def dihedral_angle(self):

@@ -16,7 +16,7 @@ import image_loss_cases as cases
 import image_ref
 import image_screen_ref
 from conftest import IOR
-from drt_amd import calibrate, det, diffrender as Render, render
+from drt_amd import _lib, calibrate, det, diffrender as Render, render
 
 pytestmark = pytest.mark.gpu
 EXT = cases.EXT
@@ -138,25 +138,30 @@ def test_the_other_gradients_keep_their_bits_in_deterministic_mode(hand_scene, d
     _check_against(got, ref_mod.reference(name, LAWS[2], True))
 
 
-def test_without_the_keyword_the_call_is_the_parents(hand_scene, deterministic):
-    """The method's route without camera_param is _ImageLossFused / _ImageLossScreenFused, as before; and the new entry point with a null
-    camera accumulator -- the new Function with nothing of the camera to track -- gives those routes' bits."""
+def test_without_the_keyword_the_call_is_the_parents(hand_scene, deterministic, monkeypatch):
+    """The method's route without camera_param is the "plain" / "screen" term, as before; and the camera entry point with a null camera
+    accumulator -- the "camera" term with nothing of the camera to track -- gives those routes' bits."""
     sc = image_cases.scene("v5")
     a = render.check_image_loss_args(sc["camera_M"], sc["height"], sc["width"], sc["screen"], sc["texture"], cases.target("v5", LAWS[1], True),
                                      supersample=sc["s"], max_bounces=6, tir="reflect", void=sc["void"], invalid=sc["invalid"])
     tex, tgt = torch.as_tensor(a["texture"], device="cuda"), torch.as_tensor(a["target"], device="cuda")
+    lib, entries = _lib.lib(), []
+    for name in ("drt_render_image_loss", "drt_render_image_loss_screen", "drt_render_image_loss_camera"):
+        monkeypatch.setattr(lib, name, lambda *args, name=name, fn=getattr(lib, name): entries.append(name) or fn(*args))
     for ends in (False, True):
         got = []
-        old = Render._ImageLossScreenFused if ends else Render._ImageLossFused
-        for fn, extra in ((old, (None, None) if ends else ()), (Render._ImageLossCameraFused, (None, None, None, None))):
+        del entries[:]
+        old = "screen" if ends else "plain"
+        for entry, extra in ((old, (None, None) if ends else ()), ("camera", (None, None, None, None))):
             ii = torch.tensor(IOR, dtype=torch.float64, device="cuda", requires_grad=True)
             T = torch.as_tensor(a["texture"], dtype=torch.float64, device="cuda").requires_grad_(True)
             if ends:
                 extra = (None, T) + extra[2:]
-            out = {}
-            loss = fn.apply(hand_scene.vertices, ii, None, *extra, hand_scene, a, (IOR, EXT), tex, tgt, None, out)
+            term = Render._image_term(hand_scene, a, (IOR, EXT), tex, tgt, None, entry)
+            loss = Render._UnitSeedTerm.apply(term, hand_scene.vertices, ii, None, *extra)
             wrt = [hand_scene.vertices, ii] + ([T] if ends else [])
-            got.append((loss.detach().clone(), out["count"].clone()) + tuple(g.clone() for g in torch.autograd.grad(loss, wrt)))
+            got.append((loss.detach().clone(), term.count.clone()) + tuple(g.clone() for g in torch.autograd.grad(loss, wrt)))
+        assert list(dict.fromkeys(entries)) == ["drt_render_image_loss" + ("_screen" if ends else ""), "drt_render_image_loss_camera"]      # two different native entry points
         assert float(got[0][0]) > 0 and got[0][2].any() and got[0][3] != 0
         for x, y in zip(*got):
             assert torch.equal(x, y)
@@ -205,8 +210,8 @@ def test_a_captured_replay_gives_the_eager_bits(deterministic):
     tex, tgt = torch.as_tensor(a["texture"], device="cuda"), torch.as_tensor(a["target"], device="cuda")
 
     def step():
-        out = {}
-        loss = Render._ImageLossCameraFused.apply(scene.vertices, None, None, None, None, Rinv, Kinv, scene, a, (IOR, EXT), tex, tgt, None, out)
+        term = Render._image_term(scene, a, (IOR, EXT), tex, tgt, None, "camera")
+        loss = Render._UnitSeedTerm.apply(term, scene.vertices, None, None, None, None, Rinv, Kinv)
         return (loss.detach(),) + torch.autograd.grad(loss, [scene.vertices, Rinv, Kinv])
 
     eager = [t.clone() for t in step()]
@@ -227,7 +232,6 @@ def test_the_first_growth_of_the_seed_buffer_under_capture_is_refused(determinis
     """A scene whose every other buffer has its size from an eager call WITHOUT camera_param: the first camera call is the first to
     need the camera-ray seeds, and inside a stream capture it is refused with the message of the pixel seeds; after one eager camera
     call the same capture goes through (the replay test above)."""
-    from drt_amd import _lib
     scene = _scene()
     sc = image_cases.scene("v5")
     Rinv, Kinv = (m.cuda().requires_grad_(True) for m in ref_mod.camera_tensors(sc["camera_M"]))
@@ -236,8 +240,8 @@ def test_the_first_growth_of_the_seed_buffer_under_capture_is_refused(determinis
     tex, tgt = torch.as_tensor(a["texture"], device="cuda"), torch.as_tensor(a["target"], device="cuda")
 
     def step(camera):
-        return Render._ImageLossCameraFused.apply(scene.vertices, None, None, None, None, *((Rinv, Kinv) if camera else (None, None)), scene, a, (IOR, EXT), tex,
-                                                  tgt, None, {})
+        term = Render._image_term(scene, a, (IOR, EXT), tex, tgt, None, "camera")
+        return Render._UnitSeedTerm.apply(term, scene.vertices, None, None, None, None, *((Rinv, Kinv) if camera else (None, None)))
 
     plain = step(False).detach().clone()
     torch.cuda.synchronize()

@@ -13,7 +13,7 @@ import image_loss_cases as cases
 import image_ref
 import image_screen_ref as ref_mod
 from conftest import IOR
-from drt_amd import calibrate, det, diffrender as Render, render
+from drt_amd import _lib, calibrate, det, diffrender as Render, render
 
 pytestmark = pytest.mark.gpu
 EXT = cases.EXT
@@ -120,19 +120,23 @@ def test_the_old_gradients_keep_their_bits_in_deterministic_mode(hand_scene, det
     _check_against(got, ref_mod.reference(name, LAWS[2], True))
 
 
-def test_without_the_keywords_the_call_is_todays(hand_scene, deterministic):
-    """The method's route without the keywords is _ImageLossFused / drt_render_image_loss, as before; and the new entry point with both
-    accumulators null -- the new Function with nothing to track -- gives that route's bits."""
+def test_without_the_keywords_the_call_is_todays(hand_scene, deterministic, monkeypatch):
+    """The method's route without the keywords is the "plain" term / drt_render_image_loss, as before; and the screen entry point with both
+    accumulators null -- the "screen" term with nothing to track -- gives that route's bits."""
     sc = image_cases.scene("v5")
     a = render.check_image_loss_args(sc["camera_M"], sc["height"], sc["width"], sc["screen"], sc["texture"], cases.target("v5", LAWS[1], True),
                                      supersample=sc["s"], max_bounces=6, tir="reflect", void=sc["void"], invalid=sc["invalid"])
     tex, tgt = torch.as_tensor(a["texture"], device="cuda"), torch.as_tensor(a["target"], device="cuda")
-    got = []
-    for fn, extra in ((Render._ImageLossFused, ()), (Render._ImageLossScreenFused, (None, None))):
+    got, entries = [], []
+    lib = _lib.lib()
+    for name in ("drt_render_image_loss", "drt_render_image_loss_screen"):
+        monkeypatch.setattr(lib, name, lambda *args, name=name, fn=getattr(lib, name): entries.append(name) or fn(*args))
+    for entry, extra in (("plain", ()), ("screen", (None, None))):
         ii = torch.tensor(IOR, dtype=torch.float64, device="cuda", requires_grad=True)
-        out = {}
-        loss = fn.apply(hand_scene.vertices, ii, None, *extra, hand_scene, a, (IOR, EXT), tex, tgt, None, out)
-        got.append((loss.detach().clone(), out["count"].clone()) + tuple(g.clone() for g in torch.autograd.grad(loss, [hand_scene.vertices, ii])))
+        term = Render._image_term(hand_scene, a, (IOR, EXT), tex, tgt, None, entry)
+        loss = Render._UnitSeedTerm.apply(term, hand_scene.vertices, ii, None, *extra)
+        got.append((loss.detach().clone(), term.count.clone()) + tuple(g.clone() for g in torch.autograd.grad(loss, [hand_scene.vertices, ii])))
+    assert list(dict.fromkeys(entries)) == ["drt_render_image_loss", "drt_render_image_loss_screen"]          # two different native entry points
     assert float(got[0][0]) > 0 and got[0][2].any() and got[0][3] != 0
     for x, y in zip(*got):
         assert torch.equal(x, y)

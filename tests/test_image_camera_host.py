@@ -230,7 +230,7 @@ def test_entry_point_is_declared_everywhere():
     assert version and int(version.group(1)) >= 12
     wave = open(os.path.join(ROOT, "drt_amd", "csrc", "drt_image_wave.h")).read()
     assert "int launch_image_camera_bwd(" in wave and "int launch_image_loss_bwd_camera(" in wave
-    assert callable(diffrender._ImageLossCameraFused.apply)
+    assert callable(diffrender._UnitSeedTerm.apply)
 
 
 def _args():
