@@ -11,8 +11,9 @@ derivative is right well away from it, and the fit bisects a bracket on that sig
 ``fit_screen`` fits the POSE of the textured screen behind the object -- placed by hand, calibrated separately -- to plain photographs:
 a rigid motion of the initial screen under the photometric loss of ``Scene.image_loss_fused(..., screen_param=)``,
 mesh and IORs fixed.  ``fit_camera`` does the same for the POSE of the camera of one photograph -- a rotation about the camera's own
-centre and a translation of the calibrated camera -- through ``Scene.image_loss_fused(..., camera_param=)``.  Neither has
-a command line.
+centre and a translation of the calibrated camera -- through ``Scene.image_loss_fused(..., camera_param=)``.
+``fit_absorption`` fits the Beer-Lambert absorption coefficients of the glass through ``Scene.image_loss_fused(..., absorption=)``
+(DESIGN.md 10.7).  None of the three has a command line.
 """
 from __future__ import annotations
 
@@ -161,6 +162,49 @@ def fit_screen(scene, views, screen, texture, *, steps, lr, **law):
     six, history = fit_pose(loss_of, screen, tex_h, tex_w, steps, lr)
     rows = screen_pose(screen, tex_h, tex_w, six).numpy()
     return render.Screen(rows[0], rows[1], rows[2]), history
+
+
+def fit_absorption(scene, views, screen, texture, *, steps, lr, **law):
+    """The absorption coefficients of the glass of ``scene`` (mesh and IOR fixed) from photographs: C numbers ``sigma >= 0`` per unit of
+    mesh length that minimise the photometric loss summed over ``views`` = [(camera_M, photograph[, weight]), ...] --
+    ``Scene.image_loss_fused(camera_M, H, W, screen, texture, photograph, absorption=sigma, vertices=False, **law)`` with H, W the
+    photograph's; the resolve kernel hands back the C partials, no path is recomputed.  ``steps`` Adam steps of ``lr`` (in units of sigma)
+    from 0, each followed by the projection onto ``sigma >= 0``.  ``law``: the law, IOR and band keywords of ``image_loss_fused``.  Returns (sigma float64 numpy [C]: that of the smallest loss seen, the loss history: one float
+    per step, evaluated BEFORE that step's update)."""
+    from . import render
+    if not isinstance(screen, render.Screen):
+        raise ValueError(f"screen must be a drt_amd.render.Screen, got {type(screen).__name__}")
+    views = [tuple(v) for v in views]
+    if not views or any(len(v) not in (2, 3) for v in views):
+        raise ValueError("views must be a non-empty list of (camera_M, photograph) or (camera_M, photograph, weight)")
+    for bad in ("absorption", "screen_param", "texture_param", "camera_param", "vertices", "want_image"):
+        if bad in law:
+            raise ValueError(f"fit_absorption sets {bad} itself")
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError(f"steps must be a positive integer, got {steps!r}")
+    if not (float(lr) > 0.0):
+        raise ValueError(f"lr must be positive, got {lr!r}")
+    tex = render.check_texture(texture)
+    sigma = torch.zeros(int(tex.shape[2]), dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.Adam([sigma], lr=float(lr))
+    history, best = [], (None, None)
+    for _ in range(int(steps)):
+        opt.zero_grad()
+        total = None
+        for v in views:
+            photo = v[1]
+            term = scene.image_loss_fused(v[0], int(photo.shape[0]), int(photo.shape[1]), screen, tex, photo, weight=v[2] if len(v) == 3 else None,
+                                          vertices=False, absorption=sigma, **law).to(sigma.device)
+            total = term if total is None else total + term
+        value = float(total.detach())
+        if best[0] is None or value < best[0]:
+            best = (value, sigma.detach().clone())
+        history.append(value)
+        total.backward()
+        opt.step()
+        with torch.no_grad():
+            sigma.clamp_(min=0.0)
+    return best[1].numpy(), history
 
 
 def camera_pose(camera_M, six, centre=None, extent=1.0):

@@ -169,18 +169,14 @@ int image_call_check(const double* camera21, int height, int width, int y0, int 
     return DRT_OK;
 }
 
-namespace {
-
 // image_forward's own start: k_image_start with the camera of the call (`src`)
-void image_start_one(const ImageStartArgs& a, const void* src) {
+void image_start_call(const ImageStartArgs& a, const void* src) {
     const ImageCall& c = *static_cast<const ImageCall*>(src);
     k_image_start<<<a.grid, kPathBlock, 0, a.st>>>(a.nodes, a.n_tris, c.cam, c.band, a.park_ori, a.park_dir, a.thr, a.state, a.hits, a.out, a.count);
 }
 
-}  // namespace
-
 int image_forward_from(drt_scene* s, const double* d_verts, const ImageCall& c, bool keep_tape, hipStream_t st, const char* who, ImageStartFn start,
-                       const void* src) {
+                       const void* src, ImageShadeFn shade_fn, const void* shade_src) {
     { int rc = ensure_paths_ws(s, c.n, st, who); if (rc) return rc; }
     { int rc = ensure_paths_fused_ws(s, c.n, st, who); if (rc) return rc; }
     { int rc = ensure_image_thr(s, c.n, st, who); if (rc) return rc; }
@@ -197,14 +193,18 @@ int image_forward_from(drt_scene* s, const double* d_verts, const ImageCall& c, 
         const ImageShade shade = image_shade_kernel(c.snell, c.fresnel, keep_tape);
         int32_t* const tape = keep_tape ? w.tape : nullptr;
         trace_lists(s, w, pc.tc, st, c.max_bounces, [&](int k, const RayList& in, const unsigned* n_in, const RayList& out, unsigned* n_out) {
-            shade<<<gs, kPathBlock, 0, st>>>(pc, (int64_t)c.n, k, c.max_bounces, c.reflect, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state, w.hits, tape);
+            if (shade_fn)
+                shade_fn(ImageShadeArgs{pc, (int64_t)c.n, k, c.max_bounces, c.reflect, c.snell, c.fresnel, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state,
+                                        w.hits, tape, gs, st}, shade_src);
+            else
+                shade<<<gs, kPathBlock, 0, st>>>(pc, (int64_t)c.n, k, c.max_bounces, c.reflect, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state, w.hits, tape);
         });
     }
     return DRT_OK;
 }
 
 int image_forward(drt_scene* s, const double* d_verts, const ImageCall& c, bool keep_tape, hipStream_t st, const char* who) {
-    return image_forward_from(s, d_verts, c, keep_tape, st, who, image_start_one, &c);
+    return image_forward_from(s, d_verts, c, keep_tape, st, who, image_start_call, &c);
 }
 
 extern "C" {

@@ -60,8 +60,29 @@ struct ImageStartArgs {
     hipStream_t st;
 };
 using ImageStartFn = void (*)(const ImageStartArgs& a, const void* src);
+// ... and with the shade kernel of the caller's choice (drt_image_absorb.hip: k_image_shade plus the interior length): `shade` launches on
+// a.st, with a.grid blocks of kPathBlock threads, a kernel that does for list k what k_image_shade<snell, fresnel, tape != null> does;
+// `shade_src` is handed through to it.  Null, the default: k_image_shade from drt_image.hip's own table, what every call launched before.
+struct ImageShadeArgs {
+    PathCtx pc;
+    int64_t n_rays;
+    int k, max_bounces;
+    bool reflect, snell, fresnel;
+    RayList in;
+    const unsigned* n_in;
+    RayList out;
+    unsigned* n_out;
+    double *park_ori, *park_dir, *thr;
+    uint8_t *state, *hits;
+    int32_t* tape;                 // null: no tape is kept
+    int grid;
+    hipStream_t st;
+};
+using ImageShadeFn = void (*)(const ImageShadeArgs& a, const void* shade_src);
 int image_forward_from(drt_scene* s, const double* d_verts, const ImageCall& call, bool keep_tape, hipStream_t st, const char* who, ImageStartFn start,
-                       const void* src);
+                       const void* src, ImageShadeFn shade = nullptr, const void* shade_src = nullptr);
+// image_forward's own start (k_image_start with the camera of the call, `src` = the ImageCall), for callers that bring a shade kernel only
+void image_start_call(const ImageStartArgs& a, const void* src);
 
 // The workspace of the loss calls behind drt_scene::image_loss_ws (drt_image_loss.hip; drt_image_views.hip shares the pixel seeds), and its
 // growth to n_seed doubles of pixel seeds and n_cam doubles of camera-ray seeds (0: none wanted) -- never inside a stream capture.

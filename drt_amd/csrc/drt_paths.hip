@@ -349,6 +349,7 @@ void paths_free(drt_scene* s) {
     (void)hipFree(w->redo); (void)hipFree(w->state); (void)hipFree(w->cnt); (void)hipFree(w->slow_stack);
     (void)hipFree(w->park); (void)hipFree(w->tape); (void)hipFree(w->hits);
     (void)hipFree(w->thr);
+    (void)hipFree(w->len);
     delete w;
     s->paths_ws = nullptr;
 }

@@ -31,6 +31,9 @@ struct PathsWs {
     // the forward wavefront of the image only (drt_image.hip image_forward), beside the rows of the one-pass form: one float64 throughput per sample
     int64_t thr_cap = 0;
     double* thr = nullptr;
+    // ... and, under absorption only (drt_image_absorb.hip), one float64 interior length per sample, grown like the throughputs
+    int64_t len_cap = 0;
+    double* len = nullptr;
 };
 
 // each block takes one contiguous run of [0, n), so that what it appends stays in input order

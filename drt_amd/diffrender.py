@@ -844,6 +844,23 @@ def enqueue_image_term(scene, vertices, a, ior, texture, target, weight, loss_pt
     return [vertices, texture, target, weight]
 
 
+def enqueue_image_absorb_term(scene, vertices, a, ior, texture, target, weight, loss_ptr, grad_ptr=None, grad_ior_ptr=None, image_ptr=None, count_ptr=None,
+                              sigma_ptr=None):
+    """``enqueue_image_term`` for absorbing glass: ONE view's photometric image term under ``a["absorption"]`` (C float64
+    coefficients on the host, checked by ``render.check_absorption``), band after band into one set of accumulators, on the current
+    stream; the one place that packs the arguments of drt_render_image_loss_absorb.  ``sigma_ptr``: C more accumulators, for
+    d loss / d sigma, addressed like ``grad_ior_ptr``; like every ``*_ptr`` but the first it may be None.  The caller is inside
+    ``_on(device)``.  Returns what the enqueued kernels read, for the caller to keep alive."""
+    fn, H, W, C = _lib.lib().drt_render_image_loss_absorb, a["height"], a["width"], a["channels"]
+    for y0, y1 in a["bands"]:
+        _lib.check(fn(
+            scene.optix_mesh._h, vertices.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
+            a["law_flags"], a["fresnel"], a["screen"].ctypes.data, texture.data_ptr(), texture.shape[0], texture.shape[1], C, a["void"].ctypes.data,
+            a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss_ptr, grad_ptr, grad_ior_ptr, image_ptr, count_ptr,
+            a["absorption"].ctypes.data, sigma_ptr, _stream()))
+    return [vertices, texture, target, weight]
+
+
 def enqueue_image_views_term(scene, vertices, binding, view_ids, texture, law, supersample, fresnel, void, invalid, ior, loss_ptr, grad_ptr,
                              grad_ior_ptr=None, count_ptr=None, bands=None):
     """Enqueues the photometric image term of the listed views of ``binding`` (a ``render.ImageViews``) -- the SUM over ``view_ids`` of one
@@ -985,6 +1002,24 @@ def _image_term(scene, a, ior, tex, target, weight, entry="plain"):
             enqueue_image_term(scene, v, a, ior, tex, target, weight, loss.data_ptr(), _lib.ptr(cells.get(_VERTS)), _lib.ptr(cells.get("ior")), _lib.ptr(image),
                                count.data_ptr(), *(_lib.ptr(cells.get(k)) for k in ("screen", "texture", "camera")), entry=entry)
     return _Term(dev, accs, enqueue, feeds, count, image)
+
+
+def _image_absorb_term(scene, a, ior, tex, target, weight):
+    """The term of image_loss_fused under an absorption (``enqueue_image_absorb_term``) for the inputs (vertices,
+    ior_int, ior_ext, absorption): the vertex accumulator follows ``a["vertices"]``, the IOR pair is always there, the C sigma
+    accumulators only when the absorption is a tensor that needs a gradient."""
+    v = _f64c(scene.vertices.detach(), "vertices")
+    dev = v.device
+    accs = _verts_ior_accs(v, a["vertices"])
+    accs["sigma"] = (torch.empty(a["channels"], dtype=torch.float64, device=dev), (3,))
+    count = torch.zeros((), dtype=torch.int64, device=dev)
+    image = torch.empty((a["height"], a["width"], a["channels"]), dtype=torch.float32, device=dev) if a["want_image"] else None
+
+    def enqueue(loss, cells):
+        with _on(dev):
+            enqueue_image_absorb_term(scene, v, a, ior, tex, target, weight, loss.data_ptr(), _lib.ptr(cells.get(_VERTS)), _lib.ptr(cells.get("ior")),
+                                      _lib.ptr(image), count.data_ptr(), _lib.ptr(cells.get("sigma")))
+    return _Term(dev, accs, enqueue, ((_VERTS, None),) + _IOR_FEEDS + (("sigma", None),), count, image)
 
 
 def _image_views_term(scene, binding, a, ior, tex, law):
@@ -1192,7 +1227,7 @@ class Scene(StepwiseMixin):
         return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), _law_flags(tir, refraction))
 
     def render_image(self, camera_M, height, width, screen, texture, *, supersample=1, max_bounces=2, tir="drop", refraction="reference",
-                     fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False):
+                     fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False, absorption=None):
         """What the pinhole camera ``camera_M`` = (R, K, R^-1, K^-1) sees of a textured planar screen through this mesh: a float32 image
         ``[height, width, C]`` on the device (drt_render_image; csrc/drt_image.h and DESIGN.md 10.2 state the law).  ``screen``: a
         ``drt_amd.render.Screen``; ``texture``: float32 ``[Th, Tw, C]`` (or ``[Th, Tw]``), C in {1, 3}, numpy or a device tensor.
@@ -1204,10 +1239,15 @@ class Scene(StepwiseMixin):
         ``invalid`` (each one number or C of them; the fills are not weighted).  The image is rendered in bands of at most
         ``max_samples`` samples (158 B of workspace each, shared with the path calls); the bands give the bits of the whole.  ``want_planes``: also return
         float32 ``[height, width]`` planes ``hit`` (share of samples with an interaction) and ``through`` (share whose path completed).
-        Forward only: the image has no autograd graph and no gradient w.r.t. anything.  Two calls give the same bits."""
+        Forward only: the image has no autograd graph and no gradient w.r.t. anything.  Two calls give the same bits.
+        ``absorption``: None (clear glass: the call is what it was), or Beer-Lambert absorption coefficients per unit of mesh length --
+        one number (every channel), C numbers, or a float64 tensor ``[C]``, each finite and >= 0: a through sample is also weighted by
+        ``exp(-absorption_ch L)``, ``L`` the length its path travels inside the object (drt_render_image_absorb; csrc/drt_image_absorb.h
+        and DESIGN.md 10.7 state the law; 8 B more workspace per sample).  ``want_planes`` then returns a fourth plane, ``length``: the
+        mean of ``L`` over the pixel's through samples, 0 where there are none."""
         from . import render as _render
         a = _render.check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid,
-                                      max_samples, want_planes)
+                                      max_samples, want_planes, absorption)
         ior = _ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR")
         dev = self._dev
         with _on(dev):
@@ -1216,6 +1256,15 @@ class Scene(StepwiseMixin):
             H, W, C = a["height"], a["width"], a["channels"]
             image = torch.empty((H, W, C), dtype=torch.float32, device=dev)
             planes = tuple(torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(2)) if a["want_planes"] else (None, None)
+            if a["absorption"] is not None:
+                length = torch.empty((H, W), dtype=torch.float32, device=dev) if a["want_planes"] else None
+                for y0, y1 in a["bands"]:
+                    _lib.check(_lib.lib().drt_render_image_absorb(
+                        self.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
+                        a["law_flags"], a["fresnel"], a["screen"].ctypes.data, tex.data_ptr(), tex.shape[0], tex.shape[1], C, a["void"].ctypes.data,
+                        a["invalid"].ctypes.data, image.data_ptr(), _lib.ptr(planes[0]), _lib.ptr(planes[1]), a["absorption"].ctypes.data,
+                        _lib.ptr(length), _stream()))
+                return (image,) + planes + (length,) if a["want_planes"] else image
             for y0, y1 in a["bands"]:
                 _lib.check(_lib.lib().drt_render_image(
                     self.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
@@ -1225,7 +1274,7 @@ class Scene(StepwiseMixin):
 
     def image_loss_fused(self, camera_M, height, width, screen, texture, target, *, weight=None, ior_int=None, ior_ext=None, vertices=True,
                          want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
-                         invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None):
+                         invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None, absorption=None):
         """The photometric loss of ``render_image`` against a photograph: sum over pixels and channels of ``w (I - target)^2`` with ``I``
         the float64 pixel mean ``render_image`` rounds to float32 -- as a scalar, with its vertex gradient AND d loss / d (ior_int,
         ior_ext) computed alongside with a unit seed and scaled in the backward pass (drt_render_image_loss; csrc/drt_image_loss.h and
@@ -1252,10 +1301,16 @@ class Scene(StepwiseMixin):
         renderer reads are independent inputs, and the gradient comes back in the tensors' own shapes (a ``[4, 4]`` ``Rinv`` gets a zero
         bottom row).  Direct and through samples both carry it (drt_render_image_loss_camera; csrc/drt_image_camera.h and DESIGN.md 10.5
         state the law); silhouettes are not differentiated.  It composes with the other keywords, ``vertices`` and tensor IORs, whose
-        gradients are the same with and without it.  Without any of the three keywords the call is what it was."""
+        gradients are the same with and without it.  Without any of the three keywords the call is what it was.
+        ``absorption``: ``render_image``'s -- None, one number, C numbers or a float64 tensor ``[C]`` (read to the host once per call,
+        like a tensor IOR); the loss is then that of the absorbing image, the vertex and IOR gradients are the derivative of the whole
+        law, the interior lengths included, and a tensor that requires grad receives d loss / d absorption, which costs no path
+        recompute and is there on any scene and with ``vertices=False`` (drt_render_image_loss_absorb; csrc/drt_image_absorb.h and
+        DESIGN.md 10.7 state the law).  It goes with none of ``screen_param`` / ``texture_param`` / ``camera_param``."""
         from . import render as _render
         a = _render.check_image_loss_args(camera_M, height, width, screen, texture, target, weight, ior_int, ior_ext, vertices, want_image, supersample,
-                                          max_bounces, tir, refraction, fresnel, void, invalid, max_samples, screen_param, texture_param, camera_param)
+                                          max_bounces, tir, refraction, fresnel, void, invalid, max_samples, screen_param, texture_param, camera_param,
+                                          absorption)
         ior, tracked = _ior_args(intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext)
         dev = self._dev
         with _on(dev):
@@ -1264,6 +1319,11 @@ class Scene(StepwiseMixin):
             tgt = (tgt.to(torch.float32) / 255.0 if tgt.dtype == torch.uint8 else tgt).reshape(a["height"], a["width"], a["channels"]).contiguous()
             wgt = None if a["weight"] is None else torch.as_tensor(a["weight"], device=dev).contiguous()
         inputs = (self.vertices if a["vertices"] else self.vertices.detach(),) + tracked
+        if a["absorption"] is not None:
+            term = _image_absorb_term(self, a, ior, tex, tgt, wgt)
+            loss = _UnitSeedTerm.apply(term, *inputs, absorption if isinstance(absorption, torch.Tensor) else None)
+            self.last_image_count = term.count
+            return (loss, term.image) if a["want_image"] else loss
         if camera_param is not None:         # (a keyword that is given takes its entry point, whether or not its tensor requires grad)
             entry, inputs = "camera", inputs + (screen_param, texture_param, camera_param[0], camera_param[1])
         elif screen_param is not None or texture_param is not None:

@@ -243,10 +243,34 @@ def _fill(x, channels, name):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def check_absorption(absorption, channels):
+    """An ``absorption`` argument as C float64 coefficients on the host: one number (the same for every channel), C
+    numbers, or a float64 tensor [C] on any device (its value is read here); each finite and >= 0.  None stays None."""
+    if absorption is None:
+        return None
+    what = f"absorption must be one finite number >= 0, {channels} of them (one per channel) or a float64 tensor [{channels}]"
+    if _is_tensor(absorption):
+        kind = str(absorption.dtype).replace("torch.", "")
+        if kind != "float64" or tuple(absorption.shape) != (channels,):
+            raise ValueError(f"{what}, got a {kind} tensor of shape {tuple(absorption.shape)}")
+    elif isinstance(absorption, (bool, np.bool_, str, bytes)):
+        raise ValueError(f"{what}, got {absorption!r}")
+    try:
+        a = np.asarray(_host(absorption), dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}, got {absorption!r}") from None
+    if a.size == 1 and not _is_tensor(absorption):
+        a = np.repeat(a, channels)
+    if a.size != channels or not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError(f"{what}, got {absorption!r}")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
 def check_render_args(camera_M, height, width, screen, texture, supersample=1, max_bounces=2, tir="drop", refraction="reference",
-                      fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False):
+                      fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False, absorption=None):
     """Every argument check of ``Scene.render_image``, none of which needs a device.  Returns a dict: camera (21 doubles: K^-1, then the
-    top 3 x 4 of R^-1), screen (9 doubles), texture, void / invalid (C doubles), bands, law_flags and the scalars."""
+    top 3 x 4 of R^-1), screen (9 doubles), texture, void / invalid (C doubles), bands, law_flags, the scalars and absorption (C doubles,
+    or None: clear glass)."""
     try:
         n_cam = len(camera_M)
     except TypeError:
@@ -273,7 +297,7 @@ def check_render_args(camera_M, height, width, screen, texture, supersample=1, m
                 screen=screen.packed(), texture=tex, channels=channels, void=_fill(void, channels, "void"),
                 invalid=_fill(invalid, channels, "invalid"), bands=bands, height=int(height), width=int(width), supersample=int(supersample),
                 max_bounces=int(max_bounces), law_flags=int(tir == "reflect") | (2 if refraction == "snell" else 0), fresnel=int(bool(fresnel)),
-                want_planes=bool(want_planes))
+                want_planes=bool(want_planes), absorption=check_absorption(absorption, channels))
 
 
 def _plane(x, shape, name, allow_bytes):
@@ -385,12 +409,16 @@ def camera_of_param(camera_param):
 
 def check_image_loss_args(camera_M, height, width, screen, texture, target, weight=None, ior_int=None, ior_ext=None, vertices=True,
                           want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
-                          invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None):
+                          invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None, absorption=None):
     """Every argument check of ``Scene.image_loss_fused``, none of which needs a device: ``check_render_args``' dict plus target
     (float32 [H, W, C]; uint8 is read as value / 255; [H, W] with a one-channel texture), weight (float32 [H, W] or None), ior (the float
     of each IOR given as a number, else None), vertices and want_image.  ``screen_param`` / ``texture_param`` (tensors a gradient is
     wanted for) take the place of ``screen`` / ``texture``, which must then be None: exactly one form of each is given; so does
-    ``camera_param`` = ``(Rinv, Kinv)`` for ``camera_M``."""
+    ``camera_param`` = ``(Rinv, Kinv)`` for ``camera_M``.  ``absorption`` (``check_absorption``) goes with none of the three."""
+    if absorption is not None:
+        for name, given in (("screen_param", screen_param), ("texture_param", texture_param), ("camera_param", camera_param)):
+            if given is not None:
+                raise ValueError(f"absorption cannot be combined with {name}: the absorbing loss has no screen, texture or camera gradient")
     if camera_param is not None:
         if camera_M is not None:
             raise ValueError("camera_param is given: the positional camera_M must be None (one of the two supplies the camera)")
@@ -409,7 +437,8 @@ def check_image_loss_args(camera_M, height, width, screen, texture, target, weig
         texture = check_texture_param(texture_param).detach()
     elif texture is None:
         raise ValueError("texture is None and no texture_param is given: one of the two must supply the texture")
-    a = check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples)
+    a = check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples,
+                          absorption=absorption)
     H, W, C = a["height"], a["width"], a["channels"]
     if target is not None and hasattr(target, "shape") and len(target.shape) == 2 and C == 1:
         target = target[:, :, None]
@@ -598,6 +627,8 @@ def main(argv=None):
     ap.add_argument("--refraction", choices=("reference", "snell"), default="snell")
     ap.add_argument("--no-fresnel", action="store_true")
     ap.add_argument("--ior", type=float, default=None, help="index of refraction of the object (default: the package's intIOR)")
+    ap.add_argument("--absorption", type=float, nargs="+", default=None, metavar="A",
+                    help="Beer-Lambert absorption per unit of mesh length: one number, or one per channel (default: clear glass)")
     ap.add_argument("--background", default="checker", help="checker, ramp, or a texture file (.npy, .ppm, .pgm, or what PIL reads)")
     ap.add_argument("--texture-size", type=int, default=1024, help="texels per side of a procedural background")
     ap.add_argument("--span", type=float, default=2.0, help="side of the screen in units of the object's extent")
@@ -629,7 +660,7 @@ def main(argv=None):
         screen = Screen.behind(cams[k], center, extent, texture.shape[1], texture.shape[0], span=a.span)
         image, hit, through = scene.render_image(cams[k], height, width, screen, texture, supersample=a.supersample, max_bounces=a.max_bounces,
                                                  tir=a.tir, refraction=a.refraction, fresnel=not a.no_fresnel, void=a.void, invalid=a.invalid,
-                                                 want_planes=True)
+                                                 want_planes=True, absorption=a.absorption)[:3]
         path = write_image(stem.format(k) + "." + a.format, image, force=a.force)
         report["views"].append({"view": k, "image": path, "hit_share": float(hit.mean()), "through_share": float(through.mean())})
     print(json.dumps(report))

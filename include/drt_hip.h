@@ -752,6 +752,30 @@ int drt_render_image_loss_camera(drt_scene_t* s, const double* d_verts, const do
                                  const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
                                  int64_t* d_count, double* d_grad_screen, double* d_grad_texture, double* d_grad_camera, void* stream);
 
+/* ---- absorbing glass: Beer-Lambert attenuation in the image and in its loss (csrc/drt_image_absorb.h states the law)
+ * drt_render_image / drt_render_image_loss with one more input, `sigma` (a HOST array of `channels` float64 absorption coefficients per
+ * unit of mesh length, each finite and >= 0).  A sample's interior length L is the sum, in interaction order, of the hit distances t of
+ * the interactions whose incoming ray travelled inside the object (refracting or mirrored; 0 for a direct sample); a through or direct
+ * sample on the screen has the colour (exp(-(sigma_ch L)) T) texture_ch, the fills are not weighted, every other forward quantity is
+ * drt_render_image's.  With every sigma_ch = 0 the outputs have the bits of drt_render_image / drt_render_image_loss.
+ *   d_length       float32 [height, width], may be NULL: rows [y0, y1) receive the mean of L over the pixel's through samples, 0 where
+ *                  there are none
+ *   d_grad_sigma   `channels` accumulators += d loss / d sigma_ch (addressed like d_grad_ior), may be NULL; computed by the resolve
+ *                  kernel from forward values, so also without any other gradient and on any scene
+ * d_grad_verts and d_grad_ior receive the derivative of the whole law, the lengths included.  Workspace: the clear call's plus 8 bytes
+ * per sample; the first call of a size allocates and cannot run inside a stream capture.  DRT_E_INVALID (nothing enqueued, no output
+ * touched): everything the clear call refuses, then a NULL sigma or an entry that is negative, NaN or infinite (the message names it).
+ * drt_version stays 13: probe for the symbols. */
+int drt_render_image_absorb(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                            double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                            const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                            float* d_image, float* d_hit, float* d_through, const double* sigma, float* d_length, void* stream);
+int drt_render_image_loss_absorb(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                                 double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                                 const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                                 const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                                 int64_t* d_count, const double* sigma, double* d_grad_sigma, void* stream);
+
 /* ---- the image term of several views in one call (csrc/drt_image_views.h states the mapping) -----------------------
  * A view table holds the cameras and screens of a capture whose views all have height x width pixels: cameras21 [n_views, 21] and
  * screens9 [n_views, 9], host arrays in drt_render_image's layouts.  drt_image_views_create checks every screen as drt_render_image
