@@ -115,87 +115,106 @@ __device__ __forceinline__ void raster_test(const TriRec& t, f3 o32, const doubl
 
 struct BigItem { int32_t view, tri, x0, y0, nx, ny; };
 
-// grid (ceil(F / 256), n_views): one thread per (image, triangle in Morton order) projects its triangle (float32 is
-// ample: the box is padded by 1/16 pixel) and counts the pixel centres inside the padded box -- 0 for most
-// sub-pixel triangles, a handful typically, dozens for a few.  The (triangle, pixel) tests of a wave are then dealt to its
-// lanes 64 at a time (wave prefix sum of the counts, owner found by bisection in LDS), so that one fat triangle does not
-// hold 63 idle lanes.
+// The unit of work is a RUN: (image, 64 consecutive triangles in Morton order), image-major.  A lane projects its triangle (float32
+// is ample: the box is padded by 1/16 pixel) and counts the pixel centres inside the padded box -- 0 for most sub-pixel triangles, a
+// handful typically, dozens for a few.  The (triangle, pixel) tests of the run are then dealt to the wave's lanes 64 at a time (wave
+// prefix sum of the counts, owner found by bisection in LDS), so that one fat triangle does not hold 63 idle lanes.
+//
+// The grid is what is resident (8 blocks per CU) and every WAVE loops over runs on its own: wave v of V takes runs v, v + V, ...
+// About half the runs of a launch hold nothing (Morton neighbours face the same way, and a launch handles one facing), the others up
+// to several thousand tests; with a block per 256 triangles, a block -- and its 16 KB of LDS -- lived as long as its slowest wave,
+// and the chip's wave slots were half empty (profiles/raster_runs.txt).  No block barrier anywhere: a wave's slice of s_lane is its
+// own; a wave barrier separates its writes from its reads, and one run's reads from the next run's writes.  (Runs dealt by cursor
+// words instead, as k_cull_listed's are, doubled the launch: same file.)
 struct RasterLane {            // what a lane publishes for the wave: its triangle and its box
     TriRec tri;
     int32_t x0, y0, nx, end;   // `end` = inclusive prefix sum of the counts (first work item NOT of this lane)
 };
 
-__global__ void __launch_bounds__(256) k_raster(const TriRec* __restrict__ tris, int n_tris, ViewModel* views,
-                                                const double* __restrict__ dir, int w, int h,
-                                                unsigned long long* __restrict__ zbuf, uint32_t* __restrict__ zmask,
-                                                BigItem* __restrict__ big, unsigned* big_count, unsigned big_cap, int pass) {
+__device__ __forceinline__ float wave_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+__global__ void __launch_bounds__(256, 8) k_raster(const TriRec* __restrict__ tris, int n_tris, ViewModel* views, int n_views,
+                                                   const double* __restrict__ dir, int w, int h,
+                                                   unsigned long long* __restrict__ zbuf, uint32_t* __restrict__ zmask,
+                                                   BigItem* __restrict__ big, unsigned* big_count, unsigned big_cap, int pass) {
     __shared__ RasterLane s_lane[256];
-    const int view = blockIdx.y;
-    const ViewModel vm = views[view];
-    if (!vm.ok) return;                                   // block-uniform
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
-    const d3 o{vm.o[0], vm.o[1], vm.o[2]};
-    const f3 o32 = to_f32(o);
-    int count = 0;
-    RasterLane me;
-    me.x0 = me.y0 = 0; me.nx = 1;
-    if (k < n_tris) {
-        me.tri = tris[k];
-        // Two launches: triangles facing the camera first (pass 0), the others second (pass 1).  Every triangle is handled in
-        // exactly one of them, so the result is the same minimum; but a pixel's closest hit is nearly always a front face,
-        // and the second launch sees the finished keys of the first: its read-before-atomic check then skips almost every
-        // back face, which cuts the 64-bit atomics -- what bounds this kernel -- by more than half.
-        if ((pass == 1) == tri_faces_away(o32, me.tri)) {
-            const PixelBox box = project_tri_box(vm, o32, me.tri, w, h);
-            if (box.unsafe) {          // the camera plane cuts (or touches) this triangle: no projection bound for this image
-                __hip_atomic_store(&views[view].ok, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else if (box.x0 <= box.x1 && box.y0 <= box.y1) {
-                me.x0 = box.x0; me.y0 = box.y0; me.nx = box.x1 - box.x0 + 1;
-                const int ny = box.y1 - box.y0 + 1;
-                const int64_t cnt = (int64_t)me.nx * ny;
-                if (cnt > kRasterMaxPerLane) {
-                    // listed for k_raster_big, one WAVE per entry: in bands of whole rows of at most kRasterBandPixels pixel centres
-                    const int rows_per = max(1, kRasterBandPixels / me.nx), n_bands = (ny + rows_per - 1) / rows_per;
-                    const unsigned slot = atomicAdd(big_count, (unsigned)n_bands);
-                    if (slot <= big_cap && (unsigned)n_bands <= big_cap - slot) {
-                        for (int b = 0; b < n_bands; ++b)
-                            big[slot + b] = BigItem{view, k, me.x0, me.y0 + b * rows_per, me.nx, min(rows_per, ny - b * rows_per)};
+    const int lane = threadIdx.x & 63;
+    RasterLane* const wl = s_lane + (threadIdx.x & ~63);      // this wave's slice
+    const unsigned n_waves = gridDim.x * 4u, wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    const unsigned runs_per_view = ((unsigned)n_tris + 63u) / 64u, n_runs = runs_per_view * (unsigned)n_views;
+    int cur_view = -1;
+    float minv32[9] = {};
+    f3 o32{0.0f, 0.0f, 0.0f};
+    for (unsigned run = wave; run < n_runs; run += n_waves) {
+        const int view = (int)(run / runs_per_view);
+        const int k = (int)(run - (unsigned)view * runs_per_view) * 64 + lane;
+        if (!__hip_atomic_load(&views[view].ok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;   // wave-uniform; read per run: an image that a run demoted is left alone by the later ones
+        if (view != cur_view) {                               // the model, as the float32 values project_tri_box uses, in scalar registers while the image lasts
+            cur_view = view;
+            for (int q = 0; q < 9; ++q) minv32[q] = wave_uniform((float)views[view].minv[q]);
+            o32 = f3{wave_uniform((float)views[view].o[0]), wave_uniform((float)views[view].o[1]), wave_uniform((float)views[view].o[2])};
+        }
+        int count = 0;
+        __builtin_amdgcn_wave_barrier();                      // the last run's reads of the slice are through
+        if (k < n_tris) {
+            const TriRec tri = tris[k];
+            // Two launches: triangles facing the camera first (pass 0), the others second (pass 1).  Every triangle is handled in
+            // exactly one of them, so the result is the same minimum; but a pixel's closest hit is nearly always a front face,
+            // and the second launch sees the finished keys of the first: its read-before-atomic check then skips almost every
+            // back face, which cuts the 64-bit atomics -- what bounds this kernel -- by more than half.
+            if ((pass == 1) == tri_faces_away(o32, tri)) {
+                ViewModel vm;                                 // (project_tri_box rounds the matrix to float32 first: the same values)
+                for (int q = 0; q < 9; ++q) vm.minv[q] = (double)minv32[q];
+                const PixelBox box = project_tri_box(vm, o32, tri, w, h);
+                if (box.unsafe) {          // the camera plane cuts (or touches) this triangle: no projection bound for this image
+                    __hip_atomic_store(&views[view].ok, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else if (box.x0 <= box.x1 && box.y0 <= box.y1) {
+                    const int nx = box.x1 - box.x0 + 1, ny = box.y1 - box.y0 + 1;
+                    const int64_t cnt = (int64_t)nx * ny;
+                    if (cnt > kRasterMaxPerLane) {
+                        // listed for k_raster_big, one WAVE per entry: in bands of whole rows of at most kRasterBandPixels pixel centres
+                        const int rows_per = max(1, kRasterBandPixels / nx), n_bands = (ny + rows_per - 1) / rows_per;
+                        const unsigned slot = atomicAdd(big_count, (unsigned)n_bands);
+                        if (slot <= big_cap && (unsigned)n_bands <= big_cap - slot) {
+                            for (int b = 0; b < n_bands; ++b)
+                                big[slot + b] = BigItem{view, k, box.x0, box.y0 + b * rows_per, nx, min(rows_per, ny - b * rows_per)};
+                        } else {
+                            __hip_atomic_store(&views[view].ok, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // list full: BVH path for this image
+                            for (unsigned q = slot; q < big_cap; ++q) big[q] = BigItem{view, k, 0, 0, 0, 0};      // (what was reserved below the cap: empty entries)
+                        }
                     } else {
-                        __hip_atomic_store(&views[view].ok, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // list full: BVH path for this image
-                        for (unsigned q = slot; q < big_cap; ++q) big[q] = BigItem{view, k, 0, 0, 0, 0};      // (what was reserved below the cap: empty entries)
+                        count = (int)cnt;
+                        wl[lane].tri = tri;                   // published for the wave (a lane without tests is never an owner: only its `end` is read)
+                        wl[lane].x0 = box.x0; wl[lane].y0 = box.y0; wl[lane].nx = nx;
                     }
-                } else {
-                    count = (int)cnt;
                 }
             }
         }
-    }
-    // inclusive prefix sum of the counts over the wave
-    int end = count;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(end, off);
-        if (lane >= off) end += v;
-    }
-    const int total = __shfl(end, 63);
-    if (total == 0) return;                                // wave-uniform: most waves of a view see nothing but background
-    me.end = end;
-    s_lane[threadIdx.x] = me;                              // read back by the lanes of this wave only: no block barrier needed
-    __builtin_amdgcn_wave_barrier();
-    const int64_t base = (int64_t)view * w * h;
-    for (int item0 = 0; item0 < total; item0 += 64) {
-        const int item = item0 + lane;
-        if (item >= total) break;
-        int lo = 0, hi = 63;                               // first lane whose `end` exceeds item
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (s_lane[wbase + mid].end > item) hi = mid; else lo = mid + 1;
+        // inclusive prefix sum of the counts over the wave
+        int end = count;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int v = __shfl_up(end, off);
+            if (lane >= off) end += v;
         }
-        const RasterLane& ow = s_lane[wbase + lo];
-        const int local = item - (lo == 0 ? 0 : s_lane[wbase + lo - 1].end);
-        const int row = (int)(((float)local + 0.5f) / (float)ow.nx);     // exact for these small integers
-        const int x = ow.x0 + (local - row * ow.nx), y = ow.y0 + row;
-        raster_test(ow.tri, o32, dir, base + (int64_t)y * w + x, raster_slot((unsigned)x, (unsigned)(view * h + y), (unsigned)w), zbuf, zmask);
+        const int total = __builtin_amdgcn_readlane(end, 63);  // (a scalar: the loop's state stays in scalar registers only while its branches are wave-uniform)
+        if (total == 0) continue;                              // most runs of a view see nothing but background
+        wl[lane].end = end;                                    // read back by the lanes of this wave only: no block barrier needed
+        __builtin_amdgcn_wave_barrier();
+        const int64_t base = (int64_t)view * w * h;
+        for (int item0 = 0; item0 < total; item0 += 64) {
+            const int item = item0 + lane;
+            if (item >= total) break;
+            int lo = 0, hi = 63;                               // first lane whose `end` exceeds item
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (wl[mid].end > item) hi = mid; else lo = mid + 1;
+            }
+            const RasterLane& ow = wl[lo];
+            const int local = item - (lo == 0 ? 0 : wl[lo - 1].end);
+            const int row = (int)(((float)local + 0.5f) / (float)ow.nx);     // exact for these small integers
+            const int x = ow.x0 + (local - row * ow.nx), y = ow.y0 + row;
+            raster_test(ow.tri, o32, dir, base + (int64_t)y * w + x, raster_slot((unsigned)x, (unsigned)(view * h + y), (unsigned)w), zbuf, zmask);
+        }
     }
 }
 
@@ -266,7 +285,7 @@ int launch_raster(drt_scene* s, drt_scene::Sub& w, hipStream_t st, const double*
     else k_fit_views<<<n_views, 64, 0, st>>>(d_origin, d_dir, iw, ih, w.vmodel);
     if (n > 0) {
         for (int pass = 0; pass < 2; ++pass) {
-            k_raster<<<dim3((n + 255) / 256, n_views), 256, 0, st>>>(s->tris_flat, n, w.vmodel, d_dir, iw, ih, w.zbuf, w.zmask,
+            k_raster<<<8 * s->n_cu, 256, 0, st>>>(s->tris_flat, n, w.vmodel, n_views, d_dir, iw, ih, w.zbuf, w.zmask,
                                                                       reinterpret_cast<BigItem*>(w.big), w.big_count, drt_scene::kBigCap, pass);
             if (pass == 0) {   // the large triangles of the first launch before the second one reads the keys
                 k_raster_big<<<8 * s->n_cu, 256, 0, st>>>(s->tris_flat, w.vmodel, d_dir, iw, ih, w.zbuf, w.zmask,
