@@ -129,6 +129,7 @@ SIGNATURES = {
     "drt_profile_read": (_c.c_int, [_P, _P, _P, _P]),
     "drt_profile_trace_stats": (_c.c_int, [_P, _P]),
     "drt_route_counts": (_c.c_int, [_P, _P]),
+    "drt_raster_deal_counts": (_c.c_int, [_P, _P]),
     "drt_check_violations": (_c.c_int, [_P]),
 }
 

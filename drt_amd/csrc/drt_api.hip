@@ -150,6 +150,9 @@ int drt_create(int device, drt_scene_t** out) {
     if (const char* ev = getenv("DRT_REBUILD_EVERY")) { const int v = atoi(ev); if (v >= 1) s->rebuild_every = v; }
     if (const char* ev = getenv("DRT_STREAMS")) { const int v = atoi(ev); if (v >= 1 && v <= drt_scene::kMaxSub) s->n_sub = v; }
     if (const char* ev = getenv("DRT_RASTER")) s->use_raster = atoi(ev) != 0;
+    if (const char* ev = getenv("DRT_RASTER_DEAL")) s->raster_deal = atoi(ev) != 0;
+    if (const char* ev = getenv("DRT_RASTER_DEAL_MIN_RUNS")) { const long long v = atoll(ev); if (v >= 0) s->raster_deal_min_runs = v; }
+    if (const char* ev = getenv("DRT_RASTER_DEAL_FIXED")) { const int v = atoi(ev); if (v >= 1 && v <= 65536) s->raster_deal_fixed = (uint32_t)v; }
     if (const char* ev = getenv("DRT_HIT_SEED")) s->hit_seed = atoi(ev) != 0;
     if (const char* ev = getenv("DRT_ARM_FINISH_BESIDE")) s->arm_finish_beside = atoi(ev) != 0;
     if (const char* ev = getenv("DRT_SEED_TILED")) s->seed_tiled = atoi(ev) != 0;
@@ -215,6 +218,7 @@ void drt_destroy(drt_scene_t* s) {
         for (int k = 0; k < 3; ++k) { (void)hipFree(w.q_idx[k]); (void)hipFree(w.q_ray[k]); (void)hipFree(w.q_face[k]); }
         (void)hipFree(w.tmp_face1); (void)hipFree(w.tmp_face2); (void)hipFree(w.qcount); (void)hipFree(w.slow_stack); (void)hipFree(w.redo);
         (void)hipFree(w.zbuf); (void)hipFree(w.zmask); (void)hipFree(w.vmodel); (void)hipFree(w.big); (void)hipFree(w.big_count); (void)hipFree(w.gen_list); (void)hipFree(w.ray64);
+        (void)hipFree(w.deal.table);
         if (w.done) (void)hipEventDestroy(w.done);
         if (w.fill_fork) (void)hipEventDestroy(w.fill_fork);
         if (w.fill_join) (void)hipEventDestroy(w.fill_join);
@@ -288,6 +292,13 @@ int drt_route_counts(drt_scene_t* s, int64_t* out8) {
     CHECK_SCENE(s);
     if (!out8) return fail(DRT_E_INVALID, "null pointer argument");
     for (int k = 0; k < 8; ++k) out8[k] = s->route_counts[k];
+    return DRT_OK;
+}
+
+int drt_raster_deal_counts(drt_scene_t* s, int64_t* out2) {
+    CHECK_SCENE(s);
+    if (!out2) return fail(DRT_E_INVALID, "null pointer argument");
+    out2[0] = s->raster_deal_counts[0]; out2[1] = s->raster_deal_counts[1];
     return DRT_OK;
 }
 

@@ -681,6 +681,7 @@ int drt_update_mesh(drt_scene_t* s, const int32_t* d_faces, int64_t n_faces, con
     s->n_faces = n_faces;
     s->n_verts = n_verts;
     s->order_valid = false;          // new topology: the previous build's order is not a permutation of these faces
+    for (int j = 0; j < drt_scene::kMaxSub; ++j) s->sub[j].deal.complete = false;   // ... and k_raster's counts per run describe other triangles
     if (n_faces) HIP_TRY(hipMemcpyAsync(s->faces, d_faces, sizeof(int32_t) * 3 * n_faces, hipMemcpyDeviceToDevice, st));
     if (n_verts) HIP_TRY(hipMemcpyAsync(s->verts, d_verts, sizeof(float) * 3 * n_verts, hipMemcpyDeviceToDevice, st));
     s->topology_fixed = false;

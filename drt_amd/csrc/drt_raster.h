@@ -138,4 +138,79 @@ DRT_HD int64_t raster_slot(unsigned x, unsigned gy, unsigned w) {
     return (((int64_t)(gy >> 2) * (w >> 2) + (x >> 2)) << 4) | ((gy & 3u) << 2) | (x & 3u);
 }
 
+// ---- the deal of k_raster's runs by the test counts of the previous call ---------------------------------------------------------------
+// k_raster's unit of work is a run (image, 64 consecutive triangles); a run holds anything from no (triangle, pixel) test to
+// 64 * kRasterMaxPerLane of them, and how many it held in the previous call on the same rays is nearly how many it holds now.  The
+// line of all work -- run after run, each `c_fixed + cost[run]` long: what a run costs without a test (record load, facing test,
+// projection, prefix sum) in units of one test, then its tests -- is cut into V pieces of equal length, one per wave.  A boundary is a
+// position (run, item): a cut that falls into a run's fixed part moves to the run's start (item 0), one that falls among its tests
+// splits the run between waves, each of which projects the run again and works its own items.
+struct DealPos { uint32_t run, item; };
+constexpr uint32_t kRasterDealFixed = 64;    // c_fixed (profiles/raster_deal.txt section 4: 16, 64 and 256 measured alike, 1 024 and more slower)
+
+DRT_HD uint64_t raster_deal_weight(uint32_t cost, uint32_t c_fixed) { return (uint64_t)c_fixed + cost; }
+DRT_HD uint64_t raster_deal_target(uint64_t total, uint32_t n_waves, uint32_t v) {      // floor(v C / V) (< C for v < V), without the product v C
+    return (total / n_waves) * v + (total % n_waves) * v / n_waves;
+}
+DRT_HD uint32_t raster_deal_item(uint64_t off, uint32_t c_fixed) { return off > c_fixed ? (uint32_t)(off - c_fixed) : 0u; }      // a cut `off` into a run's weight
+
+// Boundary v of V over `n_runs` runs, from the INCLUSIVE prefix sums of raster_deal_weight: B[0] = (0, 0), B[V] = (n_runs, 0), and B[v]
+// where the running sum reaches floor(v C / V), C the grand total.  Non-decreasing in v in the order of (run, item).
+DRT_HD DealPos raster_deal_boundary(const uint64_t* prefix, uint32_t n_runs, uint32_t n_waves, uint32_t v, uint32_t c_fixed) {
+    if (v == 0 || n_runs == 0) return DealPos{0, 0};
+    if (v >= n_waves) return DealPos{n_runs, 0};
+    const uint64_t total = prefix[n_runs - 1];
+    const uint64_t target = raster_deal_target(total, n_waves, v);
+    uint32_t lo = 0, hi = n_runs - 1;                                                     // first run whose inclusive sum exceeds the target
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (prefix[mid] > target) hi = mid; else lo = mid + 1;
+    }
+    return DealPos{lo, raster_deal_item(target - (lo ? prefix[lo - 1] : 0), c_fixed)};
+}
+
+// The same boundaries from the runs' side, without a search (k_raster_deal: a thread per run): the boundaries that fall into a run whose
+// weights before it sum to `before` and with it to `with` are those of the waves [first_wave(before), first_wave(with)) --
+// floor(v C / V) >= X exactly when v >= ceil(X V / C) -- and boundary v of them is (run, raster_deal_item(target(v) - before)).
+DRT_HD uint32_t raster_deal_first_wave(uint64_t sum, uint64_t total, uint32_t n_waves) {
+    const uint64_t q = (sum * n_waves + total - 1) / total;
+    return q > n_waves ? n_waves : (uint32_t)q;
+}
+// What k_raster_deal's thread of run `run` does once it knows the sums: write the boundaries inside its run.  Over all runs every entry
+// [0, V) is written exactly once (total > 0); entry V = (n_runs, 0) is the caller's.
+DRT_HD void raster_deal_place(DealPos* table, uint32_t run, uint64_t before, uint64_t with, uint64_t total, uint32_t n_waves, uint32_t c_fixed) {
+    if (!(with > before) || total == 0) return;
+    const uint32_t v1 = raster_deal_first_wave(with, total, n_waves);
+    for (uint32_t v = raster_deal_first_wave(before, total, n_waves); v < v1; ++v)
+        table[v] = DealPos{run, raster_deal_item(raster_deal_target(total, n_waves, v) - before, c_fixed)};
+}
+
+// What a table may hold that describes another launch (more runs, a graph replayed behind a call of another shape): nothing past the end.
+DRT_HD DealPos raster_deal_clamp(DealPos b, uint32_t n_runs) { return b.run >= n_runs ? DealPos{n_runs, 0} : b; }
+
+// The runs of the wave between boundaries b0 <= b1: first .. last, the last one only if b1 cuts into it; none when b0 == b1.
+DRT_HD uint32_t raster_deal_end(DealPos b0, DealPos b1) {
+    if (b0.run == b1.run && b0.item == b1.item) return b0.run;
+    return b1.run + (b1.item > 0 ? 1u : 0u);
+}
+
+// The wave's items [lo, hi) of run r of its range (whatever the run's actual total is: a slice past it is empty, the last slice of a run
+// is open-ended), and whether the wave OWNS the run: its range contains (r, 0).  Every run has exactly one owner.
+struct DealSlice { uint32_t lo, hi; bool owner; };
+DRT_HD DealSlice raster_deal_slice(DealPos b0, DealPos b1, uint32_t r) {
+    DealSlice s;
+    s.lo = b0.run == r ? b0.item : 0u;
+    s.hi = b1.run == r ? b1.item : 0xFFFFFFFFu;
+    s.owner = (b0.run < r || (b0.run == r && b0.item == 0)) && (r < b1.run || (r == b1.run && b1.item > 0));
+    return s;
+}
+
+
+// The same slices as a wave walks its range: only its first run can start past item 0 -- and is then not the wave's own --, only its
+// last can end early.  Four scalars of loop state instead of two boundaries and a run number (k_raster has none to spare).
+struct DealRange { uint32_t run, end, lo, last_hi; };
+DRT_HD DealRange raster_deal_range(DealPos b0, DealPos b1) { return DealRange{b0.run, raster_deal_end(b0, b1), b0.item, b1.item ? b1.item : 0xFFFFFFFFu}; }
+DRT_HD DealSlice raster_deal_slice(const DealRange& g) { return DealSlice{g.lo, g.run + 1 == g.end ? g.last_hi : 0xFFFFFFFFu, g.lo == 0}; }      // of run g.run < g.end
+DRT_HD void raster_deal_next(DealRange& g) { ++g.run; g.lo = 0; }
+
 }  // namespace drt

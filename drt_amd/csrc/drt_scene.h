@@ -150,8 +150,19 @@ struct drt_scene {
         ViewModel* vmodel = nullptr;
         int vm_cap = 0;
         void* big = nullptr;
-        unsigned* big_count = nullptr;
+        unsigned* big_count = nullptr;                       // [kRasterCostAt + 2 * deal.cap_runs]: the list's counter, then k_raster's tests per (run, pass)
         int32_t* gen_list = nullptr;                         // [q_cap] R0 slots whose ray did not verify as a grid ray: traced like before
+        // k_raster's deal by the previous call's test counts (drt_raster.h): per pass (0: camera-facing, 1: the others) the tests every run
+        // held in the last launch, their prefix sums, and the boundaries of the waves' ranges made from them.  The tag is host state: what
+        // launch the table describes, set once the kernel that writes it has been enqueued; a launch of any other description deals statically.
+        struct Deal {
+            DealPos* table = nullptr;                        // [2][cap_waves + 1]; the counts [cap_runs][2] lie behind big_count (k_raster)
+            int64_t cap_runs = 0;
+            int cap_waves = 0;
+            const double* dir = nullptr;
+            int n_views = 0, iw = 0, ih = 0, n_tris = 0, grid = 0;
+            bool complete = false;
+        } deal;
     };
     static constexpr unsigned kBigCap = 1u << 20;
     static constexpr int kMaxSub = 4;
@@ -211,6 +222,10 @@ struct drt_scene {
     bool arm_finish_beside = true; // DRT_ARM_FINISH_BESIDE=0: k_finish of an armed call stays on the sub-batch's stream, in front of its loss pass (A/B measurement)
     bool hit_seed = true;          // DRT_HIT_SEED=0: drt_render_seed's seeds are ignored (A/B measurement)
     bool use_raster = true;        // DRT_RASTER=0: every primary ray takes the BVH path (A/B measurement)
+    bool raster_deal = true;       // DRT_RASTER_DEAL=0: k_raster always deals its runs statically (wave v of V takes runs v, v + V, ...)
+    int64_t raster_deal_min_runs = 16384;            // launches of fewer runs deal statically (DRT_RASTER_DEAL_MIN_RUNS; launch_raster)
+    uint32_t raster_deal_fixed = kRasterDealFixed;   // c_fixed of the deal (DRT_RASTER_DEAL_FIXED: the sweep of profiles/raster_deal.txt)
+    int64_t raster_deal_counts[2] = {0, 0};          // drt_raster_deal_counts: k_raster launches that took their ranges from a table / that dealt statically
     bool built = false;
     void* paths_ws = nullptr;      // ray lists and counters of drt_render_paths_forward (drt_paths.hip), allocated on first use
     void* image_loss_ws = nullptr; // pixel seeds of drt_render_image_loss (drt_image_loss.hip), allocated on first use

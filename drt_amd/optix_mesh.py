@@ -229,6 +229,12 @@ class optix_mesh:
         _lib.check(_lib.lib().drt_route_counts(self._h, out))
         return dict(zip(self.ROUTES, out))
 
+    def raster_deal_counts(self):
+        """(k_raster launches that took their runs from a table of the previous call's counts, launches dealt statically) since the scene was created."""
+        out = (ctypes.c_int64 * 2)()
+        _lib.check(_lib.lib().drt_raster_deal_counts(self._h, out))
+        return tuple(out)
+
     def trace_stats(self):
         """Per k_trace stage: (wave_steps, lane_steps, refills, max_wave_steps) of the last profile_read interval."""
         out = (ctypes.c_int64 * 12)()

@@ -837,6 +837,13 @@ int drt_profile_trace_stats(drt_scene_t* s, int64_t* out12);
  * moved behind the first shading (DRT_GRID_ALL_VERIFIED), with the one-kernel back half (DRT_MEGA_MAX_LOG2) }.  The K-interaction and
  * image entry points are not counted. */
 int drt_route_counts(drt_scene_t* s, int64_t* out8);
+/* How the projection pass dealt its work: out2 = { k_raster launches since drt_create that took their ranges of runs from a table made of
+ * the previous call's test counts, launches that dealt the runs statically } (two launches per sub-batch with a projection pass; host
+ * counters, no synchronisation).  The first call on a set of rays, a call of another shape on the same workspace, a new topology and
+ * DRT_RASTER_DEAL=0 deal statically, and so do launches of fewer than DRT_RASTER_DEAL_MIN_RUNS (default 16384) runs of 64 triangles of
+ * one image; the results are the same bit for bit.  (DRT_RASTER_DEAL_FIXED, default 64: what a run without tests weighs in the deal,
+ * in tests.) */
+int drt_raster_deal_counts(drt_scene_t* s, int64_t* out2);
 
 /* Debug builds (hipcc -DDRT_CHECK=1): the persistent traversal kernels assert the invariants of their bound-check-free LDS stack
  * (csrc/drt_traverse.h FastStack) and count violations on the device.  out4 = {stores above a lane's rows, pops of an empty stack,
