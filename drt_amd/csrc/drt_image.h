@@ -3,7 +3,8 @@
 // law of drt_paths.h (unchanged), carries a Fresnel throughput, and its exit ray samples the screen's texture bilinearly.
 // Plain C++ like the other device math headers, so that tests/hostsim/image.cpp runs the same bodies on the host against the numpy
 // restatement (tests/image_ref.py) with tolerance 0: every float64 expression below is one rounding per operation in the stated
-// association (the library is built with -ffp-contract=off).  Forward only: nothing here has an adjoint.
+// association (the library is built with -ffp-contract=off).  Forward only: nothing here has an adjoint.  Each function is stated once
+// for clear and for absorbing glass (drt_image_absorb.h states that law): the clear forms never evaluate an exp.
 #pragma once
 #include "drt_paths.h"
 
@@ -64,14 +65,27 @@ DRT_HD double image_transmittance(const Bounce& b, double ior_ext, double ior_in
     return 1.0 - fresnel_R(b.ci, entering ? ior_ext : ior_int, entering ? ior_int : ior_ext);
 }
 
-// path_interact (drt_paths.h) -- the same continuation, the same bits -- that also multiplies the throughput T when FRESNEL is on.
-template <bool SNELL, bool FRESNEL>
-DRT_HD bool image_interact(const PathCtx& c, int32_t face, bool reflect, d3& o, d3& d, int& n_refr, double& T) {
+// Absorbing glass (drt_image_absorb.h states the law).  What an interaction adds to the interior length: L + t when
+// its incoming ray travelled inside the object, L otherwise.
+DRT_HD double image_absorb_length(const Bounce& b, double L) { return b.sg < 0.0 ? L + b.t : L; }
+
+// A_ch = exp(-(sigma_ch * L))
+DRT_HD double image_absorb_factor(double sigma, double L) { return exp(-(sigma * L)); }
+
+// The length hook of clear glass: nothing.
+struct ImageNoLength { DRT_HD void operator()(const Bounce&) const {} };
+
+// path_interact (drt_paths.h) -- the same continuation, the same bits -- that also multiplies the throughput T when FRESNEL is on, and
+// hands the bounce to `length` right behind law_forward, before the throughput: an absorbing caller adds image_absorb_length to the
+// interior length it keeps (a kernel does so in memory at once, so that no length is held in registers across the Fresnel term).
+template <bool SNELL, bool FRESNEL, typename Length = ImageNoLength>
+DRT_HD bool image_interact(const PathCtx& c, int32_t face, bool reflect, d3& o, d3& d, int& n_refr, double& T, Length length = Length{}) {
     d3 v0, v1, v2;
     int32_t vid[3];
     Bounce b;
     load_tri64(c, face, v0, v1, v2, vid);
     law_forward<SNELL>(o, d, v0, v1, v2, c.ior_ext, c.ior_int, b);
+    length(b);
     if (!b.tir) {
         if constexpr (FRESNEL) T = T * image_transmittance(b, c.ior_ext, c.ior_int);
         o = b.new_o; d = b.wt;
@@ -125,19 +139,28 @@ DRT_HD double image_bilinear(const ImageTex& tx, double u, double v, int ch) {
 }
 
 // Colour of one sample, c[0 .. tx.c): `invalid` for an invalid one; for a direct or through one T times the texture where its exit ray
-// lands on the screen, `void` elsewhere.  The fill colours are not weighted.
-DRT_HD void image_sample_colour(const ImageScreen& sc, const ImageTex& tx, int cls, d3 o, d3 d, double T, const double* fill_void,
-                                const double* fill_invalid, double* c) {
+// lands on the screen, `void` elsewhere.  The fill colours are not weighted.  ABSORB: (A_ch * T) times the texture, A_ch from the
+// interior length L and sigma[0 .. tx.c).  True: the sample is direct or through and landed on the screen (its colour is a function of
+// T and L); false: c is a fill.
+template <bool ABSORB = false>
+DRT_HD bool image_sample_colour(const ImageScreen& sc, const ImageTex& tx, int cls, d3 o, d3 d, double T, const double* fill_void,
+                                const double* fill_invalid, double* c, double L = 0.0, const double* sigma = nullptr) {
     if (cls == kImageInvalid) {
         for (int ch = 0; ch < tx.c; ++ch) c[ch] = fill_invalid[ch];
-        return;
+        return false;
     }
     double u, v;
     if (!image_screen_uv(sc, tx.th, tx.tw, o, d, u, v)) {
         for (int ch = 0; ch < tx.c; ++ch) c[ch] = fill_void[ch];
-        return;
+        return false;
     }
-    for (int ch = 0; ch < tx.c; ++ch) c[ch] = T * image_bilinear(tx, u, v, ch);
+    if constexpr (ABSORB) {
+        for (int ch = 0; ch < kImageMaxChannels; ++ch)          // (a fixed trip count: the three colours stay in registers on the device)
+            if (ch < tx.c) c[ch] = (image_absorb_factor(sigma[ch], L) * T) * image_bilinear(tx, u, v, ch);
+    } else {
+        for (int ch = 0; ch < tx.c; ++ch) c[ch] = T * image_bilinear(tx, u, v, ch);
+    }
+    return true;
 }
 
 }  // namespace drt

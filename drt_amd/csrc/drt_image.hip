@@ -1,6 +1,8 @@
 // drt_image.hip -- the forward renderer (drt_image.h holds the law): the refracted image of the mesh in front of a textured planar
 // screen, one band of rows per call, as the wavefront loop of drt_paths.hip with the rays made in the kernel.  The forward wavefront
-// (image_forward, declared in drt_image_wave.h) is also what drt_render_image_loss (drt_image_loss.hip) starts with.
+// (image_forward / image_forward_from, declared in drt_image_wave.h) is also what every loss call of the family starts with.  The kernels
+// are drt_image_wave.h's templates; this unit holds the clear single-view forms: k_image_start<ImageOneView>,
+// k_image_shade<., ., ., ImageClear>, k_image_resolve<ImageClear>.
 //
 //   k_image_start   all samples : forms the sample ray (image_sample_ray), top-box test; candidates -> list 0 (index + float32 ray), their
 //                                 float64 ray and a throughput of 1 parked in the workspace; one state byte and one hit count per sample
@@ -16,126 +18,18 @@
 // list appends' reservations; a list's ORDER is never read (every value is stored under its sample index), so two runs give the same bits.
 #include "drt_image_wave.h"
 
-__global__ void __launch_bounds__(kPathBlock) k_image_start(const Node4Q* __restrict__ nodes, int n_tris, ImageCam cam, ImageBand band,
-                                                             double* __restrict__ park_ori, double* __restrict__ park_dir, double* __restrict__ thr,
-                                                             uint8_t* __restrict__ state, uint8_t* __restrict__ hits, RayList out, unsigned* count) {
-    __shared__ StageMem stage;
-    stage_init(stage);
-    unsigned first, last;
-    block_run(band.n, first, last);
-    for (unsigned base = first; base < last; base += kPathBlock) {
-        const unsigned i = base + threadIdx.x;
-        bool cand = false;
-        f3 o32{0.f, 0.f, 0.f}, d32{0.f, 0.f, 1.f};
-        if (i < band.n) {
-            state[i] = 0;
-            hits[i] = 0;
-            if (n_tris > 0) {
-                int x, y, j;
-                band_sample(band, i, x, y, j);
-                d3 o, d;
-                image_sample_ray(cam, band.s, x, y, j, o, d);
-                o32 = to_f32(o); d32 = to_f32(d);
-                cand = hits_top_boxes(nodes, o32, d32);
-                if (cand) { store_d3(park_ori, i, o); store_d3(park_dir, i, d); thr[i] = 1.0; }
-            }
-        }
-        stage_push(stage, cand, (int32_t)i, o32, d32, out, count);
-    }
-    stage_flush(stage, out, count);
-}
-
-// list k -> list k + 1, as k_paths_shade (drt_paths.hip); FRESNEL: a refracting interaction multiplies the sample's throughput by 1 - R;
-// TAPE: the face of the interaction is written to tape[k, i] (without it `tape` is never touched and may be null).
-template <bool SNELL, bool FRESNEL, bool TAPE>
-__global__ void __launch_bounds__(kPathBlock) k_image_shade(PathCtx c, int64_t n_rays, int k, int max_bounces, bool reflect, RayList in,
-                                                             const unsigned* __restrict__ n_in, RayList out, unsigned* n_out,
-                                                             double* __restrict__ park_ori, double* __restrict__ park_dir, double* __restrict__ thr,
-                                                             uint8_t* __restrict__ state, uint8_t* __restrict__ hits, int32_t* __restrict__ tape) {
-    __shared__ StageMem stage;
-    stage_init(stage);
-    const unsigned n = *n_in;
-    const bool last_stage = k >= max_bounces;
-    unsigned first, last;
-    block_run(n, first, last);
-    for (unsigned base = first; base < last; base += kPathBlock) {
-        const unsigned e = base + threadIdx.x;
-        bool go = false;
-        int64_t i = 0;
-        f3 o32{0.f, 0.f, 0.f}, d32{0.f, 0.f, 1.f};
-        if (e < n) {
-            i = in.idx[e];
-            const int32_t f = in.face[e];
-            if (i >= 0 && i < n_rays) {
-                int n_refr = state[i];
-                if (f < 0) {
-                    if (path_exit_valid(n_refr)) state[i] = (uint8_t)n_refr | kPathDone;
-                } else if (!last_stage) {
-                    if constexpr (TAPE) tape[(int64_t)k * n_rays + i] = f;
-                    hits[i] = (uint8_t)(k + 1);
-                    d3 o = load_d3(park_ori, i), d = load_d3(park_dir, i);
-                    double T = FRESNEL ? thr[i] : 1.0;
-                    go = image_interact<SNELL, FRESNEL>(c, f, reflect, o, d, n_refr, T);
-                    if (go) {
-                        store_d3(park_ori, i, o); store_d3(park_dir, i, d);
-                        if (FRESNEL) thr[i] = T;
-                        state[i] = (uint8_t)n_refr;
-                        o32 = to_f32(o); d32 = to_f32(d);
-                    }
-                }
-            }
-        }
-        if (!last_stage) stage_push(stage, go, (int32_t)i, o32, d32, out, n_out);
-    }
-    if (!last_stage) stage_flush(stage, out, n_out);
-}
-
-// One thread per pixel of the band.  hit / through may be null.
-__global__ void __launch_bounds__(kPathBlock) k_image_resolve(ImageCam cam, ImageBand band, int64_t n_pix, ImageScreen sc, ImageTex tx, ImageFill fill, bool fresnel,
-                                                               const double* __restrict__ park_ori, const double* __restrict__ park_dir,
-                                                               const double* __restrict__ thr, const uint8_t* __restrict__ state,
-                                                               const uint8_t* __restrict__ hits, float* __restrict__ image, float* __restrict__ hit,
-                                                               float* __restrict__ through) {
-    const int64_t pix = (int64_t)blockIdx.x * kPathBlock + threadIdx.x;
-    if (pix >= n_pix) return;
-    const int s2 = band.s * band.s;
-    const int y = band.y0 + (int)(pix / band.width), x = (int)(pix % band.width);
-    double acc[kImageMaxChannels] = {0.0, 0.0, 0.0};
-    int n_hit, n_through;
-    image_pixel_walk(cam, band, pix, x, y, sc, tx, fill, fresnel, park_ori, park_dir, thr, state, hits, acc, n_hit, n_through);
-    const int64_t row = (int64_t)y * band.width + x;
-    for (int ch = 0; ch < tx.c; ++ch) image[row * tx.c + ch] = (float)(acc[ch] / (double)s2);
-    if (hit) hit[row] = (float)((double)n_hit / (double)s2);
-    if (through) through[row] = (float)((double)n_through / (double)s2);
-}
-
-namespace {
-
-// one throughput per sample, grown like the rows of the one-pass form it sits beside
-int ensure_image_thr(drt_scene* s, int64_t n, hipStream_t st, const char* who) {
-    PathsWs* w = paths_ws_of(s);
-    if (n <= w->thr_cap) return DRT_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(DRT_E_INVALID, "%s: the first call of this size allocates its throughputs and cannot run inside a stream "
-                                   "capture: issue one such call eagerly before capturing", who);
-    (void)hipFree(w->thr);
-    w->thr = nullptr; w->thr_cap = 0;
-    HIP_TRY(hipMalloc(&w->thr, sizeof(double) * (size_t)n));
-    w->thr_cap = n;
+int grow_doubles(double*& buf, int64_t& cap, int64_t n, hipStream_t st, const char* who, const char* what) {
+    if (n <= cap) return DRT_OK;
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone)
+        return fail(DRT_E_INVALID, "%s: the first call of this size allocates its %s and cannot run "
+                                   "inside a stream capture: issue one such call eagerly before capturing", who, what);
+    (void)hipFree(buf);
+    buf = nullptr; cap = 0;
+    HIP_TRY(hipMalloc(&buf, sizeof(double) * (size_t)n));
+    cap = n;
     return DRT_OK;
 }
-
-// k_image_shade under (snell, fresnel, tape)
-using ImageShade = void (*)(PathCtx, int64_t, int, int, bool, RayList, const unsigned*, RayList, unsigned*, double*, double*, double*, uint8_t*, uint8_t*, int32_t*);
-ImageShade image_shade_kernel(bool snell, bool fresnel, bool tape) {
-    static const ImageShade kernels[8] = {k_image_shade<false, false, false>, k_image_shade<false, false, true>, k_image_shade<false, true, false>,
-                                          k_image_shade<false, true, true>,   k_image_shade<true, false, false>, k_image_shade<true, false, true>,
-                                          k_image_shade<true, true, false>,   k_image_shade<true, true, true>};
-    return kernels[(snell ? 4 : 0) | (fresnel ? 2 : 0) | (tape ? 1 : 0)];
-}
-
-}  // namespace
 
 int image_call_check(const double* camera21, int height, int width, int y0, int y1, int supersample, double ior_int, double ior_ext, int max_bounces,
                      int law_flags, int fresnel, const double* screen9, const float* d_texture, int tex_h, int tex_w, int channels,
@@ -172,15 +66,20 @@ int image_call_check(const double* camera21, int height, int width, int y0, int 
 // image_forward's own start: k_image_start with the camera of the call (`src`)
 void image_start_call(const ImageStartArgs& a, const void* src) {
     const ImageCall& c = *static_cast<const ImageCall*>(src);
-    k_image_start<<<a.grid, kPathBlock, 0, a.st>>>(a.nodes, a.n_tris, c.cam, c.band, a.park_ori, a.park_dir, a.thr, a.state, a.hits, a.out, a.count);
+    k_image_start<<<a.grid, kPathBlock, 0, a.st>>>(a.nodes, a.n_tris, ImageOneView{c.cam, c.sc}, c.band, a.park_ori, a.park_dir, a.thr, a.state, a.hits, a.out,
+                                                   a.count);
 }
+
+// image_forward_from's default shade: the clear forms, what every call without a shade hook launches
+static void image_shade_clear(const ImageShadeArgs& a, const void*) { image_shade_launch(a, ImageClear{}); }
 
 int image_forward_from(drt_scene* s, const double* d_verts, const ImageCall& c, bool keep_tape, hipStream_t st, const char* who, ImageStartFn start,
                        const void* src, ImageShadeFn shade_fn, const void* shade_src) {
     { int rc = ensure_paths_ws(s, c.n, st, who); if (rc) return rc; }
     { int rc = ensure_paths_fused_ws(s, c.n, st, who); if (rc) return rc; }
-    { int rc = ensure_image_thr(s, c.n, st, who); if (rc) return rc; }
+    { PathsWs* w = paths_ws_of(s); int rc = grow_doubles(w->thr, w->thr_cap, c.n, st, who, "throughputs"); if (rc) return rc; }
     { int rc = wait_build(s, st); if (rc) return rc; }
+    if (!shade_fn) shade_fn = image_shade_clear;
     const PathsWs& w = *paths_ws_of(s);
     const PathCtx pc = image_path_ctx(s, d_verts, c);
     const int gs = grid_for(c.n, kPathBlock, 8 * s->n_cu);
@@ -190,14 +89,10 @@ int image_forward_from(drt_scene* s, const double* d_verts, const ImageCall& c, 
     const RayList l0{w.idx[0], w.ray[0], w.face[0]};
     start(ImageStartArgs{pc.tc.nodes, pc.tc.n_tris, park_ori, park_dir, w.thr, w.state, w.hits, l0, w.cnt + kCntList, gs, st}, src);
     if (s->n_faces > 0) {
-        const ImageShade shade = image_shade_kernel(c.snell, c.fresnel, keep_tape);
         int32_t* const tape = keep_tape ? w.tape : nullptr;
         trace_lists(s, w, pc.tc, st, c.max_bounces, [&](int k, const RayList& in, const unsigned* n_in, const RayList& out, unsigned* n_out) {
-            if (shade_fn)
-                shade_fn(ImageShadeArgs{pc, (int64_t)c.n, k, c.max_bounces, c.reflect, c.snell, c.fresnel, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state,
-                                        w.hits, tape, gs, st}, shade_src);
-            else
-                shade<<<gs, kPathBlock, 0, st>>>(pc, (int64_t)c.n, k, c.max_bounces, c.reflect, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state, w.hits, tape);
+            shade_fn(ImageShadeArgs{pc, (int64_t)c.n, k, c.max_bounces, c.reflect, c.snell, c.fresnel, in, n_in, out, n_out, park_ori, park_dir, w.thr, w.state,
+                                    w.hits, tape, gs, st}, shade_src);
         });
     }
     return DRT_OK;
@@ -221,8 +116,8 @@ int drt_render_image(drt_scene_t* s, const double* d_verts, const double* camera
     hipStream_t st = (hipStream_t)stream;
     { int rc = image_forward(s, d_verts, c, false, st, "drt_render_image"); if (rc) return rc; }
     const PathsWs& w = *paths_ws_of(s);
-    k_image_resolve<<<(unsigned)((c.n_pix + kPathBlock - 1) / kPathBlock), kPathBlock, 0, st>>>(c.cam, c.band, c.n_pix, c.sc, c.tx, c.fill, c.fresnel, w.park,
-                                                                                                 w.park + 3 * w.fused_cap, w.thr, w.state, w.hits, d_image, d_hit, d_through);
+    k_image_resolve<<<(unsigned)((c.n_pix + kPathBlock - 1) / kPathBlock), kPathBlock, 0, st>>>(
+        c.cam, c.band, c.n_pix, c.sc, c.tx, c.fill, c.fresnel, ImageClear{}, w.park, w.park + 3 * w.fused_cap, w.thr, w.state, w.hits, d_image, d_hit, d_through, nullptr);
     HIP_TRY(hipGetLastError());
     return DRT_OK;
 }

@@ -3,7 +3,7 @@
 // register allocation depends on the other kernels of its unit, and the kernels of drt_image_loss.hip and
 // drt_image_screen.hip are to stay what they are.
 //
-//   k_image_loss_bwd<.., CAMERA>  the list : drt_image_loss_bwd.h's template with the flag on, in place of drt_image_loss.hip's launch: the same
+//   k_image_loss_bwd<.., CAMERA>  the list : drt_image_loss_bwd.h's template <ImageOneView, ImageClear> with the flag on, in place of drt_image_loss.hip's launch: the same
 //                                            vertex and IOR gradients and count, and the camera-ray seeds (g_o, g_d) that image_path_backward
 //                                            ends with, stored under the sample index (48 bytes per sample of the band)
 //   k_image_camera_bwd            all pixels : behind k_image_loss_resolve and the kernel above; image_pixel_walk's classes over the s x s
@@ -55,15 +55,9 @@ __global__ void __launch_bounds__(256) k_image_camera_bwd(ImageCam cam, ImageBan
     block_flush<DET, kImageCamParams>(acc, grad_camera);
 }
 
-int launch_image_loss_bwd_camera(const drt_scene* s, const PathCtx& pc, const ImageCall& c, int grid, const int32_t* list, const unsigned* n_list,
-                                 const double* g_c, double* d_grad_verts, double* d_grad_ior, unsigned long long* d_count, double* seeds, hipStream_t st) {
-    const PathsWs& w = *static_cast<const PathsWs*>(s->paths_ws);
-    const double* const park_ori = w.park;
-    const double* const park_dir = w.park + 3 * w.fused_cap;
-    IMAGE_LOSS_BWD_LAUNCH(true, det_mode(), c.snell, c.fresnel, d_grad_verts != nullptr, grid, st, pc, c.cam, c.band, c.sc, c.tx, c.max_bounces, park_ori, park_dir, w.thr,
-                          w.tape, w.hits, list, n_list, g_c, d_grad_verts, d_grad_ior, d_count, seeds);
-    HIP_TRY(hipGetLastError());
-    return DRT_OK;
+int launch_image_loss_bwd_camera(const drt_scene* s, const PathCtx& pc, const ImageCall& c, const ImageOneView& view, const ImageClear& pay, int grid,
+                                 const int32_t* list, const unsigned* n_list, const double* g_c, const ImageLossOut& out, double* seeds, hipStream_t st) {
+    return image_loss_bwd_launch<ImageOneView, ImageClear, true>(s, pc, c, view, pay, grid, list, n_list, g_c, out, seeds, st);
 }
 
 int launch_image_camera_bwd(const drt_scene* s, const ImageCall& c, const double* g_c, const double* seeds, double* d_grad_camera, hipStream_t st) {

@@ -84,6 +84,34 @@ DRT_HD void bounce_ci_backward(const Bounce& b, double g_ci, d3& gv0, d3& gv1, d
     gv0 -= g_e1 + g_e2;
 }
 
+// Adjoint of t = e2q * inv of bounce_forward for the incoming g_t (absorbing glass: the seed of the interior length), statement for
+// statement as bounce_backward has the chain (the way bounce_ci_backward does ci): accumulates into the three vertices and into the
+// incoming ray (g_o, g_d).
+DRT_HD void bounce_t_backward(const Bounce& b, double g_t, d3& gv0, d3& gv1, d3& gv2, d3& g_o, d3& g_d) {
+    // t = (e2 . q) * inv
+    d3 g_e2 = (g_t * b.inv) * b.q;
+    const d3 g_q = (g_t * b.inv) * b.e2;
+    const double g_inv = g_t * b.e2q;
+    // q = s x e1
+    const d3 g_s = cross(b.e1, g_q);
+    d3 g_e1 = cross(g_q, b.s);
+    // s = o - v0
+    g_o += g_s;
+    // inv = 1/det ; det = e1 . p ; p = d x e2
+    const double g_det = -g_inv * b.inv * b.inv;
+    g_e1 += g_det * b.p;
+    const d3 g_p = g_det * b.e1;
+    g_d += cross(b.e2, g_p);
+    g_e2 += cross(g_p, b.d);
+    gv1 += g_e1;
+    gv2 += g_e2;
+    gv0 -= (g_s + g_e1) + g_e2;
+}
+
+// What one pixel adds to d loss / d sigma_ch: -g_c[ch] * lc[ch], lc[ch] = ((L_0 c_0[ch] + L_1 c_1[ch]) + ...) over its through samples on the
+// screen, in sample order.
+DRT_HD double image_absorb_sigma_term(double g_c, double lc) { return -(g_c * lc); }
+
 // image_bilinear of channel ch and its derivatives w.r.t. fx and fy, the formula differentiated as written; floor and the clamp of the
 // cell carry nothing, so d / du = d / dfx and d / dv = d / dfy.
 DRT_HD double image_bilinear_grad(const ImageTex& tx, double u, double v, int ch, double& dB_dfx, double& dB_dfy) {
@@ -123,10 +151,12 @@ DRT_HD void image_screen_uv_backward(const ImageScreen& sc, d3 o, d3 d, double g
 // loop), hands it through image_transmittance_backward to the IORs and to ci, and bounce_ci_backward adds ci's share to the vertices
 // and to the incoming direction.  A mirrored interaction has no factor.  g_int / g_ext: set.  seed_o / seed_d (both or neither): receive
 // what the reverse loop ends with, the adjoint of the camera ray (o, d) -- the Fresnel share of the incoming direction included
-// (drt_image_camera.h carries it on to the camera).
-template <bool SNELL, bool FRESNEL, typename Add>
+// (drt_image_camera.h carries it on to the camera).  LENGTH (absorbing glass): every interaction whose incoming ray
+// travelled inside the object (sg < 0) also hands g_L, the seed of the interior length, to its t through bounce_t_backward, into the same
+// three vertex gradients and into g_o_in / g_d_in; the interactions before it pass that on, the refracting ones also to the IORs.
+template <bool SNELL, bool FRESNEL, bool LENGTH = false, typename Add>
 DRT_HD void image_path_backward(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 g_ori, d3 g_dir, double g_T,
-                                Add add, double& g_int, double& g_ext, d3* seed_o = nullptr, d3* seed_d = nullptr) {
+                                Add add, double& g_int, double& g_ext, d3* seed_o = nullptr, d3* seed_d = nullptr, double g_L = 0.0) {
     d3 ro[kMaxBounces], rd[kMaxBounces];
     double before[kMaxBounces];                 // prod_{j < k} f_j
     d3 v0, v1, v2;
@@ -167,6 +197,9 @@ DRT_HD void image_path_backward(const PathCtx& c, d3 o, d3 d, const int32_t* fac
                 after = after * image_transmittance(b, c.ior_ext, c.ior_int);
             }
         }
+        if constexpr (LENGTH) {
+            if (b.sg < 0.0) bounce_t_backward(b, g_L, ga, gb, gc, g_o_in, g_d_in);
+        }
         add(vid[0], ga); add(vid[1], gb); add(vid[2], gc);
         g_o = g_o_in; g_d = g_d_in;
     }
@@ -175,25 +208,34 @@ DRT_HD void image_path_backward(const PathCtx& c, d3 o, d3 d, const int32_t* fac
 
 // The whole adjoint of one THROUGH sample: camera ray (o, d), face tape, the exit ray and throughput the forward left behind, and the seed
 // g_c[0 .. tx.c) of its pixel.  False (nothing handed to `add`, g_int = g_ext = 0): the sample does not land on the screen.
-// seed_o / seed_d: image_path_backward's, written only when true is returned.
-template <bool SNELL, bool FRESNEL, typename Add>
+// seed_o / seed_d: image_path_backward's, written only when true is returned.  LENGTH (absorbing glass): A_ch = exp(-(sigma_ch * L)) on
+// the seeds of T and of (u, v), and the seed g_L of the interior length L the forward left behind.
+template <bool SNELL, bool FRESNEL, bool LENGTH = false, typename Add>
 DRT_HD bool image_sample_backward(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 exit_o, d3 exit_d, double T,
                                   const ImageScreen& sc, const ImageTex& tx, const double* g_c, Add add, double& g_int, double& g_ext,
-                                  d3* seed_o = nullptr, d3* seed_d = nullptr) {
+                                  d3* seed_o = nullptr, d3* seed_d = nullptr, double L = 0.0, const double* sigma = nullptr) {
     g_int = 0.0; g_ext = 0.0;
     double u, v;
     if (!image_screen_uv(sc, tx.th, tx.tw, exit_o, exit_d, u, v)) return false;
-    double s_x = 0.0, s_y = 0.0, g_T = 0.0;
+    double s_x = 0.0, s_y = 0.0, g_T = 0.0, g_L = 0.0;
     for (int ch = 0; ch < tx.c; ++ch) {
         double bx, by;
         const double B = image_bilinear_grad(tx, u, v, ch, bx, by);
-        s_x = ch == 0 ? g_c[ch] * bx : s_x + g_c[ch] * bx;
-        s_y = ch == 0 ? g_c[ch] * by : s_y + g_c[ch] * by;
-        g_T = ch == 0 ? g_c[ch] * B : g_T + g_c[ch] * B;
+        [[maybe_unused]] double A = 1.0;
+        double gA = g_c[ch];
+        if constexpr (LENGTH) { A = image_absorb_factor(sigma[ch], L); gA = g_c[ch] * A; }
+        s_x = ch == 0 ? gA * bx : s_x + gA * bx;
+        s_y = ch == 0 ? gA * by : s_y + gA * by;
+        g_T = ch == 0 ? gA * B : g_T + gA * B;
+        if constexpr (LENGTH) {
+            const double col = (A * T) * B;             // the forward's c[ch]
+            const double gl = (g_c[ch] * (-sigma[ch])) * col;
+            g_L = ch == 0 ? gl : g_L + gl;
+        }
     }
     d3 g_o, g_d;
     image_screen_uv_backward(sc, exit_o, exit_d, T * s_x, T * s_y, g_o, g_d);
-    image_path_backward<SNELL, FRESNEL>(c, o, d, faces, face_stride, n_hits, g_o, g_d, g_T, add, g_int, g_ext, seed_o, seed_d);
+    image_path_backward<SNELL, FRESNEL, LENGTH>(c, o, d, faces, face_stride, n_hits, g_o, g_d, g_T, add, g_int, g_ext, seed_o, seed_d, g_L);
     return true;
 }
 

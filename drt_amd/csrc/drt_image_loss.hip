@@ -1,6 +1,7 @@
 // drt_image_loss.hip -- the photometric loss of the refracted image with its vertex and IOR gradients (drt_image_loss.h holds the law;
 // DESIGN.md 10.3), one band of rows per call: the forward wavefront of drt_image.hip with the face tape kept (image_forward, declared in
-// drt_image_wave.h), then the adjoint over the compact list of through samples.
+// drt_image_wave.h), then the adjoint over the compact list of through samples.  The kernels are drt_image_loss_bwd.h's templates and the
+// host body of the call is its image_loss_run; this unit holds the forms <ImageOneView, ImageClear> without CAMERA.
 //
 //   image_forward         all samples : k_image_start, then per interaction k_trace and k_image_shade<., ., tape>, which also records the
 //                                       face of the interaction in the tape [K, n] of the workspace
@@ -11,59 +12,12 @@
 //   k_image_loss_bwd      that list   : image_sample_backward per sample: camera ray formed again (image_sample_ray), exit ray and T from
 //                                       the parked rows, g_c of pixel i / s^2; vertex gradients through PathSink in kPathsBwdBatch-sized
 //                                       fills, the IOR partials through two LossAcc; VERTS = false: no table in LDS
-//                                       (the template: drt_image_loss_bwd.h; here its sixteen instantiations without CAMERA)
 //   k_image_screen_bwd    all pixels  : drt_render_image_loss_screen only (drt_image_screen.hip, through launch_image_screen_bwd): the screen-pose
 //                                       and texture gradients from the same seeds
 //   k_image_camera_bwd    all pixels  : drt_render_image_loss_camera only (drt_image_camera.hip, through launch_image_camera_bwd): the 21
 //                                       camera partials; k_image_loss_bwd is then that unit's, with CAMERA (launch_image_loss_bwd_camera)
 // Everything runs on the caller's stream, nothing is read back, every list size stays on the device.
 #include "drt_image_loss_bwd.h"
-
-// One thread per pixel of the band.  weight / image may be null.
-template <bool DET>
-__global__ void __launch_bounds__(kPathBlock) k_image_loss_resolve(ImageCam cam, ImageBand band, int64_t n_pix, ImageScreen sc, ImageTex tx, ImageFill fill,
-                                                                    bool fresnel, const double* __restrict__ park_ori,
-                                                                    const double* __restrict__ park_dir, const double* __restrict__ thr,
-                                                                    const uint8_t* __restrict__ state, const uint8_t* __restrict__ hits,
-                                                                    const float* __restrict__ target, const float* __restrict__ weight,
-                                                                    double* __restrict__ g_c, float* __restrict__ image, double* loss) {
-    const int64_t pix = (int64_t)blockIdx.x * kPathBlock + threadIdx.x;
-    LossAcc<DET> acc;
-    if (pix < n_pix) {
-        const int s2 = band.s * band.s;
-        const int y = band.y0 + (int)(pix / band.width), x = (int)(pix % band.width);
-        double sum[kImageMaxChannels] = {0.0, 0.0, 0.0};
-        int n_hit, n_through;          // (not wanted here)
-        image_pixel_walk(cam, band, pix, x, y, sc, tx, fill, fresnel, park_ori, park_dir, thr, state, hits, sum, n_hit, n_through);
-        const int64_t row = (int64_t)y * band.width + x;
-        double mean[kImageMaxChannels], g[kImageMaxChannels];
-        for (int ch = 0; ch < tx.c; ++ch) {
-            mean[ch] = sum[ch] / (double)s2;
-            if (image) image[row * tx.c + ch] = (float)mean[ch];
-        }
-        acc.add(image_loss_pixel(mean, tx.c, s2, target + row * tx.c, weight ? (double)weight[row] : 1.0, g));
-        for (int ch = 0; ch < tx.c; ++ch) g_c[pix * tx.c + ch] = g[ch];
-    }
-    acc.flush(loss);
-}
-
-namespace {
-
-// one buffer of the workspace grown to n doubles: never inside a stream capture (`what`, for the message)
-int grow_image_loss_buffer(double*& buf, int64_t& cap, int64_t n, hipStream_t st, const char* who, const char* what) {
-    if (n <= cap) return DRT_OK;
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone)
-        return fail(DRT_E_INVALID, "%s: the first call of this size allocates its %s and cannot run "
-                                   "inside a stream capture: issue one such call eagerly before capturing", who, what);
-    (void)hipFree(buf);
-    buf = nullptr; cap = 0;
-    HIP_TRY(hipMalloc(&buf, sizeof(double) * (size_t)n));
-    cap = n;
-    return DRT_OK;
-}
-
-}  // namespace
 
 // the pixel seeds [n_seed], grown like the throughputs they sit beside (drt_image.hip); the camera-ray seeds [n_cam] (0: none wanted) likewise
 int ensure_image_loss_ws(drt_scene* s, int64_t n_seed, int64_t n_cam, hipStream_t st, const char* who) {
@@ -73,8 +27,8 @@ int ensure_image_loss_ws(drt_scene* s, int64_t n_seed, int64_t n_cam, hipStream_
         if (!lw) return fail(DRT_E_NOMEM, "host allocation failed");
         s->image_loss_ws = lw;
     }
-    { int rc = grow_image_loss_buffer(lw->g_c, lw->cap, n_seed, st, who, "pixel seeds"); if (rc) return rc; }
-    return grow_image_loss_buffer(lw->seeds, lw->seed_cap, n_cam, st, who, "camera-ray seeds");
+    { int rc = grow_doubles(lw->g_c, lw->cap, n_seed, st, who, "pixel seeds"); if (rc) return rc; }
+    return grow_doubles(lw->seeds, lw->seed_cap, n_cam, st, who, "camera-ray seeds");
 }
 
 void image_loss_free(drt_scene* s) {
@@ -105,34 +59,11 @@ int image_loss_call(drt_scene* s, const double* d_verts, const double* camera21,
     if (d_grad_texture && (int64_t)tex_h * tex_w > INT32_MAX)
         return fail(DRT_E_INVALID, "tex_h x tex_w = %d x %d: a texture gradient takes at most 2^31 - 1 texels", tex_h, tex_w);
     const bool seeds_wanted = d_grad_camera && s->n_faces > 0;          // (a scene without triangles has direct samples only)
-    { int rc = ensure_image_loss_ws(s, c.n_pix * channels, seeds_wanted ? 6 * c.n : 0, st, who); if (rc) return rc; }
-    { int rc = image_forward(s, d_verts, c, true, st, who); if (rc) return rc; }
-    const PathsWs& w = *paths_ws_of(s);
+    { int rc = image_loss_run(s, d_verts, c, ImageOneView{c.cam, c.sc}, ImageClear{}, [&](ImageClear&) { return image_forward(s, d_verts, c, true, st, who); },
+                              d_grad_camera ? launch_image_loss_bwd_camera : image_loss_bwd_launch<ImageOneView, ImageClear, false>,
+                              ImageLossOut{d_target, d_weight, d_loss, d_grad_verts, d_grad_ior, d_image, d_count, nullptr}, seeds_wanted ? 6 * c.n : 0, st, who);
+      if (rc) return rc; }
     const ImageLossWs& lw = *static_cast<ImageLossWs*>(s->image_loss_ws);
-    const PathCtx pc = image_path_ctx(s, d_verts, c);
-    double* const park_ori = w.park;
-    double* const park_dir = w.park + 3 * w.fused_cap;
-    const bool det = det_mode();
-    const unsigned pix_grid = (unsigned)((c.n_pix + kPathBlock - 1) / kPathBlock);
-    if (det) k_image_loss_resolve<true><<<pix_grid, kPathBlock, 0, st>>>(c.cam, c.band, c.n_pix, c.sc, c.tx, c.fill, c.fresnel, park_ori, park_dir, w.thr, w.state, w.hits,
-                                                                          d_target, d_weight, lw.g_c, d_image, d_loss);
-    else k_image_loss_resolve<false><<<pix_grid, kPathBlock, 0, st>>>(c.cam, c.band, c.n_pix, c.sc, c.tx, c.fill, c.fresnel, park_ori, park_dir, w.thr, w.state, w.hits,
-                                                                       d_target, d_weight, lw.g_c, d_image, d_loss);
-    if (s->n_faces > 0 && (d_grad_verts || d_grad_ior || d_count || d_grad_camera)) {
-        int32_t* const done = w.idx[0];          // (both ping-pong lists are free once the loop has ended)
-        launch_paths_collect(grid_for(c.n, kPathBlock, 8 * s->n_cu), st, (unsigned)c.n, w.state, done, w.cnt + kCntValid);
-        const int grid = (d_grad_verts ? DRT_BWD_BPC : kImageLossBpc) * s->n_cu;
-        if (d_grad_camera) {
-            int rc = launch_image_loss_bwd_camera(s, pc, c, grid, done, w.cnt + kCntValid, lw.g_c, d_grad_verts, d_grad_ior,
-                                                  reinterpret_cast<unsigned long long*>(d_count), lw.seeds, st);
-            if (rc) return rc;
-        } else {
-            IMAGE_LOSS_BWD_LAUNCH(false, det, c.snell, c.fresnel, d_grad_verts != nullptr, grid, st, pc, c.cam, c.band, c.sc, c.tx, c.max_bounces, park_ori, park_dir,
-                                  w.thr, w.tape, w.hits, done, w.cnt + kCntValid, lw.g_c, d_grad_verts, d_grad_ior, reinterpret_cast<unsigned long long*>(d_count),
-                                  nullptr);
-        }
-    }
-    HIP_TRY(hipGetLastError());
     if (d_grad_screen || d_grad_texture) { int rc = launch_image_screen_bwd(s, c, lw.g_c, d_grad_screen, d_grad_texture, st); if (rc) return rc; }
     if (d_grad_camera) return launch_image_camera_bwd(s, c, lw.g_c, seeds_wanted ? lw.seeds : nullptr, d_grad_camera, st);
     return DRT_OK;

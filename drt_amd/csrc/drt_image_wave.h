@@ -1,10 +1,19 @@
-// drt_image_wave.h -- what the two calls on the refracted image share (drt_image.hip: drt_render_image; drt_image_loss.hip:
-// drt_render_image_loss): the band of rows of one call, the checked call, the forward wavefront (defined in drt_image.hip, as
-// launch_trace_list is in drt_trace.hip) and the walk over the samples of a pixel that both resolve kernels make.
+// drt_image_wave.h -- what the calls on the refracted image share (drt_image.hip, drt_image_loss.hip, drt_image_screen.hip,
+// drt_image_camera.hip, drt_image_views.hip, drt_image_absorb.hip): the band of rows of one call, the checked call, the two policies a
+// kernel of the family is stated over, and the forward half of the family, each kernel once as a template -- k_image_start<VIEW>,
+// k_image_shade<SNELL, FRESNEL, TAPE, PAYLOAD>, image_pixel_walk<PAYLOAD>, k_image_resolve<PAYLOAD> -- with the forward wavefront that
+// launches them (defined in drt_image.hip, as launch_trace_list is in drt_trace.hip).  drt_image_loss_bwd.h holds the loss half.
+//   VIEW     where a row of the band finds its camera and screen: ImageOneView (by value, the call's own) or ImageViewTable (the capture's
+//            table in device memory and the call's id list)
+//   PAYLOAD  what a sample carries beside its throughput: ImageClear (nothing) or ImageAbsorb (the interior length and sigma)
+// A unit instantiates the forms it launches and no others, so a kernel stays in the unit that held it before there was a template
+// (a kernel's register allocation depends on the other kernels of its unit: DESIGN.md section 4).
 #pragma once
+#include <utility>
 #include "drt_device.h"
 #include "drt_pathws.h"
 #include "drt_image.h"
+#include "drt_image_views.h"
 
 struct ImageBand {
     int width, y0, s;              // image width, first row of the band, supersampling
@@ -20,6 +29,48 @@ __device__ __forceinline__ void band_sample(const ImageBand& b, unsigned i, int&
 }
 
 struct ImageFill { double c_void[kImageMaxChannels], c_invalid[kImageMaxChannels]; };
+
+// ---- the view policy: row r of the band (band_sample's y; of a pixel, band.y0 + pix / width) -> whose row it is
+struct ImageViewAt {
+    const ImageCam& cam;
+    const ImageScreen& sc;
+    int y;                         // the row within the view
+    int64_t row;                   // the row of the target / weight planes: pixel (x, y) of the view is at row * width + x
+};
+// the camera and the screen of the call, by value
+struct ImageOneView {
+    ImageCam cam;
+    ImageScreen sc;
+    __device__ __forceinline__ ImageViewAt at(int r) const { return ImageViewAt{cam, sc, r, (int64_t)r}; }
+};
+// a band of the tall image of the listed views (drt_image_views.h): camera and screen are references into the table, read where
+// image_sample_ray and the plane use them; target and weight are the capture's stacks, addressed at ((view * H + y) * W + x)
+struct ImageViewTable {
+    const ImageViewRow* __restrict__ rows;
+    ImageViewIds ids;
+    __device__ __forceinline__ ImageViewAt at(int r) const {
+        int slot, view, y;
+        image_views_row(ids, r, slot, view, y);
+        const ImageViewRow& vr = rows[view];
+        return ImageViewAt{vr.cam, vr.sc, y, (int64_t)view * ids.height + y};
+    }
+};
+
+// ---- the payload policy: what a sample carries beside its throughput, and what a pixel sums beside its colours
+struct ImageSigma { double v[kImageMaxChannels]; };
+struct ImageClear {
+    static constexpr bool kAbsorb = false;
+    struct Sums {};
+};
+struct ImageAbsorb {
+    static constexpr bool kAbsorb = true;
+    double* __restrict__ len;      // the interior length of every sample of the band (PathsWs::len)
+    ImageSigma sigma;
+    struct Sums {
+        double lc[kImageMaxChannels] = {0.0, 0.0, 0.0};          // that of L_j c_j[ch] over the through samples on the screen (the sigma partials)
+        double l_sum;                                            // that of L over the through samples
+    };
+};
 
 // One call after image_call_check: the arguments the two entry points have in common, unpacked.
 struct ImageCall {
@@ -46,9 +97,10 @@ int image_call_check(const double* camera21, int height, int width, int y0, int 
 // [K, n] -- without it the tape is left untouched.  `who`: the entry point, for messages.
 int image_forward(drt_scene* s, const double* d_verts, const ImageCall& call, bool keep_tape, hipStream_t st, const char* who);
 
-// image_forward with the start kernel of the caller's choice (drt_image_views.hip: the samples of several views in one band): `start`
-// launches on a.st, with a.grid blocks of kPathBlock threads, a kernel that does for every sample of the band what k_image_start does;
-// `src` is handed through to it.  image_forward is this with k_image_start and the camera of the call.
+// image_forward with the start and shade kernels of the caller's choice, so that a kernel form is emitted in the unit that asks for it:
+// `start` launches k_image_start<VIEW> on a.st, with a.grid blocks of kPathBlock threads; `shade` launches for list k the form of
+// k_image_shade of its payload (image_shade_launch).  `src` / `shade_src` are handed through to them.  Null `shade`, the default:
+// k_image_shade<., ., ., ImageClear> from drt_image.hip.  image_forward is this with image_start_call and the default shade.
 struct ImageStartArgs {
     const Node4Q* nodes;
     int n_tris;
@@ -60,9 +112,6 @@ struct ImageStartArgs {
     hipStream_t st;
 };
 using ImageStartFn = void (*)(const ImageStartArgs& a, const void* src);
-// ... and with the shade kernel of the caller's choice (drt_image_absorb.hip: k_image_shade plus the interior length): `shade` launches on
-// a.st, with a.grid blocks of kPathBlock threads, a kernel that does for list k what k_image_shade<snell, fresnel, tape != null> does;
-// `shade_src` is handed through to it.  Null, the default: k_image_shade from drt_image.hip's own table, what every call launched before.
 struct ImageShadeArgs {
     PathCtx pc;
     int64_t n_rays;
@@ -81,8 +130,12 @@ struct ImageShadeArgs {
 using ImageShadeFn = void (*)(const ImageShadeArgs& a, const void* shade_src);
 int image_forward_from(drt_scene* s, const double* d_verts, const ImageCall& call, bool keep_tape, hipStream_t st, const char* who, ImageStartFn start,
                        const void* src, ImageShadeFn shade = nullptr, const void* shade_src = nullptr);
-// image_forward's own start (k_image_start with the camera of the call, `src` = the ImageCall), for callers that bring a shade kernel only
+// image_forward's own start (k_image_start<ImageOneView> with the camera of the call, `src` = the ImageCall), for callers that bring a
+// shade kernel only
 void image_start_call(const ImageStartArgs& a, const void* src);
+
+// One buffer of a workspace grown to n doubles (defined in drt_image.hip): never inside a stream capture (`what`, for the message).
+int grow_doubles(double*& buf, int64_t& cap, int64_t n, hipStream_t st, const char* who, const char* what);
 
 // The workspace of the loss calls behind drt_scene::image_loss_ws (drt_image_loss.hip; drt_image_views.hip shares the pixel seeds), and its
 // growth to n_seed doubles of pixel seeds and n_cam doubles of camera-ray seeds (0: none wanted) -- never inside a stream capture.
@@ -101,13 +154,22 @@ constexpr int kImageLossBpc = 4;           // blocks per CU of the adjoint witho
 // ([tex_h, tex_w, C] accumulators, padded to a multiple of three values) are accumulated into; one of them may be null.
 int launch_image_screen_bwd(const drt_scene* s, const ImageCall& call, const double* g_c, double* d_grad_screen, double* d_grad_texture, hipStream_t st);
 
-// Defined in drt_image_camera.hip (drt_render_image_loss_camera).  launch_image_loss_bwd_camera: k_image_loss_bwd with
-// CAMERA on -- what image_loss_call launches over the list of through samples, which here also stores the camera-ray seeds
-// `seeds` [2, band.n, 3] float64 (g_o rows, then g_d rows, under the sample index); d_grad_verts, d_grad_ior and d_count may be null.
+// What a loss call hands out: the planes it compares against and the accumulators it adds into.  Only target and loss must be there.
+struct ImageLossOut {
+    const float *target, *weight;
+    double *loss, *grad_verts, *grad_ior;
+    float* image;
+    int64_t* count;
+    double* grad_sigma;            // ImageAbsorb only
+};
+
+// Defined in drt_image_camera.hip (drt_render_image_loss_camera).  launch_image_loss_bwd_camera: the adjoint launch of a
+// loss call (image_loss_bwd_launch, drt_image_loss_bwd.h) with CAMERA on -- what image_loss_call hands image_loss_run in place of its own
+// unit's launch --, which also stores the camera-ray seeds `seeds` [2, band.n, 3] float64 (g_o rows, then g_d rows, under the sample index).
 // launch_image_camera_bwd: k_image_camera_bwd over the pixels of the band, behind the resolve kernel (g_c) and, on a scene with
 // triangles, behind launch_image_loss_bwd_camera (seeds; not read on a scene without); d_grad_camera: 21 accumulators, kinv then rinv.
-int launch_image_loss_bwd_camera(const drt_scene* s, const PathCtx& pc, const ImageCall& call, int grid, const int32_t* list, const unsigned* n_list,
-                                 const double* g_c, double* d_grad_verts, double* d_grad_ior, unsigned long long* d_count, double* seeds, hipStream_t st);
+int launch_image_loss_bwd_camera(const drt_scene* s, const PathCtx& pc, const ImageCall& c, const ImageOneView& view, const ImageClear& pay, int grid,
+                                 const int32_t* list, const unsigned* n_list, const double* g_c, const ImageLossOut& out, double* seeds, hipStream_t st);
 int launch_image_camera_bwd(const drt_scene* s, const ImageCall& call, const double* g_c, const double* seeds, double* d_grad_camera, hipStream_t st);
 
 // The N sums of a block of 256 threads into their accumulators grad[0 .. N) (whole block): a wave sum each, the four waves' sums added in
@@ -158,32 +220,176 @@ inline PathCtx image_path_ctx(const drt_scene* s, const double* d_verts, const I
     return pc;
 }
 
+
+// ---- the forward kernels of the family, each once
+
+// All samples of the band: forms the sample ray (image_sample_ray) with the camera of the sample's row, top-box test; candidates -> list 0
+// (index + float32 ray), their float64 ray and a throughput of 1 parked in the workspace; one state byte and one hit count per sample.
+template <typename VIEW>
+__global__ void __launch_bounds__(kPathBlock) k_image_start(const Node4Q* __restrict__ nodes, int n_tris, VIEW view, ImageBand band,
+                                                             double* __restrict__ park_ori, double* __restrict__ park_dir, double* __restrict__ thr,
+                                                             uint8_t* __restrict__ state, uint8_t* __restrict__ hits, RayList out, unsigned* count) {
+    __shared__ StageMem stage;
+    stage_init(stage);
+    unsigned first, last;
+    block_run(band.n, first, last);
+    for (unsigned base = first; base < last; base += kPathBlock) {
+        const unsigned i = base + threadIdx.x;
+        bool cand = false;
+        f3 o32{0.f, 0.f, 0.f}, d32{0.f, 0.f, 1.f};
+        if (i < band.n) {
+            state[i] = 0;
+            hits[i] = 0;
+            if (n_tris > 0) {
+                int x, r, j;
+                band_sample(band, i, x, r, j);
+                const ImageViewAt v = view.at(r);
+                d3 o, d;
+                image_sample_ray(v.cam, band.s, x, v.y, j, o, d);
+                o32 = to_f32(o); d32 = to_f32(d);
+                cand = hits_top_boxes(nodes, o32, d32);
+                if (cand) { store_d3(park_ori, i, o); store_d3(park_dir, i, d); thr[i] = 1.0; }
+            }
+        }
+        stage_push(stage, cand, (int32_t)i, o32, d32, out, count);
+    }
+    stage_flush(stage, out, count);
+}
+
+// list k -> list k + 1, as k_paths_shade (drt_paths.hip); FRESNEL: a refracting interaction multiplies the sample's throughput by 1 - R;
+// TAPE: the face of the interaction is written to tape[k, i] (without it `tape` is never touched and may be null); ImageAbsorb: the
+// interior length pay.len[i], one more float64 per sample, stored at k = 0 and added to afterwards (no memset) -- o, d, T and n_refr
+// have the clear form's bits.
+template <bool SNELL, bool FRESNEL, bool TAPE, typename PAYLOAD>
+__global__ void __launch_bounds__(kPathBlock) k_image_shade(PathCtx c, int64_t n_rays, int k, int max_bounces, bool reflect, RayList in,
+                                                             const unsigned* __restrict__ n_in, RayList out, unsigned* n_out,
+                                                             double* __restrict__ park_ori, double* __restrict__ park_dir, double* __restrict__ thr,
+                                                             uint8_t* __restrict__ state, uint8_t* __restrict__ hits, int32_t* __restrict__ tape,
+                                                             PAYLOAD pay) {
+    __shared__ StageMem stage;
+    stage_init(stage);
+    const unsigned n = *n_in;
+    const bool last_stage = k >= max_bounces;
+    unsigned first, last;
+    block_run(n, first, last);
+    for (unsigned base = first; base < last; base += kPathBlock) {
+        const unsigned e = base + threadIdx.x;
+        bool go = false;
+        int64_t i = 0;
+        f3 o32{0.f, 0.f, 0.f}, d32{0.f, 0.f, 1.f};
+        if (e < n) {
+            i = in.idx[e];
+            const int32_t f = in.face[e];
+            if (i >= 0 && i < n_rays) {
+                int n_refr = state[i];
+                if (f < 0) {
+                    if (path_exit_valid(n_refr)) state[i] = (uint8_t)n_refr | kPathDone;
+                } else if (!last_stage) {
+                    if constexpr (TAPE) tape[(int64_t)k * n_rays + i] = f;
+                    hits[i] = (uint8_t)(k + 1);
+                    d3 o = load_d3(park_ori, i), d = load_d3(park_dir, i);
+                    double T = FRESNEL ? thr[i] : 1.0;
+                    // (the length of a sample whose path dies here is stored too: nothing reads it)
+                    go = image_interact<SNELL, FRESNEL>(c, f, reflect, o, d, n_refr, T, [&](const Bounce& b) {
+                        if constexpr (PAYLOAD::kAbsorb) pay.len[i] = image_absorb_length(b, k == 0 ? 0.0 : pay.len[i]);
+                    });
+                    if (go) {
+                        store_d3(park_ori, i, o); store_d3(park_dir, i, d);
+                        if (FRESNEL) thr[i] = T;
+                        state[i] = (uint8_t)n_refr;
+                        o32 = to_f32(o); d32 = to_f32(d);
+                    }
+                }
+            }
+        }
+        if (!last_stage) stage_push(stage, go, (int32_t)i, o32, d32, out, n_out);
+    }
+    if (!last_stage) stage_flush(stage, out, n_out);
+}
+
+// k_image_shade<., ., ., PAYLOAD> under (snell, fresnel, tape) from a table of the eight, launched as a shade hook of image_forward_from is to
+template <typename PAYLOAD, int... I>
+void image_shade_launch(const ImageShadeArgs& a, const PAYLOAD& pay, std::integer_sequence<int, I...>) {
+    using Kernel = decltype(&k_image_shade<false, false, false, PAYLOAD>);
+    static const Kernel kernels[] = {k_image_shade<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0, PAYLOAD>...};
+    kernels[(a.snell ? 4 : 0) | (a.fresnel ? 2 : 0) | (a.tape ? 1 : 0)]<<<a.grid, kPathBlock, 0, a.st>>>(
+        a.pc, a.n_rays, a.k, a.max_bounces, a.reflect, a.in, a.n_in, a.out, a.n_out, a.park_ori, a.park_dir, a.thr, a.state, a.hits, a.tape, pay);
+}
+template <typename PAYLOAD>
+void image_shade_launch(const ImageShadeArgs& a, const PAYLOAD& pay) { image_shade_launch(a, pay, std::make_integer_sequence<int, 8>{}); }
+
 // The s x s contiguous samples of pixel `pix` = (x, y) of the band, in order: class, the camera ray formed again (direct) or the parked
 // exit ray and throughput (through), colour; sum[0 .. tx.c) is the ordered float64 sum of the colours, n_hit / n_through count the
-// samples that met the mesh / completed their path.
+// samples that met the mesh / completed their path.  ImageAbsorb: the colours are attenuated along the interior length, and `more`
+// receives the ordered sums the sigma partials and the length plane need.  (The channel loop and the count of the through samples are
+// spelt per payload, here and in k_image_loss_resolve: under the clear spelling the absorbing kernels keep their per-channel arrays in
+// LDS, 8 to 18 KiB a block, instead of registers -- profiles/image_family_resources.txt.)
+template <typename PAYLOAD>
 __device__ __forceinline__ void image_pixel_walk(const ImageCam& cam, const ImageBand& band, int64_t pix, int x, int y, const ImageScreen& sc, const ImageTex& tx,
-                                                 const ImageFill& fill, bool fresnel, const double* __restrict__ park_ori,
+                                                 const ImageFill& fill, bool fresnel, const PAYLOAD& pay, const double* __restrict__ park_ori,
                                                  const double* __restrict__ park_dir, const double* __restrict__ thr,
-                                                 const uint8_t* __restrict__ state, const uint8_t* __restrict__ hits, double* sum, int& n_hit,
-                                                 int& n_through) {
+                                                 const uint8_t* __restrict__ state, const uint8_t* __restrict__ hits, double* sum,
+                                                 typename PAYLOAD::Sums& more, int& n_hit, int& n_through) {
     const int s2 = band.s * band.s;
     n_hit = 0; n_through = 0;
+    if constexpr (PAYLOAD::kAbsorb) more.l_sum = 0.0;
     for (int j = 0; j < s2; ++j) {
         const int64_t i = pix * s2 + j;
         const bool was_hit = hits[i] != 0, done = (state[i] & kPathDone) != 0;
         const int cls = image_class(was_hit, done);
         n_hit += was_hit ? 1 : 0;
-        n_through += cls == kImageThrough ? 1 : 0;
+        if constexpr (!PAYLOAD::kAbsorb) n_through += cls == kImageThrough ? 1 : 0;
         d3 o{0.0, 0.0, 0.0}, d{0.0, 0.0, 1.0};
         double T = 1.0;
+        [[maybe_unused]] double L = 0.0;
         if (cls == kImageDirect) {
             image_sample_ray(cam, band.s, x, y, j, o, d);
         } else if (cls == kImageThrough) {
             o = load_d3(park_ori, i); d = load_d3(park_dir, i);
             if (fresnel) T = thr[i];
+            if constexpr (PAYLOAD::kAbsorb) {
+                L = pay.len[i];
+                more.l_sum = n_through == 0 ? L : more.l_sum + L;
+                ++n_through;
+            }
         }
         double c[kImageMaxChannels];
-        image_sample_colour(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c);
-        for (int ch = 0; ch < tx.c; ++ch) sum[ch] = j == 0 ? c[ch] : sum[ch] + c[ch];
+        if constexpr (PAYLOAD::kAbsorb) {
+            const bool lit = image_sample_colour<true>(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c, L, pay.sigma.v);
+#pragma unroll
+            for (int ch = 0; ch < kImageMaxChannels; ++ch) {
+                if (ch >= tx.c) continue;
+                sum[ch] = j == 0 ? c[ch] : sum[ch] + c[ch];
+                if (lit && cls == kImageThrough) more.lc[ch] = more.lc[ch] + L * c[ch];
+            }
+        } else {
+            image_sample_colour(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c);
+            for (int ch = 0; ch < tx.c; ++ch) sum[ch] = j == 0 ? c[ch] : sum[ch] + c[ch];
+        }
+    }
+}
+
+// One thread per pixel of the band: the mean of its samples' colours.  hit / through may be null; so may `length` (ImageAbsorb only: the
+// mean of L over the pixel's through samples).
+template <typename PAYLOAD>
+__global__ void __launch_bounds__(kPathBlock) k_image_resolve(ImageCam cam, ImageBand band, int64_t n_pix, ImageScreen sc, ImageTex tx, ImageFill fill, bool fresnel,
+                                                               PAYLOAD pay, const double* __restrict__ park_ori, const double* __restrict__ park_dir,
+                                                               const double* __restrict__ thr, const uint8_t* __restrict__ state,
+                                                               const uint8_t* __restrict__ hits, float* __restrict__ image, float* __restrict__ hit,
+                                                               float* __restrict__ through, float* __restrict__ length) {
+    const int64_t pix = (int64_t)blockIdx.x * kPathBlock + threadIdx.x;
+    if (pix >= n_pix) return;
+    const int s2 = band.s * band.s;
+    const int y = band.y0 + (int)(pix / band.width), x = (int)(pix % band.width);
+    double acc[kImageMaxChannels] = {0.0, 0.0, 0.0};
+    typename PAYLOAD::Sums more;
+    int n_hit, n_through;
+    image_pixel_walk(cam, band, pix, x, y, sc, tx, fill, fresnel, pay, park_ori, park_dir, thr, state, hits, acc, more, n_hit, n_through);
+    const int64_t row = (int64_t)y * band.width + x;
+    for (int ch = 0; ch < tx.c; ++ch) image[row * tx.c + ch] = (float)(acc[ch] / (double)s2);
+    if (hit) hit[row] = (float)((double)n_hit / (double)s2);
+    if (through) through[row] = (float)((double)n_through / (double)s2);
+    if constexpr (PAYLOAD::kAbsorb) {
+        if (length) length[row] = n_through ? (float)(more.l_sum / (double)n_through) : 0.f;
     }
 }

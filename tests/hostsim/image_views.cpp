@@ -1,7 +1,7 @@
 // tests/hostsim/image_views.cpp -- drt_amd/csrc/drt_image_views.h compiled for the host (g++ -ffp-contract=off): the mapping of a band of
 // the tall image of k stacked views to (view, x, y, sample) and the lookup of the view's table row, and the image loss of a list of views
-// through that mapping in plain loops -- per sample what k_image_views_start / _loss_resolve / _loss_bwd do, with the classes and the face
-// tapes handed in as in tests/hostsim/image_loss.cpp (no tracer takes part).  Test-only.
+// through that mapping in plain loops -- per sample what k_image_start / k_image_loss_resolve / k_image_loss_bwd do under ImageViewTable
+// (drt_image_wave.h), with the classes and the face tapes handed in as in tests/hostsim/image_loss.cpp (no tracer takes part).  Test-only.
 #include "../../drt_amd/csrc/drt_image_loss.h"
 #include "../../drt_amd/csrc/drt_image_views.h"
 
