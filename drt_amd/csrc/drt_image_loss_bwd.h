@@ -13,14 +13,16 @@
 // residual against the target, the loss term (LossAcc), the seed g_c = 2 w r / s^2 of the pixel's samples [n_pix, C]; optionally the
 // float32 image -- the bits k_image_resolve writes.  target and weight are addressed at the view's row (ImageViewAt::row).  ImageAbsorb:
 // also the C sigma partials -g_c[ch] sum_j L_j c_j[ch], which need forward values only (LossAcc x 3 through block_flush).
-// weight / image / grad_sigma may be null.  (The channel loops are spelt per payload, as in image_pixel_walk.)
-template <bool DET, typename VIEW, typename PAYLOAD>
+// weight / image / grad_sigma may be null.  (The channel loops are spelt per payload, as in image_pixel_walk.)  BACKGROUND: the walk's
+// (drt_image_wave.h); the default is the screen alone, the text of before.
+template <bool DET, typename VIEW, typename PAYLOAD, typename BACKGROUND = ImageScreenOnly>
 __global__ void __launch_bounds__(kPathBlock) k_image_loss_resolve(VIEW view, ImageBand band, int64_t n_pix, ImageTex tx, ImageFill fill, bool fresnel, PAYLOAD pay,
                                                                     const double* __restrict__ park_ori, const double* __restrict__ park_dir,
                                                                     const double* __restrict__ thr, const uint8_t* __restrict__ state,
                                                                     const uint8_t* __restrict__ hits, const float* __restrict__ target,
                                                                     const float* __restrict__ weight, double* __restrict__ g_c,
-                                                                    float* __restrict__ image, double* loss, double* grad_sigma) {
+                                                                    float* __restrict__ image, double* loss, double* grad_sigma,
+                                                                    BACKGROUND bg = BACKGROUND{}) {
     const int64_t pix = (int64_t)blockIdx.x * kPathBlock + threadIdx.x;
     LossAcc<DET> acc;
     [[maybe_unused]] LossAcc<DET> sig[kImageMaxChannels];
@@ -31,7 +33,7 @@ __global__ void __launch_bounds__(kPathBlock) k_image_loss_resolve(VIEW view, Im
         double sum[kImageMaxChannels] = {0.0, 0.0, 0.0};
         typename PAYLOAD::Sums more;
         int n_hit, n_through;          // (not wanted here)
-        image_pixel_walk(v.cam, band, pix, x, v.y, v.sc, tx, fill, fresnel, pay, park_ori, park_dir, thr, state, hits, sum, more, n_hit, n_through);
+        image_pixel_walk(v.cam, band, pix, x, v.y, v.sc, tx, fill, fresnel, pay, park_ori, park_dir, thr, state, hits, sum, more, n_hit, n_through, bg);
         const int64_t row = v.row * band.width + x;
         if constexpr (PAYLOAD::kAbsorb) {
             double mean[kImageMaxChannels] = {0.0, 0.0, 0.0}, g[kImageMaxChannels] = {0.0, 0.0, 0.0};
@@ -72,13 +74,16 @@ __global__ void __launch_bounds__(kPathBlock) k_image_loss_resolve(VIEW view, Im
 // in kPathsBwdBatch-sized fills, the IOR partials through two LossAcc; VERTS = false: no table in LDS.  grad_verts (VERTS), grad_ior and
 // count may each be null.  CAMERA: seeds [2, band.n, 3] receives (g_o; g_d) of every listed sample that lands on the screen, under its
 // sample index; the other rows are left as they are.  The absorbing forms with the table ask for two blocks per CU: without that bound
-// they drop to one wave (profiles/image_absorb_resources.txt).
-template <bool DET, bool SNELL, bool FRESNEL, bool VERTS, typename VIEW, typename PAYLOAD, bool CAMERA>
+// they drop to one wave (profiles/image_absorb_resources.txt).  BACKGROUND with an environment (ImageClear, no CAMERA): every listed
+// sample carries a gradient, through the screen where its exit ray lands on it and through the environment lookup otherwise
+// (image_env_sample_backward); the reflection's adjoint is a kernel of its own (drt_image_env.hip).
+template <bool DET, bool SNELL, bool FRESNEL, bool VERTS, typename VIEW, typename PAYLOAD, bool CAMERA, typename BACKGROUND = ImageScreenOnly>
 __global__ void __launch_bounds__(256, PAYLOAD::kAbsorb && VERTS ? 2 : 1)
     k_image_loss_bwd(PathCtx c, VIEW view, ImageBand band, ImageTex tx, PAYLOAD pay, int max_bounces, const double* __restrict__ park_ori,
                      const double* __restrict__ park_dir, const double* __restrict__ thr, const int32_t* __restrict__ tape,
                      const uint8_t* __restrict__ hits, const int32_t* __restrict__ list, const unsigned* __restrict__ n_list,
-                     const double* __restrict__ g_c, double* grad_verts, double* grad_ior, unsigned long long* count, double* seeds) {
+                     const double* __restrict__ g_c, double* grad_verts, double* grad_ior, unsigned long long* count, double* seeds,
+                     BACKGROUND bg = BACKGROUND{}) {
     int64_t n = *n_list;
     if (n > (int64_t)band.n) n = band.n;
     LossAcc<DET> acc_int, acc_ext;
@@ -99,9 +104,17 @@ __global__ void __launch_bounds__(256, PAYLOAD::kAbsorb && VERTS ? 2 : 1)
         if constexpr (PAYLOAD::kAbsorb) { L = pay.len[i]; sigma = pay.sigma.v; }
         [[maybe_unused]] d3 so, sd;
         double gi, ge;
-        if (image_sample_backward<SNELL, FRESNEL, PAYLOAD::kAbsorb>(c, o, d, tape + i, (int64_t)band.n, min((int)hits[i], max_bounces), load_d3(park_ori, i),
-                                                                    load_d3(park_dir, i), FRESNEL ? thr[i] : 1.0, v.sc, tx, g, add, gi, ge,
-                                                                    CAMERA ? &so : nullptr, CAMERA ? &sd : nullptr, L, sigma)) {
+        bool carried;
+        if constexpr (BACKGROUND::kEnv) {
+            static_assert(!PAYLOAD::kAbsorb && !CAMERA, "an environment goes with clear glass and without camera seeds");
+            carried = image_env_sample_backward<SNELL, FRESNEL>(c, o, d, tape + i, (int64_t)band.n, min((int)hits[i], max_bounces), load_d3(park_ori, i),
+                                                                load_d3(park_dir, i), FRESNEL ? thr[i] : 1.0, v.sc, tx, bg.screen, bg.env, g, add, gi, ge);
+        } else {
+            carried = image_sample_backward<SNELL, FRESNEL, PAYLOAD::kAbsorb>(c, o, d, tape + i, (int64_t)band.n, min((int)hits[i], max_bounces), load_d3(park_ori, i),
+                                                                              load_d3(park_dir, i), FRESNEL ? thr[i] : 1.0, v.sc, tx, g, add, gi, ge,
+                                                                              CAMERA ? &so : nullptr, CAMERA ? &sd : nullptr, L, sigma);
+        }
+        if (carried) {
             acc_int.add(gi); acc_ext.add(ge);
             ++cnt;
             if constexpr (CAMERA) {
@@ -118,15 +131,15 @@ __global__ void __launch_bounds__(256, PAYLOAD::kAbsorb && VERTS ? 2 : 1)
 }
 
 // k_image_loss_bwd<., ., ., ., VIEW, PAYLOAD, CAMERA> under (deterministic, snell, fresnel, verts), from a table of the sixteen
-template <typename VIEW, typename PAYLOAD, bool CAMERA, int... I>
+template <typename VIEW, typename PAYLOAD, bool CAMERA, typename BACKGROUND, int... I>
 auto image_loss_bwd_kernel(int sel, std::integer_sequence<int, I...>) {
-    using Kernel = decltype(&k_image_loss_bwd<false, false, false, false, VIEW, PAYLOAD, CAMERA>);
-    static const Kernel kernels[] = {k_image_loss_bwd<(I & 8) != 0, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0, VIEW, PAYLOAD, CAMERA>...};
+    using Kernel = decltype(&k_image_loss_bwd<false, false, false, false, VIEW, PAYLOAD, CAMERA, BACKGROUND>);
+    static const Kernel kernels[] = {k_image_loss_bwd<(I & 8) != 0, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0, VIEW, PAYLOAD, CAMERA, BACKGROUND>...};
     return kernels[sel];
 }
-template <typename VIEW, typename PAYLOAD, bool CAMERA>
+template <typename VIEW, typename PAYLOAD, bool CAMERA, typename BACKGROUND = ImageScreenOnly>
 auto image_loss_bwd_kernel(bool det, bool snell, bool fresnel, bool verts) {
-    return image_loss_bwd_kernel<VIEW, PAYLOAD, CAMERA>((det ? 8 : 0) | (snell ? 4 : 0) | (fresnel ? 2 : 0) | (verts ? 1 : 0), std::make_integer_sequence<int, 16>{});
+    return image_loss_bwd_kernel<VIEW, PAYLOAD, CAMERA, BACKGROUND>((det ? 8 : 0) | (snell ? 4 : 0) | (fresnel ? 2 : 0) | (verts ? 1 : 0), std::make_integer_sequence<int, 16>{});
 }
 
 // The adjoint launch of a loss call on `st`, behind the resolve kernel (g_c) and launch_paths_collect (list, n_list): k_image_loss_bwd
@@ -137,7 +150,7 @@ int image_loss_bwd_launch(const drt_scene* s, const PathCtx& pc, const ImageCall
     const PathsWs& w = *static_cast<const PathsWs*>(s->paths_ws);
     image_loss_bwd_kernel<VIEW, PAYLOAD, CAMERA>(det_mode(), c.snell, c.fresnel, out.grad_verts != nullptr)<<<grid, 256, 0, st>>>(
         pc, view, c.band, c.tx, pay, c.max_bounces, w.park, w.park + 3 * w.fused_cap, w.thr, w.tape, w.hits, list, n_list, g_c, out.grad_verts, out.grad_ior,
-        reinterpret_cast<unsigned long long*>(out.count), seeds);
+        reinterpret_cast<unsigned long long*>(out.count), seeds, ImageScreenOnly{});
     HIP_TRY(hipGetLastError());
     return DRT_OK;
 }
@@ -158,7 +171,7 @@ int image_loss_run(drt_scene* s, const double* d_verts, const ImageCall& c, cons
     const unsigned pix_grid = (unsigned)((c.n_pix + kPathBlock - 1) / kPathBlock);
     auto resolve = det_mode() ? k_image_loss_resolve<true, VIEW, PAYLOAD> : k_image_loss_resolve<false, VIEW, PAYLOAD>;
     resolve<<<pix_grid, kPathBlock, 0, st>>>(view, c.band, c.n_pix, c.tx, c.fill, c.fresnel, pay, w.park, w.park + 3 * w.fused_cap, w.thr, w.state, w.hits, out.target,
-                                             out.weight, lw.g_c, out.image, out.loss, out.grad_sigma);
+                                             out.weight, lw.g_c, out.image, out.loss, out.grad_sigma, ImageScreenOnly{});
     if (s->n_faces > 0 && (out.grad_verts || out.grad_ior || out.count || n_cam)) {
         int32_t* const done = w.idx[0];          // (both ping-pong lists are free once the loop has ended)
         launch_paths_collect(grid_for(c.n, kPathBlock, 8 * s->n_cu), st, (unsigned)c.n, w.state, done, w.cnt + kCntValid);

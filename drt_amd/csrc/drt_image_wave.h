@@ -1,11 +1,13 @@
 // drt_image_wave.h -- what the calls on the refracted image share (drt_image.hip, drt_image_loss.hip, drt_image_screen.hip,
-// drt_image_camera.hip, drt_image_views.hip, drt_image_absorb.hip): the band of rows of one call, the checked call, the two policies a
+// drt_image_camera.hip, drt_image_views.hip, drt_image_absorb.hip, drt_image_env.hip): the band of rows of one call, the checked call, the two policies a
 // kernel of the family is stated over, and the forward half of the family, each kernel once as a template -- k_image_start<VIEW>,
-// k_image_shade<SNELL, FRESNEL, TAPE, PAYLOAD>, image_pixel_walk<PAYLOAD>, k_image_resolve<PAYLOAD> -- with the forward wavefront that
-// launches them (defined in drt_image.hip, as launch_trace_list is in drt_trace.hip).  drt_image_loss_bwd.h holds the loss half.
-//   VIEW     where a row of the band finds its camera and screen: ImageOneView (by value, the call's own) or ImageViewTable (the capture's
-//            table in device memory and the call's id list)
-//   PAYLOAD  what a sample carries beside its throughput: ImageClear (nothing) or ImageAbsorb (the interior length and sigma)
+// k_image_shade<SNELL, FRESNEL, TAPE, PAYLOAD>, image_pixel_walk<PAYLOAD, BACKGROUND>, k_image_resolve<PAYLOAD, BACKGROUND> -- with the forward
+// wavefront that launches them (defined in drt_image.hip, as launch_trace_list is in drt_trace.hip).  drt_image_loss_bwd.h holds the loss half.
+//   VIEW        where a row of the band finds its camera and screen: ImageOneView (by value, the call's own) or ImageViewTable (the capture's
+//               table in device memory and the call's id list)
+//   PAYLOAD     what a sample carries beside its throughput: ImageClear (nothing) or ImageAbsorb (the interior length and sigma)
+//   BACKGROUND  what a sample's exit ray looks at: ImageScreenOnly (the screen, `void` beside it: the default, and the text of before) or
+//               ImageScreenEnv (a screen or none, and an environment map where the screen is not: drt_image_env.h)
 // A unit instantiates the forms it launches and no others, so a kernel stays in the unit that held it before there was a template
 // (a kernel's register allocation depends on the other kernels of its unit: DESIGN.md section 4).
 #pragma once
@@ -13,6 +15,7 @@
 #include "drt_device.h"
 #include "drt_pathws.h"
 #include "drt_image.h"
+#include "drt_image_env.h"
 #include "drt_image_views.h"
 
 struct ImageBand {
@@ -70,6 +73,28 @@ struct ImageAbsorb {
         double lc[kImageMaxChannels] = {0.0, 0.0, 0.0};          // that of L_j c_j[ch] over the through samples on the screen (the sigma partials)
         double l_sum;                                            // that of L over the through samples
     };
+};
+
+// ---- the background policy: where the colour of a direct or through sample comes from.  A form without an environment holds no trace of
+// it (`if constexpr (BACKGROUND::kEnv)`, as kAbsorb); it goes with ImageClear only.
+struct ImageScreenOnly { static constexpr bool kEnv = false; };
+struct ImageScreenEnv {
+    static constexpr bool kEnv = true, kReflect = false;
+    bool screen;                   // false: the call has no screen (and no texture); every ray sees the environment
+    ImageEnv env;
+};
+// ... with the reflection off the outer surface added to a through sample whose reflected ray was seen to leave unoccluded (the bit
+// kImageReflectSeen of its state byte, set by drt_image_env.hip's reflection pass): the walk forms the camera ray again and recomputes the
+// one Bounce of the first face (tape row 0), as it does the camera ray of a direct sample
+constexpr uint8_t kImageReflectSeen = 0x40;          // beside the refraction count (<= 8) and kPathDone (0x80)
+struct ImageScreenEnvReflect {
+    static constexpr bool kEnv = true, kReflect = true;
+    bool screen;
+    ImageEnv env;
+    PathCtx pc;
+    bool snell;
+    const int32_t* __restrict__ first_face;          // tape row 0: the face of every sample's first interaction
+    float* __restrict__ reflect;                     // the plane `reflect` [height, width], may be null
 };
 
 // One call after image_call_check: the arguments the two entry points have in common, unpacked.
@@ -324,12 +349,14 @@ void image_shade_launch(const ImageShadeArgs& a, const PAYLOAD& pay) { image_sha
 // receives the ordered sums the sigma partials and the length plane need.  (The channel loop and the count of the through samples are
 // spelt per payload, here and in k_image_loss_resolve: under the clear spelling the absorbing kernels keep their per-channel arrays in
 // LDS, 8 to 18 KiB a block, instead of registers -- profiles/image_family_resources.txt.)
-template <typename PAYLOAD>
+template <typename PAYLOAD, typename BACKGROUND = ImageScreenOnly>
 __device__ __forceinline__ void image_pixel_walk(const ImageCam& cam, const ImageBand& band, int64_t pix, int x, int y, const ImageScreen& sc, const ImageTex& tx,
                                                  const ImageFill& fill, bool fresnel, const PAYLOAD& pay, const double* __restrict__ park_ori,
                                                  const double* __restrict__ park_dir, const double* __restrict__ thr,
                                                  const uint8_t* __restrict__ state, const uint8_t* __restrict__ hits, double* sum,
-                                                 typename PAYLOAD::Sums& more, int& n_hit, int& n_through) {
+                                                 typename PAYLOAD::Sums& more, int& n_hit, int& n_through, const BACKGROUND& bg = BACKGROUND{},
+                                                 int* n_reflect = nullptr) {
+    static_assert(!(PAYLOAD::kAbsorb && BACKGROUND::kEnv), "an environment goes with clear glass only");
     const int s2 = band.s * band.s;
     n_hit = 0; n_through = 0;
     if constexpr (PAYLOAD::kAbsorb) more.l_sum = 0.0;
@@ -363,7 +390,22 @@ __device__ __forceinline__ void image_pixel_walk(const ImageCam& cam, const Imag
                 if (lit && cls == kImageThrough) more.lc[ch] = more.lc[ch] + L * c[ch];
             }
         } else {
-            image_sample_colour(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c);
+            if constexpr (BACKGROUND::kEnv) {
+                image_env_sample_colour(sc, tx, bg.screen, bg.env, cls, o, d, T, fill.c_invalid, c);
+                if constexpr (BACKGROUND::kReflect) {
+                    if (cls == kImageThrough && (state[i] & kImageReflectSeen)) {
+                        d3 co, cd, ro, wr;
+                        double R1;
+                        image_sample_ray(cam, band.s, x, y, j, co, cd);
+                        const bool seen = bg.snell ? image_reflect_first<true>(bg.pc, bg.first_face[i], co, cd, ro, wr, R1)
+                                                   : image_reflect_first<false>(bg.pc, bg.first_face[i], co, cd, ro, wr, R1);
+                        if (seen) {
+                            image_env_add_reflection(sc, tx, bg.screen, bg.env, ro, wr, R1, c);
+                            if (n_reflect) ++*n_reflect;
+                        }
+                    }
+                }
+            } else image_sample_colour(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c);
             for (int ch = 0; ch < tx.c; ++ch) sum[ch] = j == 0 ? c[ch] : sum[ch] + c[ch];
         }
     }
@@ -371,12 +413,12 @@ __device__ __forceinline__ void image_pixel_walk(const ImageCam& cam, const Imag
 
 // One thread per pixel of the band: the mean of its samples' colours.  hit / through may be null; so may `length` (ImageAbsorb only: the
 // mean of L over the pixel's through samples).
-template <typename PAYLOAD>
+template <typename PAYLOAD, typename BACKGROUND = ImageScreenOnly>
 __global__ void __launch_bounds__(kPathBlock) k_image_resolve(ImageCam cam, ImageBand band, int64_t n_pix, ImageScreen sc, ImageTex tx, ImageFill fill, bool fresnel,
                                                                PAYLOAD pay, const double* __restrict__ park_ori, const double* __restrict__ park_dir,
                                                                const double* __restrict__ thr, const uint8_t* __restrict__ state,
                                                                const uint8_t* __restrict__ hits, float* __restrict__ image, float* __restrict__ hit,
-                                                               float* __restrict__ through, float* __restrict__ length) {
+                                                               float* __restrict__ through, float* __restrict__ length, BACKGROUND bg = BACKGROUND{}) {
     const int64_t pix = (int64_t)blockIdx.x * kPathBlock + threadIdx.x;
     if (pix >= n_pix) return;
     const int s2 = band.s * band.s;
@@ -384,8 +426,14 @@ __global__ void __launch_bounds__(kPathBlock) k_image_resolve(ImageCam cam, Imag
     double acc[kImageMaxChannels] = {0.0, 0.0, 0.0};
     typename PAYLOAD::Sums more;
     int n_hit, n_through;
-    image_pixel_walk(cam, band, pix, x, y, sc, tx, fill, fresnel, pay, park_ori, park_dir, thr, state, hits, acc, more, n_hit, n_through);
+    [[maybe_unused]] int n_reflect = 0;
+    image_pixel_walk(cam, band, pix, x, y, sc, tx, fill, fresnel, pay, park_ori, park_dir, thr, state, hits, acc, more, n_hit, n_through, bg, &n_reflect);
     const int64_t row = (int64_t)y * band.width + x;
+    if constexpr (BACKGROUND::kEnv) {
+        if constexpr (BACKGROUND::kReflect) {
+            if (bg.reflect) bg.reflect[row] = (float)((double)n_reflect / (double)s2);
+        }
+    }
     for (int ch = 0; ch < tx.c; ++ch) image[row * tx.c + ch] = (float)(acc[ch] / (double)s2);
     if (hit) hit[row] = (float)((double)n_hit / (double)s2);
     if (through) through[row] = (float)((double)n_through / (double)s2);

@@ -861,6 +861,23 @@ def enqueue_image_absorb_term(scene, vertices, a, ior, texture, target, weight, 
     return [vertices, texture, target, weight]
 
 
+def enqueue_image_env_term(scene, vertices, a, ior, texture, env, target, weight, loss_ptr, grad_ptr=None, grad_ior_ptr=None, image_ptr=None, count_ptr=None):
+    """``enqueue_image_term`` in front of an environment: ONE view's photometric image term under ``a["environment"]`` and
+    ``a["reflection"]``, band after band into one set of accumulators, on the current stream; the one place that packs the arguments of
+    drt_render_image_loss_env.  ``texture``: a contiguous float32 device tensor, or None with ``a["screen"]`` None (no screen); ``env``:
+    the environment's texels as a contiguous float32 device tensor.  Every ``*_ptr`` but the first may be None.  The caller is inside
+    ``_on(device)``.  Returns what the enqueued kernels read, for the caller to keep alive."""
+    fn, H, W, C = _lib.lib().drt_render_image_loss_env, a["height"], a["width"], a["channels"]
+    rot = a["environment"].packed()
+    for y0, y1 in a["bands"]:
+        _lib.check(fn(
+            scene.optix_mesh._h, vertices.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
+            a["law_flags"], a["fresnel"], None if texture is None else a["screen"].ctypes.data, _lib.ptr(texture), 0 if texture is None else texture.shape[0],
+            0 if texture is None else texture.shape[1], C, a["void"].ctypes.data, a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss_ptr,
+            grad_ptr, grad_ior_ptr, image_ptr, count_ptr, env.data_ptr(), env.shape[0], env.shape[1], rot.ctypes.data, int(a["reflection"]), _stream()))
+    return [vertices, texture, env, target, weight]
+
+
 def enqueue_image_views_term(scene, vertices, binding, view_ids, texture, law, supersample, fresnel, void, invalid, ior, loss_ptr, grad_ptr,
                              grad_ior_ptr=None, count_ptr=None, bands=None):
     """Enqueues the photometric image term of the listed views of ``binding`` (a ``render.ImageViews``) -- the SUM over ``view_ids`` of one
@@ -1002,6 +1019,21 @@ def _image_term(scene, a, ior, tex, target, weight, entry="plain"):
             enqueue_image_term(scene, v, a, ior, tex, target, weight, loss.data_ptr(), _lib.ptr(cells.get(_VERTS)), _lib.ptr(cells.get("ior")), _lib.ptr(image),
                                count.data_ptr(), *(_lib.ptr(cells.get(k)) for k in ("screen", "texture", "camera")), entry=entry)
     return _Term(dev, accs, enqueue, feeds, count, image)
+
+
+def _image_env_term(scene, a, ior, tex, env, target, weight):
+    """The term of image_loss_fused in front of an environment (``enqueue_image_env_term``) for the inputs (vertices,
+    ior_int, ior_ext): the vertex accumulator follows ``a["vertices"]``, the IOR pair is always there."""
+    v = _f64c(scene.vertices.detach(), "vertices")
+    dev = v.device
+    count = torch.zeros((), dtype=torch.int64, device=dev)
+    image = torch.empty((a["height"], a["width"], a["channels"]), dtype=torch.float32, device=dev) if a["want_image"] else None
+
+    def enqueue(loss, cells):
+        with _on(dev):
+            enqueue_image_env_term(scene, v, a, ior, tex, env, target, weight, loss.data_ptr(), _lib.ptr(cells.get(_VERTS)), _lib.ptr(cells.get("ior")),
+                                   _lib.ptr(image), count.data_ptr())
+    return _Term(dev, _verts_ior_accs(v, a["vertices"]), enqueue, ((_VERTS, None),) + _IOR_FEEDS, count, image)
 
 
 def _image_absorb_term(scene, a, ior, tex, target, weight):
@@ -1227,7 +1259,7 @@ class Scene(StepwiseMixin):
         return _RenderPaths.apply(self.vertices, origin, ray_dir, self, ior, int(max_bounces), _law_flags(tir, refraction))
 
     def render_image(self, camera_M, height, width, screen, texture, *, supersample=1, max_bounces=2, tir="drop", refraction="reference",
-                     fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False, absorption=None):
+                     fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False, absorption=None, environment=None, reflection=False):
         """What the pinhole camera ``camera_M`` = (R, K, R^-1, K^-1) sees of a textured planar screen through this mesh: a float32 image
         ``[height, width, C]`` on the device (drt_render_image; csrc/drt_image.h and DESIGN.md 10.2 state the law).  ``screen``: a
         ``drt_amd.render.Screen``; ``texture``: float32 ``[Th, Tw, C]`` (or ``[Th, Tw]``), C in {1, 3}, numpy or a device tensor.
@@ -1244,18 +1276,40 @@ class Scene(StepwiseMixin):
         one number (every channel), C numbers, or a float64 tensor ``[C]``, each finite and >= 0: a through sample is also weighted by
         ``exp(-absorption_ch L)``, ``L`` the length its path travels inside the object (drt_render_image_absorb; csrc/drt_image_absorb.h
         and DESIGN.md 10.7 state the law; 8 B more workspace per sample).  ``want_planes`` then returns a fourth plane, ``length``: the
-        mean of ``L`` over the pixel's through samples, 0 where there are none."""
+        mean of ``L`` over the pixel's through samples, 0 where there are none.
+        ``environment``: None (the call is what it was), or a ``drt_amd.render.Environment`` -- a lat-long panorama at infinity with a
+        rotation world -> environment frame: a direct or through sample that the screen does not catch then takes its weighted
+        bilinear sample of the panorama along its exit direction instead of ``void`` (drt_render_image_env; csrc/drt_image_env.h and
+        DESIGN.md 10.8 state the law).  ``screen`` and ``texture`` may then both be None: no screen, every ray sees the environment,
+        and C is the environment's; with a screen the channel counts must agree.  It does not go with ``absorption``.
+        ``want_planes`` then returns a fourth plane, ``reflect``.  ``reflection=True`` (needs an environment and ``fresnel``) adds the
+        light the Fresnel term takes away at the outer surface: a sample whose first interaction enters the object reflects there; where
+        one any-hit query finds the reflected ray unoccluded and the sample's path completes, its colour is
+        ``T B(exit) + R1 B(reflected)`` with ``R1`` the reflectance of that interaction and ``B`` the background of a ray (screen, else
+        environment); ``reflect`` is the share of a pixel's samples with such a term (0 everywhere without ``reflection``)."""
         from . import render as _render
         a = _render.check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid,
-                                      max_samples, want_planes, absorption)
+                                      max_samples, want_planes, absorption, environment, reflection)
         ior = _ior_host(intIOR, "intIOR"), _ior_host(extIOR, "extIOR")
         dev = self._dev
         with _on(dev):
-            tex = torch.as_tensor(a["texture"], device=dev).to(torch.float32).contiguous()
+            tex = None if a["texture"] is None else torch.as_tensor(a["texture"], device=dev).to(torch.float32).contiguous()
             v = _f64c(self.vertices.detach(), "vertices")
             H, W, C = a["height"], a["width"], a["channels"]
             image = torch.empty((H, W, C), dtype=torch.float32, device=dev)
             planes = tuple(torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(2)) if a["want_planes"] else (None, None)
+            if a["environment"] is not None:
+                env = torch.as_tensor(a["environment"].texels, device=dev).to(torch.float32).contiguous()
+                rot = a["environment"].packed()
+                reflect = torch.empty((H, W), dtype=torch.float32, device=dev) if a["want_planes"] else None
+                for y0, y1 in a["bands"]:
+                    _lib.check(_lib.lib().drt_render_image_env(
+                        self.optix_mesh._h, v.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
+                        a["law_flags"], a["fresnel"], None if tex is None else a["screen"].ctypes.data, _lib.ptr(tex), 0 if tex is None else tex.shape[0],
+                        0 if tex is None else tex.shape[1], C, a["void"].ctypes.data, a["invalid"].ctypes.data, image.data_ptr(), _lib.ptr(planes[0]),
+                        _lib.ptr(planes[1]), env.data_ptr(), env.shape[0], env.shape[1], rot.ctypes.data, int(a["reflection"]), _lib.ptr(reflect),
+                        _stream()))
+                return (image,) + planes + (reflect,) if a["want_planes"] else image
             if a["absorption"] is not None:
                 length = torch.empty((H, W), dtype=torch.float32, device=dev) if a["want_planes"] else None
                 for y0, y1 in a["bands"]:
@@ -1274,7 +1328,8 @@ class Scene(StepwiseMixin):
 
     def image_loss_fused(self, camera_M, height, width, screen, texture, target, *, weight=None, ior_int=None, ior_ext=None, vertices=True,
                          want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
-                         invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None, absorption=None):
+                         invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None, absorption=None, environment=None,
+                         reflection=False):
         """The photometric loss of ``render_image`` against a photograph: sum over pixels and channels of ``w (I - target)^2`` with ``I``
         the float64 pixel mean ``render_image`` rounds to float32 -- as a scalar, with its vertex gradient AND d loss / d (ior_int,
         ior_ext) computed alongside with a unit seed and scaled in the backward pass (drt_render_image_loss; csrc/drt_image_loss.h and
@@ -1306,19 +1361,32 @@ class Scene(StepwiseMixin):
         like a tensor IOR); the loss is then that of the absorbing image, the vertex and IOR gradients are the derivative of the whole
         law, the interior lengths included, and a tensor that requires grad receives d loss / d absorption, which costs no path
         recompute and is there on any scene and with ``vertices=False`` (drt_render_image_loss_absorb; csrc/drt_image_absorb.h and
-        DESIGN.md 10.7 state the law).  It goes with none of ``screen_param`` / ``texture_param`` / ``camera_param``."""
+        DESIGN.md 10.7 state the law).  It goes with none of ``screen_param`` / ``texture_param`` / ``camera_param``.
+        ``environment`` / ``reflection``: ``render_image``'s (``screen`` and ``texture`` may then both be None); the loss is that of the
+        image in front of the environment, with the outer-surface reflection when asked for, and the vertex and IOR gradients are the
+        derivative of that whole law: the exit direction through the environment lookup, ``R1`` and the reflected ray through the first
+        face (drt_render_image_loss_env; csrc/drt_image_env.h and DESIGN.md 10.8 state the law).  Every through sample then carries a
+        gradient.  The environment's texels and rotation receive none.  It goes with none of ``absorption`` / ``screen_param`` /
+        ``texture_param`` / ``camera_param``."""
         from . import render as _render
         a = _render.check_image_loss_args(camera_M, height, width, screen, texture, target, weight, ior_int, ior_ext, vertices, want_image, supersample,
                                           max_bounces, tir, refraction, fresnel, void, invalid, max_samples, screen_param, texture_param, camera_param,
-                                          absorption)
+                                          absorption, environment, reflection)
         ior, tracked = _ior_args(intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext)
         dev = self._dev
         with _on(dev):
-            tex = torch.as_tensor(a["texture"], device=dev).to(torch.float32).contiguous()
+            tex = None if a["texture"] is None else torch.as_tensor(a["texture"], device=dev).to(torch.float32).contiguous()
             tgt = torch.as_tensor(a["target"], device=dev)
             tgt = (tgt.to(torch.float32) / 255.0 if tgt.dtype == torch.uint8 else tgt).reshape(a["height"], a["width"], a["channels"]).contiguous()
             wgt = None if a["weight"] is None else torch.as_tensor(a["weight"], device=dev).contiguous()
         inputs = (self.vertices if a["vertices"] else self.vertices.detach(),) + tracked
+        if a["environment"] is not None:
+            with _on(dev):
+                env = torch.as_tensor(a["environment"].texels, device=dev).to(torch.float32).contiguous()
+            term = _image_env_term(self, a, ior, tex, env, tgt, wgt)
+            loss = _UnitSeedTerm.apply(term, *inputs)
+            self.last_image_count = term.count
+            return (loss, term.image) if a["want_image"] else loss
         if a["absorption"] is not None:
             term = _image_absorb_term(self, a, ior, tex, tgt, wgt)
             loss = _UnitSeedTerm.apply(term, *inputs, absorption if isinstance(absorption, torch.Tensor) else None)
@@ -1345,15 +1413,18 @@ class Scene(StepwiseMixin):
         return _render.ImageViews(self, _render.check_image_views_args(cameras, height, width, screens, targets, weights))
 
     def image_loss_views_fused(self, binding, view_ids, texture, *, ior_int=None, ior_ext=None, vertices=True, supersample=1, max_bounces=2,
-                               tir="drop", refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22):
+                               tir="drop", refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, environment=None,
+                               reflection=False):
         """The SUM over ``view_ids`` (1..16 views of ``binding``, repeats allowed) of ``image_loss_fused`` of each view against its target
         (and weight plane) of the binding -- loss, vertex gradient, IOR partials, ``last_image_count`` -- evaluated as ONE forward
         wavefront and ONE adjoint pass instead of one chain of launches per view (drt_render_image_loss_views).  The views
         share ``texture``, the law and band keywords, the fills and the IORs, all as in ``image_loss_fused``; the listed views are stacked
         into an image of ``len(view_ids) * H`` rows, which is evaluated in bands of at most ``max_samples`` samples (a band may straddle
         a view border) into one set of accumulators.  No image output and no screen, texture or camera gradients:
-        ``image_loss_fused`` has those."""
+        ``image_loss_fused`` has those, and it alone takes an ``environment`` or ``reflection``: given here they raise ``ValueError``."""
         from . import render as _render
+        if environment is not None or reflection is not False:
+            raise ValueError("environment / reflection: the multi-view call has no environment form; use image_loss_fused view by view")
         a = _render.check_image_views_law(binding, view_ids, texture, ior_int, ior_ext, vertices, supersample, max_bounces, tir, refraction, fresnel,
                                           void, invalid, max_samples)
         if binding.scene is not self:

@@ -2,7 +2,7 @@
 
     python -m drt_amd.render --name horse [--mesh result.ply] [--capture horse.h5 | --views N] --view-ids 0 9 18 --res H W
                              --supersample 3 --max-bounces 6 --tir reflect --refraction snell [--no-fresnel]
-                             [--background checker|ramp|FILE] -o DIR [--force]
+                             [--background checker|ramp|FILE] [--environment FILE [--env-rotation ...] [--no-screen] [--reflection]] -o DIR [--force]
 
 ``Scene.render_image`` (drt_amd.diffrender) is the entry point; this module holds what goes with it: the screen, procedural
 textures, image files, the band plan and the command line.  The law is stated once, in csrc/drt_image.h (and DESIGN.md section 10.2):
@@ -14,6 +14,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import re
 
 import numpy as np
 
@@ -163,6 +164,120 @@ def load_texture(path):
     return check_texture(a)
 
 
+def _read_hdr(path):
+    """float32 [H, W, 3] of a Radiance ``.hdr`` / ``.pic`` file (RGBE, ``-Y H +X W``; flat or run-length encoded scanlines): a pixel
+    (r, g, b, e) with e > 0 is (r + 0.5, g + 0.5, b + 0.5) * 2^(e - 136), Radiance's own colr_color; e = 0 is black."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if not raw.startswith((b"#?RADIANCE", b"#?RGBE")):
+        raise ValueError(f"{path}: not a Radiance picture (it does not begin with #?RADIANCE)")
+    blank = re.search(rb"\r?\n\r?\n", raw)
+    if blank is None:
+        raise ValueError(f"{path}: the Radiance header does not end")
+    for line in raw[:blank.start()].split(b"\n"):
+        if line.startswith(b"FORMAT=") and line.strip() != b"FORMAT=32-bit_rle_rgbe":
+            raise ValueError(f"{path}: only FORMAT=32-bit_rle_rgbe is read, got {line.strip().decode(errors='replace')}")
+    pos = raw.find(b"\n", blank.end())
+    if pos < 0:
+        raise ValueError(f"{path}: the size line (-Y H +X W) behind the Radiance header is missing or does not end")
+    size = raw[blank.end():pos].split()
+    if len(size) == 4 and (size[0], size[2]) != (b"-Y", b"+X") and size[0][1:] in (b"Y", b"X") and size[2][1:] in (b"Y", b"X"):
+        raise ValueError(f"{path}: only the standard orientation -Y H +X W is read, got {raw[blank.end():pos].decode(errors='replace')!r}")
+    try:
+        if len(size) != 4 or (size[0], size[2]) != (b"-Y", b"+X"):
+            raise ValueError
+        h, w = int(size[1]), int(size[3])
+    except ValueError:
+        raise ValueError(f"{path}: the size line must read -Y H +X W with two integers, got {raw[blank.end():pos].decode(errors='replace')!r}") from None
+    pos += 1
+    data = np.frombuffer(raw, np.uint8, offset=pos)
+    rgbe = np.empty((h, w, 4), np.uint8)
+    if h < 1 or w < 1:
+        raise ValueError(f"{path}: empty picture ({h} x {w})")
+    encoded = 8 <= w <= 32767 and len(data) >= 4 and data[0] == 2 and data[1] == 2 and data[2] < 128
+    if not encoded:
+        if len(data) < h * w * 4:
+            raise ValueError(f"{path}: the file ends before its {h} x {w} pixels do")
+        rgbe[:] = data[:h * w * 4].reshape(h, w, 4)
+    else:
+        p = 0
+        for y in range(h):
+            if p + 4 > len(data) or data[p] != 2 or data[p + 1] != 2 or (int(data[p + 2]) << 8 | int(data[p + 3])) != w:
+                raise ValueError(f"{path}: scanline {y} is not run-length encoded for a width of {w}")
+            p += 4
+            for ch in range(4):
+                x = 0
+                while x < w:
+                    if p >= len(data):
+                        raise ValueError(f"{path}: the file ends inside scanline {y}")
+                    n = int(data[p])
+                    if n > 128:                          # a run: n - 128 copies of the next byte
+                        n -= 128
+                        if n == 0 or x + n > w or p + 1 >= len(data):
+                            raise ValueError(f"{path}: bad run in scanline {y}")
+                        rgbe[y, x:x + n, ch] = data[p + 1]
+                        p += 2
+                    else:                                # n literal bytes
+                        if n == 0 or x + n > w or p + 1 + n > len(data):
+                            raise ValueError(f"{path}: bad literal in scanline {y}")
+                        rgbe[y, x:x + n, ch] = data[p + 1:p + 1 + n]
+                        p += 1 + n
+                    x += n
+    e = rgbe[:, :, 3].astype(np.int32)
+    scale = np.where(e > 0, np.ldexp(1.0, e - 136), 0.0)
+    return ((rgbe[:, :, :3].astype(np.float64) + 0.5) * scale[:, :, None]).astype(np.float32)
+
+
+class Environment:
+    """An environment map at infinity: ``texels`` float32 ``[Eh, Ew, C]`` (or ``[Eh, Ew]``), C in {1, 3}, at least
+    2 x 2, numpy or a device tensor -- a lat-long panorama whose row 0 looks along +y of the environment frame and whose columns run once
+    around it; ``rotation``: 3 x 3, world -> environment frame, y up (None: the identity), orthonormal to 1e-12
+    (max |R R^T - I|).  The values are radiances: they are not clipped to [0, 1]."""
+
+    def __init__(self, texels, rotation=None):
+        t = texels
+        if not (hasattr(t, "shape") and hasattr(t, "dtype")):
+            try:
+                t = np.asarray(t)
+            except (TypeError, ValueError):
+                raise ValueError(f"environment texels must be a float array [Eh, Ew, C], got {type(texels).__name__}") from None
+        if t.ndim == 2:
+            t = t[:, :, None]
+        if t.ndim != 3 or t.shape[2] not in (1, 3):
+            raise ValueError(f"environment texels must be [Eh, Ew], [Eh, Ew, 1] or [Eh, Ew, 3], got shape {tuple(t.shape)}")
+        if t.shape[0] < 2 or t.shape[1] < 2:
+            raise ValueError(f"environment must be at least 2 x 2 texels, got {tuple(t.shape[:2])}")
+        if "float" not in str(t.dtype):
+            raise ValueError(f"environment texels must be a float array (float32 is used), got dtype {t.dtype}")
+        self.texels = np.ascontiguousarray(t, dtype=np.float32) if isinstance(t, np.ndarray) else t
+        R = np.eye(3) if rotation is None else _mat(rotation, (3, 3), "environment rotation")
+        defect = float(np.abs(R @ R.T - np.eye(3)).max())
+        if not defect <= ORTHO_TOL:
+            raise ValueError(f"environment rotation must be orthonormal: max |R R^T - I| = {defect!r} exceeds {ORTHO_TOL}")
+        self.rotation = np.ascontiguousarray(R, dtype=np.float64)
+
+    @property
+    def channels(self):
+        return int(self.texels.shape[2])
+
+    def packed(self):
+        """The nine doubles of the C ABI: the rotation, row-major."""
+        return np.ascontiguousarray(self.rotation.reshape(-1), dtype=np.float64)
+
+    @staticmethod
+    def yaw(degrees):
+        """The rotation that turns the panorama by ``degrees`` about the world's y axis."""
+        a = np.deg2rad(float(degrees))
+        c, s = np.cos(a), np.sin(a)
+        return np.array([[c, 0.0, -s], [0.0, 1.0, 0.0], [s, 0.0, c]])
+
+    @classmethod
+    def load(cls, path, rotation=None):
+        """An environment from a file: Radiance ``.hdr`` / ``.pic`` (read here with numpy), or whatever ``load_texture`` reads."""
+        ext = os.path.splitext(path)[1].lower()
+        return cls(_read_hdr(path) if ext in (".hdr", ".pic") else load_texture(path), rotation)
+
+
 def to_bytes(image):
     """uint8 [H, W, C] of a float image: clipped to [0, 1], scaled by 255, rounded to nearest."""
     a = _host(image)
@@ -267,10 +382,12 @@ def check_absorption(absorption, channels):
 
 
 def check_render_args(camera_M, height, width, screen, texture, supersample=1, max_bounces=2, tir="drop", refraction="reference",
-                      fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False, absorption=None):
+                      fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, want_planes=False, absorption=None, environment=None, reflection=False):
     """Every argument check of ``Scene.render_image``, none of which needs a device.  Returns a dict: camera (21 doubles: K^-1, then the
-    top 3 x 4 of R^-1), screen (9 doubles), texture, void / invalid (C doubles), bands, law_flags, the scalars and absorption (C doubles,
-    or None: clear glass)."""
+    top 3 x 4 of R^-1), screen (9 doubles), texture, void / invalid (C doubles), bands, law_flags, the scalars, absorption (C doubles,
+    or None: clear glass) and environment (an ``Environment``, or None).  With an environment ``screen`` and ``texture`` may both be
+    None (screen and texture are then None in the dict, and C is the environment's); absorption does not go with one.  ``reflection``
+    (the outer-surface reflection) needs an environment and ``fresnel=True``."""
     try:
         n_cam = len(camera_M)
     except TypeError:
@@ -289,12 +406,30 @@ def check_render_args(camera_M, height, width, screen, texture, supersample=1, m
         raise ValueError(f"fresnel must be True or False, got {fresnel!r}")
     if not isinstance(want_planes, (bool, np.bool_)):
         raise ValueError(f"want_planes must be True or False, got {want_planes!r}")
-    if not isinstance(screen, Screen):
-        raise ValueError(f"screen must be a drt_amd.render.Screen, got {type(screen).__name__}")
-    tex = check_texture(texture)
-    channels = int(tex.shape[2])
+    if not isinstance(reflection, (bool, np.bool_)):
+        raise ValueError(f"reflection must be True or False, got {reflection!r}")
+    if reflection and environment is None:
+        raise ValueError("reflection=True needs an environment: the reflected rays almost never meet a screen behind the object")
+    if reflection and not fresnel:
+        raise ValueError("reflection=True needs fresnel=True: the reflected share is the complement of what the Fresnel term transmits")
+    if environment is not None:
+        if not isinstance(environment, Environment):
+            raise ValueError(f"environment must be a drt_amd.render.Environment, got {type(environment).__name__}")
+        if absorption is not None:
+            raise ValueError("environment cannot be combined with absorption: the absorbing image has no environment form")
+        if (screen is None) != (texture is None):
+            raise ValueError("environment: screen and texture must be given together or both be None (no screen: every ray sees the environment)")
+    if environment is not None and screen is None:
+        tex, channels = None, environment.channels
+    else:
+        if not isinstance(screen, Screen):
+            raise ValueError(f"screen must be a drt_amd.render.Screen, got {type(screen).__name__}")
+        tex = check_texture(texture)
+        channels = int(tex.shape[2])
+        if environment is not None and environment.channels != channels:
+            raise ValueError(f"environment has {environment.channels} channels, the texture has {channels}: they must agree")
     return dict(camera=np.ascontiguousarray(np.concatenate([kinv.reshape(-1), rinv[:3, :].reshape(-1)]), dtype=np.float64),
-                screen=screen.packed(), texture=tex, channels=channels, void=_fill(void, channels, "void"),
+                screen=None if tex is None else screen.packed(), texture=tex, environment=environment, reflection=bool(reflection), channels=channels, void=_fill(void, channels, "void"),
                 invalid=_fill(invalid, channels, "invalid"), bands=bands, height=int(height), width=int(width), supersample=int(supersample),
                 max_bounces=int(max_bounces), law_flags=int(tir == "reflect") | (2 if refraction == "snell" else 0), fresnel=int(bool(fresnel)),
                 want_planes=bool(want_planes), absorption=check_absorption(absorption, channels))
@@ -409,12 +544,24 @@ def camera_of_param(camera_param):
 
 def check_image_loss_args(camera_M, height, width, screen, texture, target, weight=None, ior_int=None, ior_ext=None, vertices=True,
                           want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
-                          invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None, absorption=None):
+                          invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None, absorption=None, environment=None,
+                          reflection=False):
     """Every argument check of ``Scene.image_loss_fused``, none of which needs a device: ``check_render_args``' dict plus target
     (float32 [H, W, C]; uint8 is read as value / 255; [H, W] with a one-channel texture), weight (float32 [H, W] or None), ior (the float
     of each IOR given as a number, else None), vertices and want_image.  ``screen_param`` / ``texture_param`` (tensors a gradient is
     wanted for) take the place of ``screen`` / ``texture``, which must then be None: exactly one form of each is given; so does
-    ``camera_param`` = ``(Rinv, Kinv)`` for ``camera_M``.  ``absorption`` (``check_absorption``) goes with none of the three."""
+    ``camera_param`` = ``(Rinv, Kinv)`` for ``camera_M``.  ``absorption`` (``check_absorption``) goes with none of the three.  ``environment`` / ``reflection``
+    (``check_render_args``): with an environment ``screen`` and ``texture`` may both be None; it goes with none of
+    ``absorption``, ``screen_param``, ``texture_param``, ``camera_param``."""
+    if environment is not None or reflection is not False:
+        for name, given in (("absorption", absorption), ("screen_param", screen_param), ("texture_param", texture_param), ("camera_param", camera_param)):
+            if given is not None:
+                raise ValueError(f"environment / reflection cannot be combined with {name}: the loss over an environment has vertex and IOR gradients only")
+        if camera_M is None:
+            raise ValueError("camera_M is None and no camera_param is given: one of the two must supply the camera")
+        a = check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples,
+                              environment=environment, reflection=reflection)
+        return _loss_planes(a, target, weight, ior_int, ior_ext, vertices, want_image)
     if absorption is not None:
         for name, given in (("screen_param", screen_param), ("texture_param", texture_param), ("camera_param", camera_param)):
             if given is not None:
@@ -439,6 +586,11 @@ def check_image_loss_args(camera_M, height, width, screen, texture, target, weig
         raise ValueError("texture is None and no texture_param is given: one of the two must supply the texture")
     a = check_render_args(camera_M, height, width, screen, texture, supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples,
                           absorption=absorption)
+    return _loss_planes(a, target, weight, ior_int, ior_ext, vertices, want_image)
+
+
+def _loss_planes(a, target, weight, ior_int, ior_ext, vertices, want_image):
+    """``check_image_loss_args`` behind ``check_render_args``: target, weight, ior, vertices and want_image into the dict ``a``."""
     H, W, C = a["height"], a["width"], a["channels"]
     if target is not None and hasattr(target, "shape") and len(target.shape) == 2 and C == 1:
         target = target[:, :, None]
@@ -632,12 +784,35 @@ def main(argv=None):
     ap.add_argument("--background", default="checker", help="checker, ramp, or a texture file (.npy, .ppm, .pgm, or what PIL reads)")
     ap.add_argument("--texture-size", type=int, default=1024, help="texels per side of a procedural background")
     ap.add_argument("--span", type=float, default=2.0, help="side of the screen in units of the object's extent")
+    ap.add_argument("--environment", default=None, metavar="FILE",
+                    help="a lat-long panorama seen where the screen is not: Radiance .hdr, .npy, .ppm, .pgm, or what PIL reads")
+    ap.add_argument("--env-rotation", nargs="+", default=None, metavar="R",
+                    help="world -> environment frame, y up: nine numbers (row-major), or `yaw DEG`")
+    ap.add_argument("--no-screen", action="store_true", help="render without a screen: every ray sees the environment")
+    ap.add_argument("--reflection", action="store_true", help="add the light reflected off the outer surface (needs --environment and the Fresnel term)")
     ap.add_argument("--invalid", type=float, nargs="+", default=[0.0], help="colour of samples whose path does not complete")
     ap.add_argument("--void", type=float, nargs="+", default=[0.0], help="colour of samples that miss the screen")
     ap.add_argument("-o", "--output", required=True, help="directory the images are written to")
     ap.add_argument("--format", default="png", help="png (needs PIL; netpbm is written without it), ppm / pgm")
     ap.add_argument("--force", action="store_true", help="overwrite existing images")
     a = ap.parse_args(argv)
+    if (a.env_rotation is not None or a.no_screen or a.reflection) and a.environment is None:
+        raise SystemExit("--env-rotation, --no-screen and --reflection need --environment")
+    if a.reflection and a.no_fresnel:
+        raise SystemExit("--reflection cannot be combined with --no-fresnel")
+    if a.environment is not None and a.absorption is not None:
+        raise SystemExit("--environment cannot be combined with --absorption")
+    rotation = None
+    if a.env_rotation is not None:
+        try:
+            if a.env_rotation[0] == "yaw" and len(a.env_rotation) == 2:
+                rotation = Environment.yaw(float(a.env_rotation[1]))
+            elif len(a.env_rotation) == 9:
+                rotation = np.array([float(x) for x in a.env_rotation]).reshape(3, 3)
+            else:
+                raise ValueError
+        except ValueError:
+            raise SystemExit(f"--env-rotation takes nine numbers or `yaw DEG`, got {' '.join(a.env_rotation)!r}") from None
     stem = os.path.join(a.output, a.name + "_view{:03d}")
     for k in a.view_ids:
         for ext in {a.format, "ppm", "pgm"}:
@@ -654,13 +829,14 @@ def main(argv=None):
         height, width = a.res
         turntable = views.turntable_cameras(center, extent, a.views, width, height)
         cams = {k: turntable[k] for k in a.view_ids}
-    texture = _background(a.background, a.texture_size)
+    texture = None if a.no_screen else _background(a.background, a.texture_size)
+    more = {} if a.environment is None else {"environment": Environment.load(a.environment, rotation), "reflection": a.reflection}      # (without it: the call of before)
     report = {"name": a.name, "height": height, "width": width, "views": []}
     for k in a.view_ids:
-        screen = Screen.behind(cams[k], center, extent, texture.shape[1], texture.shape[0], span=a.span)
+        screen = None if a.no_screen else Screen.behind(cams[k], center, extent, texture.shape[1], texture.shape[0], span=a.span)
         image, hit, through = scene.render_image(cams[k], height, width, screen, texture, supersample=a.supersample, max_bounces=a.max_bounces,
                                                  tir=a.tir, refraction=a.refraction, fresnel=not a.no_fresnel, void=a.void, invalid=a.invalid,
-                                                 want_planes=True, absorption=a.absorption)[:3]
+                                                 want_planes=True, absorption=a.absorption, **more)[:3]
         path = write_image(stem.format(k) + "." + a.format, image, force=a.force)
         report["views"].append({"view": k, "image": path, "hit_share": float(hit.mean()), "through_share": float(through.mean())})
     print(json.dumps(report))

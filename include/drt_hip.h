@@ -776,6 +776,49 @@ int drt_render_image_loss_absorb(drt_scene_t* s, const double* d_verts, const do
                                  const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
                                  int64_t* d_count, const double* sigma, double* d_grad_sigma, void* stream);
 
+/* ---- an environment map behind, or instead of, the screen (csrc/drt_image_env.h states the law) ------------------
+ * drt_render_image with a lat-long panorama at infinity: d_env float32 [env_h, env_w, channels] (device; env_h, env_w >= 2; row 0 looks
+ * along +y of the environment frame), env_rot9 (HOST, nine doubles) the row-major rotation world -> environment frame, y up, with
+ * max |R R^T - I| <= 1e-12.  A direct or through sample with exit ray (o, d) takes T * texture where the screen catches it, as in
+ * drt_render_image; every other such sample takes T * E(d) instead of fill_void:
+ *   e_r = (R[r][0] d.x + R[r][1] d.y) + R[r][2] d.z,  theta = acos(clamp(e_y, -1, 1)),  phi = atan2(e_x, -e_z),
+ *   u = ((phi / (2 pi)) + 0.5) env_w - 0.5,  v = (theta / pi) env_h - 0.5, v clamped to [0, env_h - 1], y0 = min(floor(v), env_h - 2),
+ *   x0 = floor(u) in -1 .. env_w - 1 with the columns (x0 + env_w) mod env_w and (x0 + 1) mod env_w, and the bilinear formula above.
+ * An invalid sample keeps fill_invalid; fill_void is checked and never used.  screen9 and d_texture may BOTH be NULL: no screen, every
+ * ray sees the environment (tex_h, tex_w are then ignored; `channels` is the environment's).  d_hit / d_through are drt_render_image's.
+ * reflection = 1 (needs fresnel = 1) adds the light that R takes away at the OUTER surface: a sample whose first interaction enters the
+ * object (sg > 0, no TIR flag) has the reflected ray (ro, wr) of that interaction (wr = d + 2 ci n, ro = hit point + 1e-5 wr: the mirrored
+ * interactions' own formula) and R1 = R of that interaction, the value whose complement entered T.  One any-hit query of the float32 cast
+ * of (ro, wr) runs under the tracer contract; where it finds nothing and the sample is THROUGH, colour = T B(exit) + R1 B(ro, wr), B the
+ * background of a ray as above (screen, else environment).  Classes, T, the path and the fills are unchanged.  An occluded reflection,
+ * the reflection of an invalid sample and reflections off inner surfaces contribute nothing (stated losses).  d_reflect (float32
+ * [height, width], may be NULL): rows [y0, y1) receive the share of a pixel's samples whose reflection was added (0 with reflection = 0).
+ * Workspace: drt_render_image's; the reflection keeps the face tape of drt_render_image_loss (its row 0 is the first face) and one bit of
+ * the state byte, nothing more.  DRT_E_INVALID (nothing enqueued, no output touched): a screen without a texture or the reverse, everything
+ * drt_render_image refuses, then a NULL d_env, an environment side below 2, a NULL or non-orthonormal env_rot9, a reflection
+ * outside {0, 1}, reflection without fresnel -- the message names the argument.  drt_version stays 13: probe for the symbol. */
+int drt_render_image_env(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                         double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                         const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                         float* d_image, float* d_hit, float* d_through, const float* d_env, int env_h, int env_w, const double* env_rot9,
+                         int reflection, float* d_reflect, void* stream);
+
+/* ---- ... and its photometric loss --------------------------------------------------------------------------------
+ * drt_render_image_loss with drt_render_image_env's background: the loss of drt_render_image_loss on the image of drt_render_image_env
+ * (environment, optional screen, optional reflection), and the derivative of the WHOLE law w.r.t. the vertices and the two IORs.  Every
+ * THROUGH sample carries a gradient (*d_count += all of them): where its exit ray lands on the screen as in drt_render_image_loss; where
+ * it goes to the environment the exit ray's seed is g_o = 0 and g_d through the lookup (atan2, acos, the bilinear gradient in u, v).
+ * With reflection = 1 a sample whose reflection was added also hands the seeds of (ro, wr) through the reflection's adjoint and the seed
+ * of R1 through FrDielectric's adjoint and ci into the three vertices of its first face and both IORs.  The occlusion verdict, classes,
+ * faces, the texel cell, the wrap column and the clamp of v carry no gradient; neither do the environment's texels or rotation.  Both
+ * accumulation modes (float64 atomics, FxCell under drt_deterministic).  Workspace: drt_render_image_loss's.  DRT_E_INVALID as
+ * drt_render_image_loss and drt_render_image_env. */
+int drt_render_image_loss_env(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                              double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                              const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                              const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                              int64_t* d_count, const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection, void* stream);
+
 /* ---- the image term of several views in one call (csrc/drt_image_views.h states the mapping) -----------------------
  * A view table holds the cameras and screens of a capture whose views all have height x width pixels: cameras21 [n_views, 21] and
  * screens9 [n_views, 9], host arrays in drt_render_image's layouts.  drt_image_views_create checks every screen as drt_render_image
