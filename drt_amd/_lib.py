@@ -94,6 +94,8 @@ SIGNATURES = {
                                         _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P]),
     "drt_render_image_loss_env": (_c.c_int, [_P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _D, _D, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_int,
                                              _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P]),
+    "drt_render_image_loss_env_param": (_c.c_int, [_P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _D, _D, _c.c_int, _c.c_int, _c.c_int, _P, _P,
+                                                   _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P, _P]),
     "drt_image_views_check": (_c.c_int, [_c.c_int, _P, _P, _c.c_int, _c.c_int]),
     "drt_image_views_create": (_c.c_int, [_P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.POINTER(_P)]),
     "drt_image_views_destroy": (None, [_P]),

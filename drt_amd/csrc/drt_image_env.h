@@ -119,8 +119,9 @@ DRT_HD double image_env_lookup(const ImageEnv& e, d3 d, int ch) {
 //   u = ((phi / 2pi) + 0.5) Ew - 0.5 ; phi = atan2(a, b), a = e_x, b = -e_z : d phi = (b da - a db) / (a^2 + b^2)
 //   v = (theta / pi) Eh - 0.5 ; theta = acos(cy) : d theta = -d cy / sqrt(1 - cy^2), cy = clamp(e_y, -1, 1)
 // At a pole (a = b = 0, or |cy| = 1) the quotients are those torch forms: inf or NaN; the tests keep such samples out (pole cut).
-DRT_HD void image_env_uv_backward(const ImageEnv& e, d3 d, double g_u, double g_v, d3& g_d) {
-    const d3 q = image_env_dir(e, d);
+// image_env_uv_seed: the seed g_e of the direction q in the ENVIRONMENT frame, which the rotation's own gradient starts from as well
+// (drt_image_env_param.h: g_R[r][c] = g_e[r] d[c]); image_env_uv_backward multiplies it by R^T.
+DRT_HD d3 image_env_uv_seed(const ImageEnv& e, d3 q, double g_u, double g_v) {
     const double cy = q.y < -1.0 ? -1.0 : (q.y > 1.0 ? 1.0 : q.y);
     const double g_phi = (g_u * (double)e.ew) / (2.0 * kImageEnvPi);
     const double g_theta = (g_v * (double)e.eh) / kImageEnvPi;
@@ -129,7 +130,10 @@ DRT_HD void image_env_uv_backward(const ImageEnv& e, d3 d, double g_u, double g_
     const double g_a = g_phi * (b / r2), g_b = g_phi * (-a / r2);
     const double g_cy = -g_theta / sqrt(1.0 - cy * cy);
     const double g_qy = (q.y >= -1.0 && q.y <= 1.0) ? g_cy : 0.0;
-    const d3 g_q{g_a, g_qy, -g_b};
+    return d3{g_a, g_qy, -g_b};
+}
+DRT_HD void image_env_uv_backward(const ImageEnv& e, d3 d, double g_u, double g_v, d3& g_d) {
+    const d3 g_q = image_env_uv_seed(e, image_env_dir(e, d), g_u, g_v);
     const double* R = e.rot;
     g_d = d3{(R[0] * g_q.x + R[3] * g_q.y) + R[6] * g_q.z, (R[1] * g_q.x + R[4] * g_q.y) + R[7] * g_q.z, (R[2] * g_q.x + R[5] * g_q.y) + R[8] * g_q.z};
 }

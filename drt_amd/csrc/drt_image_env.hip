@@ -29,6 +29,8 @@
 //                                       forms its camera ray again and runs image_reflect_backward: one triangle, one Bounce; vertex gradients
 //                                       through PathSink, the IOR partials through two LossAcc.  A kernel of its own: k_image_loss_bwd sits at
 //                                       197 to 256 VGPRs
+//   k_image_env_param_bwd all pixels  : drt_render_image_loss_env_param with an accumulator for the environment's texels or rotation
+//                                       (DESIGN.md 10.9): drt_image_env_param.hip's, last on the stream
 // No workspace of its own: the first face is the tape's row 0 (4 B per sample, already there for the loss) and the bit sits in the state
 // byte.  The list's order is never read, so two runs give the same bits.
 // Everything runs on the caller's stream, nothing is read back, every list size stays on the device.
@@ -140,8 +142,11 @@ void reflection_pass(drt_scene* s, const PathCtx& pc, const ImageCall& c, hipStr
 // The host body of the loss call behind its checks, image_loss_run's steps under a background: workspace, forward (tape kept), reflection
 // pass, loss resolve, and -- on a scene with triangles, when a gradient or the count is wanted -- the list of through samples, the adjoint
 // and the reflection's adjoint.
-int env_loss_run(drt_scene* s, const double* d_verts, const ImageCall& c, const ImageScreenEnv& bg, bool reflection, const ImageLossOut& out, hipStream_t st,
-                 const char* who) {
+// grad_env / grad_env_rot (drt_render_image_loss_env_param; either may be null): the pass of drt_image_env_param.hip over the pixels of the
+// band comes last.  Between the resolve and it only w.idx[0] and the counter kCntValid are written (the through list): the state bytes,
+// the parked rows, the throughputs and the tape are what the resolve read.
+int env_loss_run(drt_scene* s, const double* d_verts, const ImageCall& c, const ImageScreenEnv& bg, bool reflection, const ImageLossOut& out, double* grad_env,
+                 double* grad_env_rot, hipStream_t st, const char* who) {
     { int rc = ensure_image_loss_ws(s, c.n_pix * c.tx.c, 0, st, who); if (rc) return rc; }
     { int rc = image_forward(s, d_verts, c, true, st, who); if (rc) return rc; }
     const PathCtx pc = image_path_ctx(s, d_verts, c);
@@ -174,11 +179,36 @@ int env_loss_run(drt_scene* s, const double* d_verts, const ImageCall& c, const 
                 pc, view, c.band, c.tx, bg, w.tape, w.state, done, w.cnt + kCntValid, lw.g_c, out.grad_verts, out.grad_ior);
     }
     HIP_TRY(hipGetLastError());
+    if (grad_env || grad_env_rot) return launch_image_env_param_bwd(s, pc, c, bg, reflection, lw.g_c, grad_env, grad_env_rot, st);
     return DRT_OK;
 }
 
 // a screen that stands for none: never evaluated (ImageScreenEnv::screen is false), it only has to pass image_call_check
 const double kNoScreen[9] = {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+
+// The one host body of drt_render_image_loss_env and drt_render_image_loss_env_param (`who`); the former hands two null pointers.
+int env_loss_call(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample, double ior_int,
+                  double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9, const float* d_texture, int tex_h, int tex_w, int channels,
+                  const double* fill_void, const double* fill_invalid, const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts,
+                  double* d_grad_ior, float* d_image, int64_t* d_count, const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection,
+                  double* d_grad_env, double* d_grad_env_rot, void* stream, const char* who) {
+    CHECK_BUILT(s);
+    if ((screen9 == nullptr) != (d_texture == nullptr))
+        return fail(DRT_E_INVALID, "screen9 and d_texture must be given together or both be NULL (no screen: every ray sees the environment)");
+    if (!d_env) return fail(DRT_E_INVALID, "null device pointer argument (d_env)");
+    const bool has_screen = screen9 != nullptr;
+    ImageCall c;
+    { int rc = image_call_check(camera21, height, width, y0, y1, supersample, ior_int, ior_ext, max_bounces, law_flags, fresnel, has_screen ? screen9 : kNoScreen,
+                                has_screen ? d_texture : d_env, has_screen ? tex_h : 2, has_screen ? tex_w : 2, channels, fill_void, fill_invalid,
+                                d_target && d_loss && (s->n_faces == 0 || d_verts), "null device pointer argument (d_verts, d_target, d_loss)", c); if (rc) return rc; }
+    ImageScreenEnv bg{};
+    { int rc = env_args_check(d_env, env_h, env_w, env_rot9, reflection, fresnel, channels, has_screen, bg); if (rc) return rc; }
+    if (d_grad_env && (int64_t)env_h * env_w > INT32_MAX)
+        return fail(DRT_E_INVALID, "env_h x env_w = %d x %d: an environment texel gradient (d_grad_env) takes at most 2^31 - 1 texels", env_h, env_w);
+    hipStream_t st = (hipStream_t)stream;
+    const ImageLossOut out{d_target, d_weight, d_loss, d_grad_verts, d_grad_ior, d_image, d_count, nullptr};
+    return env_loss_run(s, d_verts, c, bg, reflection != 0, out, d_grad_env, d_grad_env_rot, st, who);
+}
 
 }  // namespace
 
@@ -228,21 +258,20 @@ int drt_render_image_loss_env(drt_scene_t* s, const double* d_verts, const doubl
                               const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
                               const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
                               int64_t* d_count, const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection, void* stream) {
-    const char* const who = "drt_render_image_loss_env";
-    CHECK_BUILT(s);
-    if ((screen9 == nullptr) != (d_texture == nullptr))
-        return fail(DRT_E_INVALID, "screen9 and d_texture must be given together or both be NULL (no screen: every ray sees the environment)");
-    if (!d_env) return fail(DRT_E_INVALID, "null device pointer argument (d_env)");
-    const bool has_screen = screen9 != nullptr;
-    ImageCall c;
-    { int rc = image_call_check(camera21, height, width, y0, y1, supersample, ior_int, ior_ext, max_bounces, law_flags, fresnel, has_screen ? screen9 : kNoScreen,
-                                has_screen ? d_texture : d_env, has_screen ? tex_h : 2, has_screen ? tex_w : 2, channels, fill_void, fill_invalid,
-                                d_target && d_loss && (s->n_faces == 0 || d_verts), "null device pointer argument (d_verts, d_target, d_loss)", c); if (rc) return rc; }
-    ImageScreenEnv bg{};
-    { int rc = env_args_check(d_env, env_h, env_w, env_rot9, reflection, fresnel, channels, has_screen, bg); if (rc) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    const ImageLossOut out{d_target, d_weight, d_loss, d_grad_verts, d_grad_ior, d_image, d_count, nullptr};
-    return env_loss_run(s, d_verts, c, bg, reflection != 0, out, st, who);
+    return env_loss_call(s, d_verts, camera21, height, width, y0, y1, supersample, ior_int, ior_ext, max_bounces, law_flags, fresnel, screen9, d_texture, tex_h, tex_w,
+                         channels, fill_void, fill_invalid, d_target, d_weight, d_loss, d_grad_verts, d_grad_ior, d_image, d_count, d_env, env_h, env_w, env_rot9,
+                         reflection, nullptr, nullptr, stream, "drt_render_image_loss_env");
+}
+
+int drt_render_image_loss_env_param(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                                    double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                                    const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                                    const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                                    int64_t* d_count, const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection, double* d_grad_env,
+                                    double* d_grad_env_rot, void* stream) {
+    return env_loss_call(s, d_verts, camera21, height, width, y0, y1, supersample, ior_int, ior_ext, max_bounces, law_flags, fresnel, screen9, d_texture, tex_h, tex_w,
+                         channels, fill_void, fill_invalid, d_target, d_weight, d_loss, d_grad_verts, d_grad_ior, d_image, d_count, d_env, env_h, env_w, env_rot9,
+                         reflection, d_grad_env, d_grad_env_rot, stream, "drt_render_image_loss_env_param");
 }
 
 }  // extern "C"

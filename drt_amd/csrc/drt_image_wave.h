@@ -1,5 +1,5 @@
 // drt_image_wave.h -- what the calls on the refracted image share (drt_image.hip, drt_image_loss.hip, drt_image_screen.hip,
-// drt_image_camera.hip, drt_image_views.hip, drt_image_absorb.hip, drt_image_env.hip): the band of rows of one call, the checked call, the two policies a
+// drt_image_camera.hip, drt_image_views.hip, drt_image_absorb.hip, drt_image_env.hip, drt_image_env_param.hip): the band of rows of one call, the checked call, the two policies a
 // kernel of the family is stated over, and the forward half of the family, each kernel once as a template -- k_image_start<VIEW>,
 // k_image_shade<SNELL, FRESNEL, TAPE, PAYLOAD>, image_pixel_walk<PAYLOAD, BACKGROUND>, k_image_resolve<PAYLOAD, BACKGROUND> -- with the forward
 // wavefront that launches them (defined in drt_image.hip, as launch_trace_list is in drt_trace.hip).  drt_image_loss_bwd.h holds the loss half.
@@ -178,6 +178,13 @@ constexpr int kImageLossBpc = 4;           // blocks per CU of the adjoint witho
 // of the loss, whose pixel seeds g_c [n_pix, C] it reads.  d_grad_screen (nine accumulators: p0, eu, ev) and d_grad_texture
 // ([tex_h, tex_w, C] accumulators, padded to a multiple of three values) are accumulated into; one of them may be null.
 int launch_image_screen_bwd(const drt_scene* s, const ImageCall& call, const double* g_c, double* d_grad_screen, double* d_grad_texture, hipStream_t st);
+
+// Defined in drt_image_env_param.hip: k_image_env_param_bwd on `st` over the pixels of the band, behind image_forward with
+// the tape kept, the reflection pass (with `reflection`) and the resolve kernel of the environment loss, whose pixel seeds g_c it reads
+// with the state bytes, the parked rows and the tape's row 0 as that kernel read them.  d_grad_env ([env_h, env_w, C] accumulators, padded
+// to a multiple of three values) and d_grad_env_rot (nine accumulators, row-major) are accumulated into; one of them may be null.
+int launch_image_env_param_bwd(const drt_scene* s, const PathCtx& pc, const ImageCall& call, const ImageScreenEnv& bg, bool reflection, const double* g_c,
+                               double* d_grad_env, double* d_grad_env_rot, hipStream_t st);
 
 // What a loss call hands out: the planes it compares against and the accumulators it adds into.  Only target and loss must be there.
 struct ImageLossOut {

@@ -861,20 +861,28 @@ def enqueue_image_absorb_term(scene, vertices, a, ior, texture, target, weight, 
     return [vertices, texture, target, weight]
 
 
-def enqueue_image_env_term(scene, vertices, a, ior, texture, env, target, weight, loss_ptr, grad_ptr=None, grad_ior_ptr=None, image_ptr=None, count_ptr=None):
+def enqueue_image_env_term(scene, vertices, a, ior, texture, env, target, weight, loss_ptr, grad_ptr=None, grad_ior_ptr=None, image_ptr=None, count_ptr=None,
+                           env_ptr=None, env_rot_ptr=None, param=False):
     """``enqueue_image_term`` in front of an environment: ONE view's photometric image term under ``a["environment"]`` and
     ``a["reflection"]``, band after band into one set of accumulators, on the current stream; the one place that packs the arguments of
-    drt_render_image_loss_env.  ``texture``: a contiguous float32 device tensor, or None with ``a["screen"]`` None (no screen); ``env``:
-    the environment's texels as a contiguous float32 device tensor.  Every ``*_ptr`` but the first may be None.  The caller is inside
-    ``_on(device)``.  Returns what the enqueued kernels read, for the caller to keep alive."""
-    fn, H, W, C = _lib.lib().drt_render_image_loss_env, a["height"], a["width"], a["channels"]
+    drt_render_image_loss_env and drt_render_image_loss_env_param.  ``texture``: a contiguous float32 device tensor, or None with
+    ``a["screen"]`` None (no screen); ``env``: the environment's texels as a contiguous float32 device tensor.  ``env_ptr`` /
+    ``env_rot_ptr``: the accumulators of the environment's texels (padded to a multiple of three values) and of its nine
+    rotation entries; given, or with ``param``, the call goes to drt_render_image_loss_env_param, else to drt_render_image_loss_env with
+    the arguments of before.  Every ``*_ptr`` but the first may be None.  The caller is inside ``_on(device)``.  Returns what the enqueued
+    kernels read, for the caller to keep alive."""
+    H, W, C = a["height"], a["width"], a["channels"]
+    if param or env_ptr is not None or env_rot_ptr is not None:
+        fn, extra = _lib.lib().drt_render_image_loss_env_param, (env_ptr, env_rot_ptr)
+    else:
+        fn, extra = _lib.lib().drt_render_image_loss_env, ()
     rot = a["environment"].packed()
     for y0, y1 in a["bands"]:
         _lib.check(fn(
             scene.optix_mesh._h, vertices.data_ptr(), a["camera"].ctypes.data, H, W, y0, y1, a["supersample"], ior[0], ior[1], a["max_bounces"],
             a["law_flags"], a["fresnel"], None if texture is None else a["screen"].ctypes.data, _lib.ptr(texture), 0 if texture is None else texture.shape[0],
             0 if texture is None else texture.shape[1], C, a["void"].ctypes.data, a["invalid"].ctypes.data, target.data_ptr(), _lib.ptr(weight), loss_ptr,
-            grad_ptr, grad_ior_ptr, image_ptr, count_ptr, env.data_ptr(), env.shape[0], env.shape[1], rot.ctypes.data, int(a["reflection"]), _stream()))
+            grad_ptr, grad_ior_ptr, image_ptr, count_ptr, env.data_ptr(), env.shape[0], env.shape[1], rot.ctypes.data, int(a["reflection"]), *extra, _stream()))
     return [vertices, texture, env, target, weight]
 
 
@@ -1021,19 +1029,27 @@ def _image_term(scene, a, ior, tex, target, weight, entry="plain"):
     return _Term(dev, accs, enqueue, feeds, count, image)
 
 
-def _image_env_term(scene, a, ior, tex, env, target, weight):
+def _image_env_term(scene, a, ior, tex, env, target, weight, param=False):
     """The term of image_loss_fused in front of an environment (``enqueue_image_env_term``) for the inputs (vertices,
-    ior_int, ior_ext): the vertex accumulator follows ``a["vertices"]``, the IOR pair is always there."""
+    ior_int, ior_ext): the vertex accumulator follows ``a["vertices"]``, the IOR pair is always there.  ``param``: the
+    inputs go on with (env_texels_param, env_rotation_param), and the call reaches drt_render_image_loss_env_param; the environment's
+    texel accumulator (scattered in threes: padded to a multiple of three, sliced back) and the nine of its rotation are there only when
+    such an input needs a gradient."""
     v = _f64c(scene.vertices.detach(), "vertices")
-    dev = v.device
+    dev, n_env = v.device, env.numel()
+    accs, feeds = _verts_ior_accs(v, a["vertices"]), ((_VERTS, None),) + _IOR_FEEDS
+    if param:
+        like = lambda n: torch.empty(n, dtype=torch.float64, device=dev)      # noqa: E731
+        accs["env"], accs["env_rot"] = (like((n_env + 2) // 3 * 3), (3,)), (like(9), (4,))
+        feeds += (("env", lambda s, shape: s[:n_env]), ("env_rot", None))
     count = torch.zeros((), dtype=torch.int64, device=dev)
     image = torch.empty((a["height"], a["width"], a["channels"]), dtype=torch.float32, device=dev) if a["want_image"] else None
 
     def enqueue(loss, cells):
         with _on(dev):
             enqueue_image_env_term(scene, v, a, ior, tex, env, target, weight, loss.data_ptr(), _lib.ptr(cells.get(_VERTS)), _lib.ptr(cells.get("ior")),
-                                   _lib.ptr(image), count.data_ptr())
-    return _Term(dev, _verts_ior_accs(v, a["vertices"]), enqueue, ((_VERTS, None),) + _IOR_FEEDS, count, image)
+                                   _lib.ptr(image), count.data_ptr(), _lib.ptr(cells.get("env")), _lib.ptr(cells.get("env_rot")), param)
+    return _Term(dev, accs, enqueue, feeds, count, image)
 
 
 def _image_absorb_term(scene, a, ior, tex, target, weight):
@@ -1329,7 +1345,7 @@ class Scene(StepwiseMixin):
     def image_loss_fused(self, camera_M, height, width, screen, texture, target, *, weight=None, ior_int=None, ior_ext=None, vertices=True,
                          want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
                          invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None, absorption=None, environment=None,
-                         reflection=False):
+                         reflection=False, env_texels_param=None, env_rotation_param=None):
         """The photometric loss of ``render_image`` against a photograph: sum over pixels and channels of ``w (I - target)^2`` with ``I``
         the float64 pixel mean ``render_image`` rounds to float32 -- as a scalar, with its vertex gradient AND d loss / d (ior_int,
         ior_ext) computed alongside with a unit seed and scaled in the backward pass (drt_render_image_loss; csrc/drt_image_loss.h and
@@ -1366,12 +1382,19 @@ class Scene(StepwiseMixin):
         image in front of the environment, with the outer-surface reflection when asked for, and the vertex and IOR gradients are the
         derivative of that whole law: the exit direction through the environment lookup, ``R1`` and the reflected ray through the first
         face (drt_render_image_loss_env; csrc/drt_image_env.h and DESIGN.md 10.8 state the law).  Every through sample then carries a
-        gradient.  The environment's texels and rotation receive none.  It goes with none of ``absorption`` / ``screen_param`` /
-        ``texture_param`` / ``camera_param``."""
+        gradient.  It goes with none of ``absorption`` / ``screen_param`` / ``texture_param`` / ``camera_param``.
+        ``env_texels_param`` / ``env_rotation_param`` (both need ``environment``, which stays a ``render.Environment``): a float32 or
+        float64 tensor shaped like the environment's texels (``[Eh, Ew, C]``, or ``[Eh, Ew]`` with one channel) that supplies the texels
+        in their place, and a float64 tensor ``[3, 3]`` on any device that supplies the rotation in its place -- read to the host once per
+        call, like ``screen_param``, and through ``Environment``'s own orthonormality check.  The loss is differentiable w.r.t. each that
+        requires grad: every sample that reads the environment carries the gradient -- direct ones, through ones along their exit ray,
+        added reflections --, the nine rotation entries are independent inputs, and the gradients come back in the tensors' own dtype,
+        device and shape (drt_render_image_loss_env_param; csrc/drt_image_env_param.h and DESIGN.md 10.9 state the law).  The other
+        gradients are the same with and without them; without both the call is what it was."""
         from . import render as _render
         a = _render.check_image_loss_args(camera_M, height, width, screen, texture, target, weight, ior_int, ior_ext, vertices, want_image, supersample,
                                           max_bounces, tir, refraction, fresnel, void, invalid, max_samples, screen_param, texture_param, camera_param,
-                                          absorption, environment, reflection)
+                                          absorption, environment, reflection, env_texels_param, env_rotation_param)
         ior, tracked = _ior_args(intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext)
         dev = self._dev
         with _on(dev):
@@ -1383,8 +1406,9 @@ class Scene(StepwiseMixin):
         if a["environment"] is not None:
             with _on(dev):
                 env = torch.as_tensor(a["environment"].texels, device=dev).to(torch.float32).contiguous()
-            term = _image_env_term(self, a, ior, tex, env, tgt, wgt)
-            loss = _UnitSeedTerm.apply(term, *inputs)
+            param = env_texels_param is not None or env_rotation_param is not None      # (a keyword that is given takes its entry point)
+            term = _image_env_term(self, a, ior, tex, env, tgt, wgt, param)
+            loss = _UnitSeedTerm.apply(term, *inputs, *((env_texels_param, env_rotation_param) if param else ()))
             self.last_image_count = term.count
             return (loss, term.image) if a["want_image"] else loss
         if a["absorption"] is not None:

@@ -542,17 +542,60 @@ def camera_of_param(camera_param):
     return (None, None, rinv, mats[1])
 
 
+def environment_of_params(environment, env_texels_param=None, env_rotation_param=None):
+    """The ``Environment`` of ``environment`` with ``env_texels_param`` in the place of its texels and ``env_rotation_param`` in the place
+    of its rotation.  ``env_texels_param``: a float32 or float64 tensor shaped like the environment's texels,
+    ``[Eh, Ew, C]`` (or ``[Eh, Ew]`` with one channel); finite where that can be seen without touching a device.  ``env_rotation_param``:
+    a float64 tensor ``[3, 3]`` on any device, read to the host here, through ``Environment``'s own rotation check."""
+    given = [n for n, p in (("env_texels_param", env_texels_param), ("env_rotation_param", env_rotation_param)) if p is not None]
+    if not isinstance(environment, Environment):
+        raise ValueError(f"{' / '.join(given)} needs an environment: a drt_amd.render.Environment, got {type(environment).__name__}")
+    texels, rotation = environment.texels, environment.rotation
+    if env_texels_param is not None:
+        p = env_texels_param
+        if not _is_tensor(p):
+            raise ValueError(f"env_texels_param must be a float32 or float64 tensor [Eh, Ew, C] or [Eh, Ew], got {type(p).__name__}")
+        kind = str(p.dtype).replace("torch.", "")
+        if kind not in ("float32", "float64"):
+            raise ValueError(f"env_texels_param must be float32 or float64, got dtype {kind}")
+        want = tuple(environment.texels.shape)
+        if tuple(p.shape) != want and not (want[2] == 1 and tuple(p.shape) == want[:2]):
+            raise ValueError(f"env_texels_param must have the shape of the environment's texels, {want}" + (f" or {want[:2]}" if want[2] == 1 else "") +
+                             f", got shape {tuple(p.shape)}")
+        if p.device.type == "cpu" and not np.isfinite(p.detach().numpy()).all():
+            raise ValueError("env_texels_param must be finite")
+        texels = p.detach()
+    if env_rotation_param is not None:
+        p = env_rotation_param
+        if not _is_tensor(p):
+            raise ValueError(f"env_rotation_param must be a float64 tensor of shape (3, 3), got {type(p).__name__}")
+        if tuple(p.shape) != (3, 3):
+            raise ValueError(f"env_rotation_param must have shape (3, 3), got {tuple(p.shape)}")
+        kind = str(p.dtype).replace("torch.", "")
+        if kind != "float64":
+            raise ValueError(f"env_rotation_param must be float64, got dtype {kind}")
+        rotation = p.detach().cpu().numpy()
+    try:
+        return Environment(texels, rotation)
+    except ValueError as e:
+        raise ValueError(f"{' / '.join(given)}: {e}") from None
+
+
 def check_image_loss_args(camera_M, height, width, screen, texture, target, weight=None, ior_int=None, ior_ext=None, vertices=True,
                           want_image=False, supersample=1, max_bounces=2, tir="drop", refraction="reference", fresnel=True, void=0.0,
                           invalid=0.0, max_samples=1 << 22, screen_param=None, texture_param=None, camera_param=None, absorption=None, environment=None,
-                          reflection=False):
+                          reflection=False, env_texels_param=None, env_rotation_param=None):
     """Every argument check of ``Scene.image_loss_fused``, none of which needs a device: ``check_render_args``' dict plus target
     (float32 [H, W, C]; uint8 is read as value / 255; [H, W] with a one-channel texture), weight (float32 [H, W] or None), ior (the float
     of each IOR given as a number, else None), vertices and want_image.  ``screen_param`` / ``texture_param`` (tensors a gradient is
     wanted for) take the place of ``screen`` / ``texture``, which must then be None: exactly one form of each is given; so does
     ``camera_param`` = ``(Rinv, Kinv)`` for ``camera_M``.  ``absorption`` (``check_absorption``) goes with none of the three.  ``environment`` / ``reflection``
     (``check_render_args``): with an environment ``screen`` and ``texture`` may both be None; it goes with none of
-    ``absorption``, ``screen_param``, ``texture_param``, ``camera_param``."""
+    ``absorption``, ``screen_param``, ``texture_param``, ``camera_param``.  ``env_texels_param`` / ``env_rotation_param``
+    (``environment_of_params``) need an environment and take the place of its texels / rotation: ``a["environment"]`` is
+    then the environment the call renders."""
+    if env_texels_param is not None or env_rotation_param is not None:
+        environment = environment_of_params(environment, env_texels_param, env_rotation_param)
     if environment is not None or reflection is not False:
         for name, given in (("absorption", absorption), ("screen_param", screen_param), ("texture_param", texture_param), ("camera_param", camera_param)):
             if given is not None:

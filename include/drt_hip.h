@@ -819,6 +819,30 @@ int drt_render_image_loss_env(drt_scene_t* s, const double* d_verts, const doubl
                               const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
                               int64_t* d_count, const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection, void* stream);
 
+/* ---- ... and its gradients w.r.t. the environment's texels and rotation (csrc/drt_image_env_param.h states the law) --
+ * drt_render_image_loss_env with two more accumulating targets, each nullable (with both NULL the call IS drt_render_image_loss_env):
+ *   d_grad_env      [env_h, env_w, channels] accumulators += d loss / d (double)texel, addressed like d_grad_texture: the array is padded
+ *                   to a multiple of three values, (env_h * env_w * channels + 2) / 3 * 3 of them
+ *   d_grad_env_rot  9 accumulators += d loss / d env_rot9, row-major, the nine entries taken as independent inputs (addressed like
+ *                   d_grad_screen)
+ * A sample reads the environment along a direction with a weight w: a direct sample that the screen does not catch (or any, without a
+ * screen) along its camera ray with w = 1; a through sample whose exit ray the screen does not catch along that ray with w = T (1 with
+ * fresnel = 0); and, with reflection = 1, a through sample whose reflection was added and whose reflected ray the screen does not catch,
+ * along wr with w = R1.  One sample can read twice; an invalid one reads nothing.  Per read with cell, fx, fy of the lookup and the
+ * pixel's seeds g_c: the four texels of the cell (wrapped columns) receive (g_c[ch] w) times the bilinear weights; g_u = w sum_ch
+ * g_c[ch] dE/dfx, g_v likewise (0 outside the clamp of v), through atan2 and acos to the seed g_e of the direction in the environment
+ * frame, and d_grad_env_rot[3 r + c] += g_e[r] d[c].  The on-screen test, the cell, the wrap column, the clamp of v, the orthonormality
+ * check, the occlusion verdict, the class and the direction itself carry no gradient here; the other outputs are
+ * drt_render_image_loss_env's, bit for bit under drt_deterministic.  One more kernel over the pixels of the band; it also runs on a
+ * scene without triangles (every sample is direct).  No more workspace.  Both accumulation modes.  DRT_E_INVALID as
+ * drt_render_image_loss_env, and for d_grad_env with more than 2^31 - 1 texels.  drt_version() stays 13: probe for the symbol. */
+int drt_render_image_loss_env_param(drt_scene_t* s, const double* d_verts, const double* camera21, int height, int width, int y0, int y1, int supersample,
+                                    double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const double* screen9,
+                                    const float* d_texture, int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid,
+                                    const float* d_target, const float* d_weight, double* d_loss, double* d_grad_verts, double* d_grad_ior, float* d_image,
+                                    int64_t* d_count, const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection, double* d_grad_env,
+                                    double* d_grad_env_rot, void* stream);
+
 /* ---- the image term of several views in one call (csrc/drt_image_views.h states the mapping) -----------------------
  * A view table holds the cameras and screens of a capture whose views all have height x width pixels: cameras21 [n_views, 21] and
  * screens9 [n_views, 9], host arrays in drt_render_image's layouts.  drt_image_views_create checks every screen as drt_render_image
