@@ -238,11 +238,12 @@ class PhotoData(Data):
     ``weights`` ``[n, resy, resx]``, and the soft silhouette masks ``soft_masks`` float64 ``[n, resy, resx]`` of the silhouette term.
     ``get_view`` keeps the tuple layout of ``Data.get_view`` for that term -- (None, None, soft mask [P], eye point [1, 3], None,
     camera_M): a photograph has no per-pixel correspondences, so those fields are None.  ``binding(scene)`` is the capture as a
-    ``render.ImageViews`` of that scene."""
+    ``render.ImageViews`` of that scene.  ``environment`` (a ``render.Environment``): the room the photographs were
+    taken in, one for all views; with it ``screens`` and ``texture`` may both be None (no screen stood behind the object)."""
 
-    def __init__(self, cameras, screens, texture, photos, soft_masks, resx, resy, weights=None, device="cuda", seed=0, name="photo"):
-        self.cameras, self.screens, self.texture = list(cameras), list(screens), texture
-        self.photos, self.weights = photos, weights
+    def __init__(self, cameras, screens, texture, photos, soft_masks, resx, resy, weights=None, device="cuda", seed=0, name="photo", environment=None):
+        self.cameras, self.screens, self.texture = list(cameras), None if screens is None else list(screens), texture
+        self.photos, self.weights, self.environment = photos, weights, environment
         self.resx, self.resy = int(resx), int(resy)
         self.num_view = self.n_total = len(self.cameras)
         self.name, self.device = name, device
@@ -268,7 +269,8 @@ class PhotoData(Data):
         import weakref
         held = self.__dict__.get("_image_views")
         if held is None or held[0]() is not scene:
-            b = scene.bind_image_views(self.cameras, self.resy, self.resx, self.screens, self.photos, self.weights)
+            more = {} if self.environment is None else {"environment": self.environment}      # (without it: the call of before)
+            b = scene.bind_image_views(self.cameras, self.resy, self.resx, self.screens, self.photos, self.weights, **more)
             held = self._image_views = (weakref.ref(scene), b)
         return held[1]
 
@@ -277,27 +279,35 @@ class SyntheticPhotoData(PhotoData):
     """Turntable photographs of a ground-truth mesh in front of a textured screen, rendered by ``scene_gt.render_image`` under
     ``path_law`` = (max_bounces, tir[, refraction]) with ``supersample``^2 samples per pixel: per view the screen is
     ``render.Screen.behind`` the object, the photograph the rendered image, and the silhouette mask the pixels with an interaction (the
-    ``hit`` plane > 0) through ``views.process_mask``.  ``view_ids``: keep only these views of the turntable of ``n_total``."""
+    ``hit`` plane > 0) through ``views.process_mask``.  ``view_ids``: keep only these views of the turntable of ``n_total``.
+    ``environment`` / ``reflection``: ``render_image``'s -- the photographs are taken in that room, with the light reflected off the outer
+    surface when asked for; ``screen=False`` (needs an environment): no screen behind the object, ``texture`` is then ignored."""
 
     def __init__(self, scene_gt, center, extent, resx, resy, texture, num_view=8, device="cuda", n_total=None, view_ids=None, seed=0,
-                 name="synthetic-photo", path_law=(6, "reflect", "snell"), supersample=2, fresnel=True, span=2.0, void=0.0, invalid=0.0):
+                 name="synthetic-photo", path_law=(6, "reflect", "snell"), supersample=2, fresnel=True, span=2.0, void=0.0, invalid=0.0,
+                 environment=None, reflection=False, screen=True):
         from . import render
-        tex = render.check_texture(texture)
+        if not screen and environment is None:
+            raise ValueError("screen=False needs an environment: without either there is nothing to photograph")
+        tex = render.check_texture(texture) if screen else None
         n_total = num_view if n_total is None else n_total
         cams = views.turntable_cameras(center, extent, n_total, resx, resy)
         ids = list(range(n_total)) if view_ids is None else list(view_ids)
         law = tuple(path_law) + ("reference",) * (3 - len(path_law))
+        more = {} if environment is None else {"environment": environment, "reflection": reflection}      # (without it: the call of before)
         cameras, screens, photos, soft = [], [], [], []
         for k in ids:
-            screen = render.Screen.behind(cams[k], center, extent, tex.shape[1], tex.shape[0], span=span)
-            image, hit, _ = scene_gt.render_image(cams[k], resy, resx, screen, tex, supersample=supersample, max_bounces=law[0], tir=law[1],
-                                                  refraction=law[2], fresnel=fresnel, void=void, invalid=invalid, want_planes=True)
+            at = render.Screen.behind(cams[k], center, extent, tex.shape[1], tex.shape[0], span=span) if screen else None
+            image, hit, _ = scene_gt.render_image(cams[k], resy, resx, at, tex, supersample=supersample, max_bounces=law[0], tir=law[1],
+                                                  refraction=law[2], fresnel=fresnel, void=void, invalid=invalid, want_planes=True, **more)[:3]
             cameras.append(cams[k])
-            screens.append(screen)
+            screens.append(at)
             photos.append(image)
             soft.append(views.process_mask((hit > 0).cpu().numpy()))
-        super().__init__(cameras, screens, tex, torch.stack(photos), soft, resx, resy, device=device, seed=seed, name=name)
+        super().__init__(cameras, screens if screen else None, tex, torch.stack(photos), soft, resx, resy, device=device, seed=seed, name=name,
+                         environment=environment)
         self.path_law, self.supersample, self.fresnel, self.void, self.invalid = law, supersample, fresnel, void, invalid
+        self.reflection = bool(reflection)
 
 
 # ---------------------------------------------------------------------------------------------------------------

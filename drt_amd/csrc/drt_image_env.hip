@@ -9,7 +9,8 @@
 //                                       the environment along its exit direction (acos, atan2 and a wrapped bilinear fetch, for those
 //                                       samples only); no sample receives `void`
 // With `reflection` the forward wavefront keeps its face tape, whose row 0 is the first face of every sample, and between it
-// and the resolve kernel runs the reflection pass:
+// and the resolve kernel runs the reflection pass (reflection_pass, drt_image_env_loss.h: k_image_reflect_list and k_image_reflect_bwd are
+// stated there once over the view policy, for this unit's ImageOneView and for drt_image_views_env.hip's ImageViewTable):
 //   k_image_reflect_list  all samples : a sample that met the mesh forms its camera ray again, recomputes the Bounce of its first face and, where
 //                                       that is an entering, non-TIR interaction, appends the float32 reflected ray to a list of its own (the
 //                                       staged append of drt_pathsink.h into ping-pong list 0, free once the loop has ended; its size and its
@@ -34,37 +35,9 @@
 // No workspace of its own: the first face is the tape's row 0 (4 B per sample, already there for the loss) and the bit sits in the state
 // byte.  The list's order is never read, so two runs give the same bits.
 // Everything runs on the caller's stream, nothing is read back, every list size stays on the device.
-#include "drt_image_loss_bwd.h"
+#include "drt_image_env_loss.h"
 
 namespace {
-
-constexpr int kCntReflect = 34, kCntReflectRedo = 35;          // spare words of the counter block (drt_pathws.h): list size, second-pass count
-static_assert(kCntReflectRedo < kCntWords && kCntReflect > kCntValid, "counter block layout");
-
-template <bool SNELL>
-__global__ void __launch_bounds__(kPathBlock) k_image_reflect_list(PathCtx c, ImageCam cam, ImageBand band, const uint8_t* __restrict__ hits,
-                                                                    const int32_t* __restrict__ first_face, RayList out, unsigned* count) {
-    __shared__ StageMem stage;
-    stage_init(stage);
-    unsigned first, last;
-    block_run(band.n, first, last);
-    for (unsigned base = first; base < last; base += kPathBlock) {
-        const unsigned i = base + threadIdx.x;
-        bool go = false;
-        f3 o32{0.f, 0.f, 0.f}, d32{0.f, 0.f, 1.f};
-        if (i < band.n && hits[i] != 0) {
-            int x, y, j;
-            band_sample(band, i, x, y, j);
-            d3 o, d, ro, wr;
-            double R1;
-            image_sample_ray(cam, band.s, x, y, j, o, d);
-            go = image_reflect_first<SNELL>(c, first_face[i], o, d, ro, wr, R1);
-            if (go) { o32 = to_f32(ro); d32 = to_f32(wr); }
-        }
-        stage_push(stage, go, (int32_t)i, o32, d32, out, count);
-    }
-    stage_flush(stage, out, count);
-}
 
 // entry e of the traced reflection list: face < 0 = nothing in the way
 __global__ void __launch_bounds__(kPathBlock) k_image_reflect_mark(RayList list, const unsigned* __restrict__ n_list, unsigned n_samples, uint8_t* __restrict__ state) {
@@ -74,113 +47,6 @@ __global__ void __launch_bounds__(kPathBlock) k_image_reflect_mark(RayList list,
         const int32_t i = list.idx[e];
         if (i >= 0 && (unsigned)i < n_samples && list.face[e] < 0) state[i] = state[i] | kImageReflectSeen;
     }
-}
-
-// The adjoint of the reflection term of every listed (through) sample whose reflection was added.
-template <bool DET, bool SNELL, bool VERTS>
-__global__ void __launch_bounds__(256) k_image_reflect_bwd(PathCtx c, ImageOneView view, ImageBand band, ImageTex tx, ImageScreenEnv bg,
-                                                           const int32_t* __restrict__ first_face, const uint8_t* __restrict__ state,
-                                                           const int32_t* __restrict__ list, const unsigned* __restrict__ n_list,
-                                                           const double* __restrict__ g_c, double* grad_verts, double* grad_ior) {
-    int64_t n = *n_list;
-    if (n > (int64_t)band.n) n = band.n;
-    LossAcc<DET> acc_int, acc_ext;
-    sink_pass<DET, kPathsBwdBatch, VERTS>(n, grad_verts, [&](int64_t k, auto add) {
-        const int64_t i = list[k];
-        if (i < 0 || i >= (int64_t)band.n || !(state[i] & kImageReflectSeen)) return;
-        int x, r, j;
-        band_sample(band, (unsigned)i, x, r, j);
-        d3 o, d;
-        image_sample_ray(view.cam, band.s, x, r, j, o, d);
-        const int64_t pix = i / (band.s * band.s);
-        double g[kImageMaxChannels] = {0.0, 0.0, 0.0};
-        for (int ch = 0; ch < tx.c; ++ch) g[ch] = g_c[pix * tx.c + ch];
-        double gi, ge;
-        if (image_reflect_backward<SNELL>(c, first_face[i], o, d, view.sc, tx, bg.screen, bg.env, g, add, gi, ge)) { acc_int.add(gi); acc_ext.add(ge); }
-    });
-    if (grad_ior) {
-        acc_int.flush(ior_slot<DET>(grad_ior, 0));
-        acc_ext.flush(ior_slot<DET>(grad_ior, 1));
-    }
-}
-
-template <int... I>
-auto reflect_bwd_kernel(int sel, std::integer_sequence<int, I...>) {
-    using Kernel = decltype(&k_image_reflect_bwd<false, false, false>);
-    static const Kernel kernels[] = {k_image_reflect_bwd<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0>...};
-    return kernels[sel];
-}
-
-// The arguments an environment call adds, after image_call_check: fills `bg`.
-int env_args_check(const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection, int fresnel, int channels, bool has_screen,
-                   ImageScreenEnv& bg) {
-    if (!d_env) return fail(DRT_E_INVALID, "null device pointer argument (d_env)");
-    if (env_h < 2 || env_w < 2) return fail(DRT_E_INVALID, "env_h x env_w = %d x %d: the environment must be at least 2 x 2", env_h, env_w);
-    if (!env_rot9) return fail(DRT_E_INVALID, "null host pointer argument (env_rot9)");
-    if (!image_env_rot_ok(env_rot9)) return fail(DRT_E_INVALID, "env_rot9: the rotation must be orthonormal (max |R R^T - I| <= 1e-12)");
-    if (reflection != 0 && reflection != 1) return fail(DRT_E_INVALID, "reflection = %d: 0 (the reflected light is dropped) or 1 (add the outer-surface reflection)", reflection);
-    if (reflection && !fresnel) return fail(DRT_E_INVALID, "reflection = 1 needs fresnel = 1: the reflected share R1 is the complement of what the Fresnel term transmits");
-    bg.screen = has_screen;
-    bg.env = ImageEnv{d_env, env_h, env_w, channels, {}};
-    memcpy(bg.env.rot, env_rot9, sizeof(double) * 9);
-    return DRT_OK;
-}
-
-// The reflection pass on `st`, behind image_forward with the tape kept (a scene without triangles has direct samples only: nothing to do).
-void reflection_pass(drt_scene* s, const PathCtx& pc, const ImageCall& c, hipStream_t st) {
-    if (s->n_faces == 0) return;
-    const PathsWs& w = *paths_ws_of(s);
-    const RayList list{w.idx[0], w.ray[0], w.face[0]};          // (both ping-pong lists are free once the loop has ended)
-    const int gs = grid_for(c.n, kPathBlock, 8 * s->n_cu);
-    auto fill = c.snell ? k_image_reflect_list<true> : k_image_reflect_list<false>;
-    fill<<<gs, kPathBlock, 0, st>>>(pc, c.cam, c.band, w.hits, w.tape, list, w.cnt + kCntReflect);
-    launch_trace_list(kTraceAny, s->grid_path, st, pc.tc, list.ray, w.cnt + kCntReflect, TraceOut{list.face, nullptr, nullptr, nullptr}, w.redo,
-                      w.cnt + kCntReflectRedo, w.cnt + kCntDone, s->refill_min, s->inner_min, nullptr);
-    k_image_reflect_mark<<<gs, kPathBlock, 0, st>>>(list, w.cnt + kCntReflect, (unsigned)c.n, w.state);
-}
-
-// The host body of the loss call behind its checks, image_loss_run's steps under a background: workspace, forward (tape kept), reflection
-// pass, loss resolve, and -- on a scene with triangles, when a gradient or the count is wanted -- the list of through samples, the adjoint
-// and the reflection's adjoint.
-// grad_env / grad_env_rot (drt_render_image_loss_env_param; either may be null): the pass of drt_image_env_param.hip over the pixels of the
-// band comes last.  Between the resolve and it only w.idx[0] and the counter kCntValid are written (the through list): the state bytes,
-// the parked rows, the throughputs and the tape are what the resolve read.
-int env_loss_run(drt_scene* s, const double* d_verts, const ImageCall& c, const ImageScreenEnv& bg, bool reflection, const ImageLossOut& out, double* grad_env,
-                 double* grad_env_rot, hipStream_t st, const char* who) {
-    { int rc = ensure_image_loss_ws(s, c.n_pix * c.tx.c, 0, st, who); if (rc) return rc; }
-    { int rc = image_forward(s, d_verts, c, true, st, who); if (rc) return rc; }
-    const PathCtx pc = image_path_ctx(s, d_verts, c);
-    if (reflection) reflection_pass(s, pc, c, st);
-    const PathsWs& w = *paths_ws_of(s);
-    const ImageLossWs& lw = *static_cast<ImageLossWs*>(s->image_loss_ws);
-    const ImageOneView view{c.cam, c.sc};
-    const unsigned pix_grid = (unsigned)((c.n_pix + kPathBlock - 1) / kPathBlock);
-    if (reflection) {          // (the tape's address is read here, behind the forward that may have grown it)
-        const ImageScreenEnvReflect bgr{bg.screen, bg.env, pc, c.snell, w.tape, nullptr};
-        auto resolve = det_mode() ? k_image_loss_resolve<true, ImageOneView, ImageClear, ImageScreenEnvReflect>
-                                  : k_image_loss_resolve<false, ImageOneView, ImageClear, ImageScreenEnvReflect>;
-        resolve<<<pix_grid, kPathBlock, 0, st>>>(view, c.band, c.n_pix, c.tx, c.fill, c.fresnel, ImageClear{}, w.park, w.park + 3 * w.fused_cap, w.thr, w.state,
-                                                 w.hits, out.target, out.weight, lw.g_c, out.image, out.loss, nullptr, bgr);
-    } else {
-        auto resolve = det_mode() ? k_image_loss_resolve<true, ImageOneView, ImageClear, ImageScreenEnv>
-                                  : k_image_loss_resolve<false, ImageOneView, ImageClear, ImageScreenEnv>;
-        resolve<<<pix_grid, kPathBlock, 0, st>>>(view, c.band, c.n_pix, c.tx, c.fill, c.fresnel, ImageClear{}, w.park, w.park + 3 * w.fused_cap, w.thr, w.state,
-                                                 w.hits, out.target, out.weight, lw.g_c, out.image, out.loss, nullptr, bg);
-    }
-    if (s->n_faces > 0 && (out.grad_verts || out.grad_ior || out.count)) {
-        int32_t* const done = w.idx[0];          // (the reflection list is no longer needed: its verdicts are in the state bytes)
-        launch_paths_collect(grid_for(c.n, kPathBlock, 8 * s->n_cu), st, (unsigned)c.n, w.state, done, w.cnt + kCntValid);
-        const int grid = (out.grad_verts ? DRT_BWD_BPC : kImageLossBpc) * s->n_cu;
-        image_loss_bwd_kernel<ImageOneView, ImageClear, false, ImageScreenEnv>(det_mode(), c.snell, c.fresnel, out.grad_verts != nullptr)<<<grid, 256, 0, st>>>(
-            pc, view, c.band, c.tx, ImageClear{}, c.max_bounces, w.park, w.park + 3 * w.fused_cap, w.thr, w.tape, w.hits, done, w.cnt + kCntValid, lw.g_c,
-            out.grad_verts, out.grad_ior, reinterpret_cast<unsigned long long*>(out.count), nullptr, bg);
-        if (reflection && (out.grad_verts || out.grad_ior))
-            reflect_bwd_kernel((det_mode() ? 4 : 0) | (c.snell ? 2 : 0) | (out.grad_verts ? 1 : 0), std::make_integer_sequence<int, 8>{})<<<grid, 256, 0, st>>>(
-                pc, view, c.band, c.tx, bg, w.tape, w.state, done, w.cnt + kCntValid, lw.g_c, out.grad_verts, out.grad_ior);
-    }
-    HIP_TRY(hipGetLastError());
-    if (grad_env || grad_env_rot) return launch_image_env_param_bwd(s, pc, c, bg, reflection, lw.g_c, grad_env, grad_env_rot, st);
-    return DRT_OK;
 }
 
 // a screen that stands for none: never evaluated (ImageScreenEnv::screen is false), it only has to pass image_call_check
@@ -207,10 +73,36 @@ int env_loss_call(drt_scene_t* s, const double* d_verts, const double* camera21,
         return fail(DRT_E_INVALID, "env_h x env_w = %d x %d: an environment texel gradient (d_grad_env) takes at most 2^31 - 1 texels", env_h, env_w);
     hipStream_t st = (hipStream_t)stream;
     const ImageLossOut out{d_target, d_weight, d_loss, d_grad_verts, d_grad_ior, d_image, d_count, nullptr};
-    return env_loss_run(s, d_verts, c, bg, reflection != 0, out, d_grad_env, d_grad_env_rot, st, who);
+    const ImageOneView view{c.cam, c.sc};
+    { int rc = env_loss_run(s, d_verts, c, view, [&] { return image_forward(s, d_verts, c, true, st, who); }, bg, reflection != 0, out, st, who); if (rc) return rc; }
+    // grad_env / grad_env_rot (drt_render_image_loss_env_param; either may be null): the pass of drt_image_env_param.hip over the pixels of
+    // the band comes last, behind what env_loss_run left in the workspace
+    if (d_grad_env || d_grad_env_rot)
+        return launch_image_env_param_bwd(s, image_path_ctx(s, d_verts, c), c, bg, reflection != 0, static_cast<ImageLossWs*>(s->image_loss_ws)->g_c, d_grad_env,
+                                          d_grad_env_rot, st);
+    return DRT_OK;
 }
 
 }  // namespace
+
+// The arguments an environment call adds, after image_call_check: fills `bg`.
+int env_args_check(const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection, int fresnel, int channels, bool has_screen,
+                   ImageScreenEnv& bg) {
+    if (!d_env) return fail(DRT_E_INVALID, "null device pointer argument (d_env)");
+    if (env_h < 2 || env_w < 2) return fail(DRT_E_INVALID, "env_h x env_w = %d x %d: the environment must be at least 2 x 2", env_h, env_w);
+    if (!env_rot9) return fail(DRT_E_INVALID, "null host pointer argument (env_rot9)");
+    if (!image_env_rot_ok(env_rot9)) return fail(DRT_E_INVALID, "env_rot9: the rotation must be orthonormal (max |R R^T - I| <= 1e-12)");
+    if (reflection != 0 && reflection != 1) return fail(DRT_E_INVALID, "reflection = %d: 0 (the reflected light is dropped) or 1 (add the outer-surface reflection)", reflection);
+    if (reflection && !fresnel) return fail(DRT_E_INVALID, "reflection = 1 needs fresnel = 1: the reflected share R1 is the complement of what the Fresnel term transmits");
+    bg.screen = has_screen;
+    bg.env = ImageEnv{d_env, env_h, env_w, channels, {}};
+    memcpy(bg.env.rot, env_rot9, sizeof(double) * 9);
+    return DRT_OK;
+}
+
+void launch_image_reflect_mark(int grid, hipStream_t st, RayList list, const unsigned* n_list, unsigned n_samples, uint8_t* state) {
+    k_image_reflect_mark<<<grid, kPathBlock, 0, st>>>(list, n_list, n_samples, state);
+}
 
 extern "C" {
 
@@ -236,7 +128,7 @@ int drt_render_image_env(drt_scene_t* s, const double* d_verts, const double* ca
     const unsigned pix_grid = (unsigned)((c.n_pix + kPathBlock - 1) / kPathBlock);
     if (reflection) {
         const PathCtx pc = image_path_ctx(s, d_verts, c);
-        reflection_pass(s, pc, c, st);
+        reflection_pass(s, pc, c, ImageOneView{c.cam, c.sc}, st);
         const ImageScreenEnvReflect bgr{bg.screen, bg.env, pc, c.snell, w.tape, d_reflect};
         k_image_resolve<ImageClear, ImageScreenEnvReflect><<<pix_grid, kPathBlock, 0, st>>>(
             c.cam, c.band, c.n_pix, c.sc, c.tx, c.fill, c.fresnel, ImageClear{}, w.park, w.park + 3 * w.fused_cap, w.thr, w.state, w.hits, d_image, d_hit, d_through,

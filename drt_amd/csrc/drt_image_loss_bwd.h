@@ -4,7 +4,9 @@
 // loss call.  Four units instantiate them: drt_image_loss.hip <ImageOneView, ImageClear> (drt_render_image_loss),
 // drt_image_camera.hip the same with CAMERA, which also parks every sample's camera-ray seeds for k_image_camera_bwd (10.5),
 // drt_image_views.hip <ImageViewTable, ImageClear> (10.6) and drt_image_absorb.hip <ImageOneView, ImageAbsorb> (10.7).
-// Four units because a kernel's register allocation depends on the other kernels of its unit.
+// Four units because a kernel's register allocation depends on the other kernels of its unit.  For the same reason the
+// forms under an environment have units of their own: drt_image_env.hip <ImageOneView, ImageClear, ., ImageScreenEnv[Reflect]> (10.8) and
+// drt_image_views_env.hip <ImageViewTable, ImageClear, ., ImageScreenEnv[Reflect]> (10.10), through env_loss_run (drt_image_env_loss.h).
 #pragma once
 #include "drt_image_wave.h"
 #include "drt_image_loss.h"

@@ -17,26 +17,9 @@
 // The slot -> view id list reaches the kernels by value (ImageViewIds) and is resolved by an unrolled select (image_views_id): the call
 // stays capturable and copies nothing to the device per step.
 #include "drt_image_loss_bwd.h"
-
-struct drt_image_views {
-    drt_scene* scene = nullptr;
-    int n_views = 0, height = 0, width = 0;
-    ImageViewRow* d_rows = nullptr;
-    double* cam21 = nullptr;               // host copies [n_views, 21] / [n_views, 9]: what image_call_check reads of the first listed view
-    double* scr9 = nullptr;
-    drt_image_views* next = nullptr;       // the scene's list (drt_scene::image_views)
-};
+#include "drt_image_views_host.h"
 
 namespace {
-
-struct ViewsStart {
-    ImageViewTable view;
-    ImageBand band;
-};
-void image_start_views(const ImageStartArgs& a, const void* src) {
-    const ViewsStart& v = *static_cast<const ViewsStart*>(src);
-    k_image_start<<<a.grid, kPathBlock, 0, a.st>>>(a.nodes, a.n_tris, v.view, v.band, a.park_ori, a.park_dir, a.thr, a.state, a.hits, a.out, a.count);
-}
 
 void views_release(drt_image_views* v) {
     (void)hipFree(v->d_rows);
@@ -46,6 +29,11 @@ void views_release(drt_image_views* v) {
 }
 
 }  // namespace
+
+void image_start_views(const ImageStartArgs& a, const void* src) {
+    const ViewsStart& v = *static_cast<const ViewsStart*>(src);
+    k_image_start<<<a.grid, kPathBlock, 0, a.st>>>(a.nodes, a.n_tris, v.view, v.band, a.park_ori, a.park_dir, a.thr, a.state, a.hits, a.out, a.count);
+}
 
 void image_views_free(drt_scene* s) {
     drt_image_views* v = static_cast<drt_image_views*>(s->image_views);

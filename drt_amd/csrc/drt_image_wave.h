@@ -1,5 +1,5 @@
 // drt_image_wave.h -- what the calls on the refracted image share (drt_image.hip, drt_image_loss.hip, drt_image_screen.hip,
-// drt_image_camera.hip, drt_image_views.hip, drt_image_absorb.hip, drt_image_env.hip, drt_image_env_param.hip): the band of rows of one call, the checked call, the two policies a
+// drt_image_camera.hip, drt_image_views.hip, drt_image_absorb.hip, drt_image_env.hip, drt_image_env_param.hip, drt_image_views_env.hip): the band of rows of one call, the checked call, the two policies a
 // kernel of the family is stated over, and the forward half of the family, each kernel once as a template -- k_image_start<VIEW>,
 // k_image_shade<SNELL, FRESNEL, TAPE, PAYLOAD>, image_pixel_walk<PAYLOAD, BACKGROUND>, k_image_resolve<PAYLOAD, BACKGROUND> -- with the forward
 // wavefront that launches them (defined in drt_image.hip, as launch_trace_list is in drt_trace.hip).  drt_image_loss_bwd.h holds the loss half.

@@ -887,22 +887,32 @@ def enqueue_image_env_term(scene, vertices, a, ior, texture, env, target, weight
 
 
 def enqueue_image_views_term(scene, vertices, binding, view_ids, texture, law, supersample, fresnel, void, invalid, ior, loss_ptr, grad_ptr,
-                             grad_ior_ptr=None, count_ptr=None, bands=None):
+                             grad_ior_ptr=None, count_ptr=None, bands=None, reflection=False):
     """Enqueues the photometric image term of the listed views of ``binding`` (a ``render.ImageViews``) -- the SUM over ``view_ids`` of one
     view's loss and d loss / d vertices (unit seed), as one forward wavefront and one adjoint pass per band -- on the current stream; the
-    one place that packs the arguments of drt_render_image_loss_views.  ``law``: a normalised law tuple (K, tir[, refraction]);
-    ``texture``: a contiguous float32 device tensor [Th, Tw, C]; ``void`` / ``invalid``: float64 numpy arrays of C values; ``ior``:
-    (interior, exterior) floats; ``bands``: rows [r0, r1) of the tall image of ``len(view_ids) * H`` rows (``render.plan_bands``), the
-    whole of it without.  ``loss_ptr`` / ``grad_ptr`` / ``grad_ior_ptr`` / ``count_ptr`` are raw device addresses the kernels ADD into
-    (float64, or fixed-point cells in deterministic mode; int64 count); all but the first may be None.  Nothing is checked here but what
-    the library checks.  The caller is inside ``_on(device)``.  Returns what the enqueued kernels read, for the caller to keep alive."""
+    one place that packs the arguments of drt_render_image_loss_views and drt_render_image_loss_views_env.  The entry point follows the
+    binding: one made with an environment goes to drt_render_image_loss_views_env with its resident texels, its
+    rotation and ``reflection``; one without packs exactly the arguments of before.  ``law``: a normalised law tuple (K, tir[,
+    refraction]); ``texture``: a contiguous float32 device tensor [Th, Tw, C], or None with a binding without screens; ``void`` /
+    ``invalid``: float64 numpy arrays of C values; ``ior``: (interior, exterior) floats; ``bands``: rows [r0, r1) of the tall image of
+    ``len(view_ids) * H`` rows (``render.plan_bands``), the whole of it without.  ``loss_ptr`` / ``grad_ptr`` / ``grad_ior_ptr`` /
+    ``count_ptr`` are raw device addresses the kernels ADD into (float64, or fixed-point cells in deterministic mode; int64 count); all
+    but the first may be None.  Nothing is checked here but what the library checks.  The caller is inside ``_on(device)``.  Returns
+    what the enqueued kernels read, for the caller to keep alive."""
     ids = (ctypes.c_int * len(view_ids))(*view_ids)
     flags = _law_flags(law[1], law[2] if len(law) > 2 else "reference")
+    env = getattr(binding, "env", None)
+    if env is None:
+        fn, more = _lib.lib().drt_render_image_loss_views, ()
+        tex_args = (texture.data_ptr(), texture.shape[0], texture.shape[1], texture.shape[2])
+    else:
+        fn, more = _lib.lib().drt_render_image_loss_views_env, (env.data_ptr(), env.shape[0], env.shape[1], binding.env_rot.ctypes.data, int(reflection))
+        tex_args = (None, 0, 0, env.shape[2]) if texture is None else (texture.data_ptr(), texture.shape[0], texture.shape[1], texture.shape[2])
     for r0, r1 in (bands if bands is not None else [(0, len(view_ids) * binding.height)]):
-        _lib.check(_lib.lib().drt_render_image_loss_views(
+        _lib.check(fn(
             scene.optix_mesh._h, vertices.data_ptr(), binding._h, ids, len(view_ids), r0, r1, supersample, ior[0], ior[1], law[0], flags, int(fresnel),
-            texture.data_ptr(), texture.shape[0], texture.shape[1], texture.shape[2], void.ctypes.data, invalid.ctypes.data, binding.targets.data_ptr(),
-            _lib.ptr(binding.weights), loss_ptr, grad_ptr, grad_ior_ptr, count_ptr, _stream()))
+            *tex_args, void.ctypes.data, invalid.ctypes.data, binding.targets.data_ptr(),
+            _lib.ptr(binding.weights), loss_ptr, grad_ptr, grad_ior_ptr, count_ptr, *more, _stream()))
     return [vertices, texture, binding]
 
 
@@ -1079,7 +1089,7 @@ def _image_views_term(scene, binding, a, ior, tex, law):
     def enqueue(loss, cells):
         with _on(v.device):
             enqueue_image_views_term(scene, v, binding, a["ids"], tex, law, a["supersample"], a["fresnel"], a["void"], a["invalid"], ior, loss.data_ptr(),
-                                     _lib.ptr(cells.get(_VERTS)), cells["ior"].data_ptr(), count.data_ptr(), a["bands"])
+                                     _lib.ptr(cells.get(_VERTS)), cells["ior"].data_ptr(), count.data_ptr(), a["bands"], a.get("reflection", False))
     return _Term(v.device, _verts_ior_accs(v, a["vertices"]), enqueue, ((_VERTS, None),) + _IOR_FEEDS, count)
 
 
@@ -1427,14 +1437,17 @@ class Scene(StepwiseMixin):
         self.last_image_count = term.count
         return (loss, term.image) if a["want_image"] else loss
 
-    def bind_image_views(self, cameras, height, width, screens, targets, weights=None):
+    def bind_image_views(self, cameras, height, width, screens, targets, weights=None, *, environment=None):
         """A handle for the views of a capture of photographs (``render.ImageViews``) for ``image_loss_views_fused``: ``cameras`` a list of
         ``camera_M`` tuples, ``screens`` a list of ``render.Screen`` (one per camera), ``targets`` ``[n, height, width(, C)]`` float32, or
         uint8 read as value / 255, ``weights`` float32 ``[n, height, width]`` or None; numpy or device tensors.  The cameras and screens
-        go to a device table once; the target and weight stacks stay resident.  Every argument error is raised before the device is
-        touched (``render.check_image_views_args``)."""
+        go to a device table once; the target and weight stacks stay resident.  ``environment`` (a ``render.Environment`` with the
+        targets' channels): the room the capture was taken in, one for all views -- it belongs to the capture, so it
+        lives here: its texels stay resident with the stacks, and the calls on this binding render in front of it.  With one,
+        ``screens`` may be None: the capture has no screen.  Every argument error is raised before the device is touched
+        (``render.check_image_views_args``)."""
         from . import render as _render
-        return _render.ImageViews(self, _render.check_image_views_args(cameras, height, width, screens, targets, weights))
+        return _render.ImageViews(self, _render.check_image_views_args(cameras, height, width, screens, targets, weights, environment))
 
     def image_loss_views_fused(self, binding, view_ids, texture, *, ior_int=None, ior_ext=None, vertices=True, supersample=1, max_bounces=2,
                                tir="drop", refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, environment=None,
@@ -1445,17 +1458,25 @@ class Scene(StepwiseMixin):
         share ``texture``, the law and band keywords, the fills and the IORs, all as in ``image_loss_fused``; the listed views are stacked
         into an image of ``len(view_ids) * H`` rows, which is evaluated in bands of at most ``max_samples`` samples (a band may straddle
         a view border) into one set of accumulators.  No image output and no screen, texture or camera gradients:
-        ``image_loss_fused`` has those, and it alone takes an ``environment`` or ``reflection``: given here they raise ``ValueError``."""
+        ``image_loss_fused`` has those.  A binding made with an environment (``bind_image_views(..., environment=)``) renders every view
+        in front of it, as ``image_loss_fused(..., environment=)`` does view by view (drt_render_image_loss_views_env; DESIGN.md 10.10);
+        ``texture`` is None exactly when that binding has no screens, and ``reflection=True`` (needs such a binding and ``fresnel``) adds
+        the outer-surface reflection.  The environment belongs to the capture: ``environment=`` given HERE raises ``ValueError``, and so
+        does ``reflection=True`` on a binding without an environment.  The environment's texels and rotation receive no gradient in this
+        call; ``image_loss_fused`` keeps those."""
         from . import render as _render
-        if environment is not None or reflection is not False:
-            raise ValueError("environment / reflection: the multi-view call has no environment form; use image_loss_fused view by view")
+        if environment is not None:
+            raise ValueError("environment: the multi-view call takes its environment from the binding; give it to bind_image_views(..., environment=)")
+        if reflection is not False and not (isinstance(binding, _render.ImageViews) and binding.args.get("environment") is not None):
+            raise ValueError("reflection: the multi-view call reflects the binding's environment and this binding has none; "
+                             "give one to bind_image_views(..., environment=)")
         a = _render.check_image_views_law(binding, view_ids, texture, ior_int, ior_ext, vertices, supersample, max_bounces, tir, refraction, fresnel,
-                                          void, invalid, max_samples)
+                                          void, invalid, max_samples, reflection)
         if binding.scene is not self:
             raise ValueError("binding was made by another scene's bind_image_views")
         ior, tracked = _ior_args(intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext)
         with _on(self._dev):
-            tex = torch.as_tensor(a["texture"], device=self._dev).to(torch.float32).contiguous()
+            tex = None if a["texture"] is None else torch.as_tensor(a["texture"], device=self._dev).to(torch.float32).contiguous()
         term = _image_views_term(self, binding, a, ior, tex, (a["max_bounces"], tir, refraction))
         loss = _UnitSeedTerm.apply(term, self.vertices if a["vertices"] else self.vertices.detach(), *tracked)
         self.last_image_count = term.count

@@ -502,10 +502,12 @@ class PhotoIteration(FusedIteration):
     adjoint pass (diffrender.enqueue_image_views_term) with the weight ``HyperParams["image_w"] / (views_per_step H W)``
     -- the mean squared residual per pixel.  The silhouette and smoothness terms, the side stream and the tail are FusedIteration's.
     ``path_law`` = (max_bounces, tir[, refraction]), ``fresnel`` and ``supersample`` are the image's law (``Scene.render_image``);
-    ``HyperParams["IOR"]`` is the object's index of refraction.  One process only."""
+    ``HyperParams["IOR"]`` is the object's index of refraction.  A capture with an ``environment`` is rendered in
+    front of it (its binding carries it), without a screen when the capture has none; ``reflection=True`` (needs such a capture and
+    ``fresnel``) adds the outer-surface reflection.  One process only."""
 
     def __init__(self, scene, data, HyperParams, lr, views_per_step=8, path_law=(6, "reflect", "snell"), fresnel=True, supersample=1, concurrent=True,
-                 schedule=None, max_samples=1 << 22):
+                 schedule=None, max_samples=1 << 22, reflection=False):
         import torch.distributed as tdist
         if tdist.is_available() and tdist.is_initialized():
             raise NotImplementedError("PhotoIteration runs in one process: under an initialised torch.distributed group the photometric term "
@@ -522,13 +524,19 @@ class PhotoIteration(FusedIteration):
         self.image_law = (tuple(law) + ("reference",))[:3]
         if not isinstance(fresnel, (bool, np.bool_)):
             raise ValueError(f"fresnel must be True or False, got {fresnel!r}")
-        self.fresnel, self.supersample = bool(fresnel), supersample
+        if not isinstance(reflection, (bool, np.bool_)):
+            raise ValueError(f"reflection must be True or False, got {reflection!r}")
+        if reflection and getattr(data, "environment", None) is None:
+            raise ValueError("reflection=True needs a capture with an environment (PhotoData(..., environment=))")
+        if reflection and not fresnel:
+            raise ValueError("reflection=True needs fresnel=True: the reflected share is the complement of what the Fresnel term transmits")
+        self.fresnel, self.supersample, self.reflection = bool(fresnel), supersample, bool(reflection)
         self.bands_of = lambda n: render.plan_bands(n * data.resy, data.resx, supersample, max_samples)
         self._init(scene, data, hp, lr, k, concurrent, None, schedule)
         self.binding = data.binding(scene)
         dev = scene.vertices.device
         with torch.cuda.device(dev):
-            self.texture = torch.as_tensor(render.check_texture(data.texture), device=dev).to(torch.float32).contiguous()
+            self.texture = None if data.screens is None else torch.as_tensor(render.check_texture(data.texture), device=dev).to(torch.float32).contiguous()
         c = self.binding.channels
         self.fills = (render._fill(getattr(data, "void", 0.0), c, "void"), render._fill(getattr(data, "invalid", 0.0), c, "invalid"))
         self.ior = (Render._ior_host(hp["IOR"], "HyperParams['IOR']"), Render._ior_host(Render.extIOR, "extIOR"))
@@ -546,7 +554,8 @@ class PhotoIteration(FusedIteration):
         if not image_ids:
             return []
         return Render.enqueue_image_views_term(self.scene, vertices, self.binding, image_ids, self.texture, self.image_law, self.supersample, self.fresnel,
-                                               *self.fills, self.ior, self._l_ptr[0], self._g_ptr[0], bands=self.bands_of(len(image_ids)))
+                                               *self.fills, self.ior, self._l_ptr[0], self._g_ptr[0], bands=self.bands_of(len(image_ids)),
+                                               reflection=self.reflection)
 
     def _weights(self):
         hp, data = self.hp, self.data
@@ -555,10 +564,10 @@ class PhotoIteration(FusedIteration):
 
 
 def optimize_photometric(scene, data, HyperParams, views_per_step=8, remesh="isotropic", output=True, path_law=(6, "reflect", "snell"), fresnel=True,
-                         supersample=1):
+                         supersample=1, reflection=False):
     """The pass / iteration loop of ``optimize_sharded`` on one rank with PhotoIteration steps: fits ``scene``'s mesh to the photographs of
     ``data`` (captured_data.PhotoData) under ``HyperParams`` (``image_w`` in the place of ``ray_w``; the other keys as in ``optimize``).
-    ``remesh`` as in ``optimize``.  Returns (scene, history, stats): history = the weighted loss every 100 iterations, stats the passes,
+    ``remesh`` as in ``optimize``; ``reflection`` as in PhotoIteration.  Returns (scene, history, stats): history = the weighted loss every 100 iterations, stats the passes,
     iterations and ``step_seconds`` (the iterations without the remesh, device-synchronised at the end of each pass)."""
     remesh = resolve_remesh(remesh)
     hp = dict(HyperParams)
@@ -574,7 +583,8 @@ def optimize_photometric(scene, data, HyperParams, views_per_step=8, remesh="iso
             print(f"remesh_len {remesh_len:g} lr {lr:g}")
         if remesh is not None:
             remesh(scene, remesh_len)
-        stepper = PhotoIteration(scene, data, hp, lr, views_per_step, path_law=path_law, fresnel=fresnel, supersample=supersample, schedule=schedule)
+        stepper = PhotoIteration(scene, data, hp, lr, views_per_step, path_law=path_law, fresnel=fresnel, supersample=supersample, schedule=schedule,
+                                 reflection=reflection)
         torch.cuda.synchronize(scene.vertices.device)
         t0 = time.perf_counter()
         run_steps(stepper, hp["Iters"], history, output)

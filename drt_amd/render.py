@@ -662,16 +662,29 @@ def _camera21(camera_M, name):
     return np.concatenate([kinv.reshape(-1), rinv[:3, :].reshape(-1)])
 
 
-def check_image_views_args(cameras, height, width, screens, targets, weights=None):
+# the table row of a view without a screen: never evaluated (the environment call then runs with no screen), it only has to pass the
+# library's check of a screen
+NO_SCREEN_ROW = (0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def check_image_views_args(cameras, height, width, screens, targets, weights=None, environment=None):
     """Every argument check of ``Scene.bind_image_views``, none of which needs a device.  Returns a dict: n, height, width, channels,
     cameras (float64 [n, 21]: K^-1, then the top 3 x 4 of R^-1, per view), screens (float64 [n, 9]), targets (float32 [n, H, W, C];
     uint8 is read as value / 255; [n, H, W] is one channel) and weights (float32 [n, H, W] or None) -- numpy arrays made contiguous, or
-    device tensors as they are after the shape and dtype checks."""
+    device tensors as they are after the shape and dtype checks --, environment (an ``Environment`` or None; its channels must be the
+    targets') and has_screens.  ``screens=None`` goes with an environment only: the capture has no screen, the rows of
+    ``screens`` are then placeholders that are never read."""
     height, width = _int(height, "height"), _int(width, "width")
     if height < 1 or width < 1:
         raise ValueError(f"height, width must be at least 1, got {(height, width)}")
+    if environment is not None and not isinstance(environment, Environment):
+        raise ValueError(f"environment must be a drt_amd.render.Environment, got {type(environment).__name__}")
+    has_screens = screens is not None
+    if not has_screens and environment is None:
+        raise ValueError("screens is None and no environment is given: a capture without screens needs an environment to look at")
     try:
-        cameras, screens = list(cameras), list(screens)
+        cameras = list(cameras)
+        screens = list(screens) if has_screens else [Screen(NO_SCREEN_ROW[0:3], NO_SCREEN_ROW[3:6], NO_SCREEN_ROW[6:9])] * len(cameras)
     except TypeError:
         raise ValueError("cameras must be a list of camera_M tuples and screens a list of Screen objects") from None
     n = len(cameras)
@@ -700,9 +713,12 @@ def check_image_views_args(cameras, height, width, screens, targets, weights=Non
     if len(targets.shape) != 4 or targets.shape[3] not in (1, 3):
         raise ValueError(f"targets must be [n, H, W], [n, H, W, 1] or [n, H, W, 3], got shape {tuple(targets.shape)}")
     channels = int(targets.shape[3])
+    if environment is not None and environment.channels != channels:
+        raise ValueError(f"environment has {environment.channels} channels, the targets have {channels}: they must agree")
     return dict(n=n, height=height, width=width, channels=channels, cameras=cams, screens=np.ascontiguousarray(np.stack(rows), dtype=np.float64),
                 targets=_plane(targets, (n, height, width, channels), "targets", True),
-                weights=None if weights is None else _plane(weights, (n, height, width), "weights", False))
+                weights=None if weights is None else _plane(weights, (n, height, width), "weights", False), environment=environment,
+                has_screens=has_screens)
 
 
 def check_view_ids(view_ids, n_views):
@@ -720,17 +736,28 @@ def check_view_ids(view_ids, n_views):
 
 
 def check_image_views_law(binding, view_ids, texture, ior_int=None, ior_ext=None, vertices=True, supersample=1, max_bounces=2, tir="drop",
-                          refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22):
+                          refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, reflection=False):
     """Every argument check of ``Scene.image_loss_views_fused`` behind the binding: ``check_render_args``' dict for the tall image of
-    ``len(view_ids) * H`` rows (camera and screen are the first listed view's and stand for nothing), plus ids, ior and vertices."""
+    ``len(view_ids) * H`` rows (camera and screen are the first listed view's and stand for nothing), plus ids, ior and vertices.  The
+    environment is the binding's (``a["environment"]``, or None); ``texture`` is None exactly when the binding has no screens;
+    ``reflection`` needs the binding's environment and ``fresnel``."""
     if not isinstance(binding, ImageViews):
         raise ValueError(f"binding must be a drt_amd.render.ImageViews (Scene.bind_image_views), got {type(binding).__name__}")
     ids = check_view_ids(view_ids, binding.n)
     cam = binding.args["cameras"][ids[0]]
     rinv = np.concatenate([cam[9:].reshape(3, 4), np.array([[0.0, 0.0, 0.0, 1.0]])])
     sc = binding.args["screens"][ids[0]]
-    a = check_render_args((None, None, rinv, cam[:9].reshape(3, 3)), len(ids) * binding.height, binding.width, Screen(sc[0:3], sc[3:6], sc[6:9]), texture,
-                          supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples)
+    env = binding.args.get("environment")
+    if binding.args.get("has_screens", True):
+        if texture is None:
+            raise ValueError("texture is None: the binding has screens, and the views share one texture")
+        screen = Screen(sc[0:3], sc[3:6], sc[6:9])
+    else:
+        if texture is not None:
+            raise ValueError("texture must be None: the binding was made with screens=None (every ray sees the environment)")
+        screen = None
+    a = check_render_args((None, None, rinv, cam[:9].reshape(3, 3)), len(ids) * binding.height, binding.width, screen, texture,
+                          supersample, max_bounces, tir, refraction, fresnel, void, invalid, max_samples, environment=env, reflection=reflection)
     if a["channels"] != binding.channels:
         raise ValueError(f"texture has {a['channels']} channels, the binding's targets have {binding.channels}")
     a["ids"] = ids
@@ -744,7 +771,9 @@ def check_image_views_law(binding, view_ids, texture, ior_int=None, ior_ext=None
 class ImageViews:
     """The views of a capture for ``Scene.image_loss_views_fused``, made by ``Scene.bind_image_views``: the device table of cameras and
     screens (drt_image_views_create; owned here, freed with this object or with the scene, whichever goes first) and the resident
-    target and weight stacks.  ``n`` views of ``height`` x ``width`` pixels and ``channels`` channels."""
+    target and weight stacks.  ``n`` views of ``height`` x ``width`` pixels and ``channels`` channels.  A binding made with an
+    environment also keeps its texels resident (``env``, float32 [Eh, Ew, C]) and holds the packed rotation
+    (``env_rot``, nine doubles); without one both are None."""
 
     def __init__(self, scene, args):
         import ctypes
@@ -759,6 +788,9 @@ class ImageViews:
             t = torch.as_tensor(args["targets"], device=dev)
             self.targets = (t.to(torch.float32) / 255.0 if t.dtype == torch.uint8 else t).reshape(self.n, self.height, self.width, self.channels).contiguous()
             self.weights = None if args["weights"] is None else torch.as_tensor(args["weights"], device=dev).contiguous()
+            environment = args.get("environment")
+            self.env = None if environment is None else torch.as_tensor(environment.texels, device=dev).to(torch.float32).contiguous()
+            self.env_rot = None if environment is None else environment.packed()
             _lib.check(_lib.lib().drt_image_views_create(scene.optix_mesh._h, self.n, args["cameras"].ctypes.data, args["screens"].ctypes.data,
                                                          self.height, self.width, ctypes.byref(h)))
         self._h = h.value

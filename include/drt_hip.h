@@ -870,6 +870,26 @@ int drt_render_image_loss_views(drt_scene_t* s, const double* d_verts, const drt
                                 int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid, const float* d_targets,
                                 const float* d_weights, double* d_loss, double* d_grad_verts, double* d_grad_ior, int64_t* d_count, void* stream);
 
+/* ---- ... in front of one environment ------------------------------------------------------------------------------
+ * The SUM over the listed views of what drt_render_image_loss_env adds for each of them -- *d_loss, d_grad_verts, d_grad_ior, *d_count --
+ * as ONE forward wavefront, ONE reflection pass and ONE adjoint pass: drt_render_image_loss_views' 26 arguments, then
+ * drt_render_image_loss_env's five (d_env, env_h, env_w, env_rot9, reflection) before `stream`.  Shared by the views: the environment
+ * (texels and rotation), `reflection`, the path law, supersampling, the texture, fill_invalid and the IORs; per view: camera, screen,
+ * target and optional weight plane.  d_texture == NULL: no screen for any view -- the table's screens are then never read (they must
+ * still have passed drt_image_views_create), tex_h and tex_w are ignored and `channels` is the environment's.  The reflected ray of a
+ * sample is formed with the camera of its row's view and the row within that view.  No environment texel or rotation gradient here:
+ * drt_render_image_loss_env_param has those.  Workspace: drt_render_image_loss_views'; growth inside a stream capture is refused with
+ * this function's name.  Both accumulation modes.  DRT_E_INVALID (nothing enqueued, no output touched): everything
+ * drt_render_image_loss_views refuses about the table and the id list, a NULL d_env (it is looked at first: without a screen it stands
+ * in for the texture), everything else that call refuses (but a NULL d_texture), then an environment side below 2, a NULL or non-orthonormal
+ * env_rot9, a reflection outside {0, 1}, reflection without fresnel -- the message names the argument.  drt_version() stays 13: probe for
+ * the symbol. */
+int drt_render_image_loss_views_env(drt_scene_t* s, const double* d_verts, const drt_image_views_t* views, const int* view_ids, int k, int r0, int r1,
+                                    int supersample, double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const float* d_texture,
+                                    int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid, const float* d_targets,
+                                    const float* d_weights, double* d_loss, double* d_grad_verts, double* d_grad_ior, int64_t* d_count, const float* d_env,
+                                    int env_h, int env_w, const double* env_rot9, int reflection, void* stream);
+
 /* ---- measurement (bench.py's live per-kernel timing) --------------------------------------------
  * When enabled (on = 1; on = 2 additionally collects the traversal statistics below, which perturbs
  * timing; on = 3 runs the sub-batches of a call one after the other on ONE internal stream instead of two, so that
