@@ -17,6 +17,8 @@ SIGMA3, SIGMA1 = (0.004, 0.012, 0.03), (0.012,)      # per unit of mesh length; 
 
 
 def sigma(name):
+    if isinstance(name, dict):           # a scene dict carries its own coefficients (tests/image_fuzz_cases.py)
+        return np.asarray(name["sigma"], np.float64)
     return np.array(SIGMA3 if image_cases.SCENES[name][4] == 3 else SIGMA1, np.float64)
 
 
@@ -32,5 +34,8 @@ def reference(name, law, fresnel, weighted=False, length_gradient=True):
 def image_tolerance(name, base, law):
     """image_cases.tolerance plus sigma_max (max_bounces - 1) 2 RAY_ABS (1 + 1 / GRAZING): an interior segment's two end points are each
     off by at most RAY_ABS (1 + 1 / GRAZING) along the ray, there are at most max_bounces - 1 interior segments, and
-    |d c / d L| <= sigma_max for a colour in [0, 1]."""
+    |d c / d L| <= sigma_max for a colour in [0, 1].  On a scene dict (a random shape) an end point is off by the fuzz tests' origin
+    tolerance image_cases.FUZZ_ORI in place of RAY_ABS."""
+    if isinstance(name, dict):
+        return image_cases.tolerance(name, base) + float(sigma(name).max()) * (law[0] - 1) * 2 * image_cases.FUZZ_ORI * (1 + 1 / image_cases.GRAZING)
     return image_cases.tolerance(name, base) + float(sigma(name).max()) * (law[0] - 1) * 2 * image_cases.RAY_ABS * (1 + 1 / image_cases.GRAZING)

@@ -18,6 +18,7 @@ RAY_ABS = 1e-10              # the project's exit-ray tolerance (tests/test_gpu_
 GRAZING = 0.05               # |dot(d, n)| below this: the plane hit amplifies the exit ray's error by more than 1 + 1 / 0.05 = 21
 BORDER = 1e-3                # texels: a sample this close to a screen border may fall on the other side of it
 SENSITIVE_CAP = 0.03         # share of pixels the image comparison may leave out
+FUZZ_ORI, FUZZ_DIR = 1e-9, 1e-10          # the project's exit-ray tolerances on random shapes (tests/test_gpu_fuzz.py): origin, direction
 
 # (name, view, height, width, supersample, channels)
 SCENES = {"v5": (5, 32, 32, 2, 3), "v41": (41, 32, 32, 2, 3), "wide": (41, 24, 40, 2, 1)}
@@ -59,17 +60,24 @@ def reference(name, law, fresnel):
                             law[0], law[1], law[2], fresnel, sc["void"], sc["invalid"], IOR, EXT)
 
 
+def _scene(name):
+    """A named scene, or a scene dict of the same shape as it is (tests/image_fuzz_cases.py)."""
+    return name if isinstance(name, dict) else scene(name)
+
+
 def sensitive(name, ref):
     """bool [H, W]: pixels with a sample whose exit ray grazes the screen (|dot(d, n^)| < GRAZING) or lands within BORDER texels of one of
-    its borders -- samples that evaluate the plane at all (direct and through ones that see it)."""
-    sc = scene(name)
+    its borders -- samples that evaluate the plane at all (direct and through ones that see it).  The tops of u and v are the texture's
+    own width and height, less one."""
+    sc = _scene(name)
+    tex_h, tex_w = np.asarray(sc["texture"]).shape[:2]
     n = np.cross(sc["screen"].eu, sc["screen"].ev)
     cos = (ref["dn"] / np.linalg.norm(n)).abs().numpy()
     looks = (ref["cls"] != image_ref.INVALID).numpy()
     seen = looks & (ref["dn"] != 0).numpy() & (ref["t"] > 0).numpy()
     u, v = ref["u"].numpy(), ref["v"].numpy()
     near = np.zeros_like(seen)
-    for w, top in ((u, TEX - 1), (v, TEX - 1)):
+    for w, top in ((u, tex_w - 1), (v, tex_h - 1)):
         near |= (np.abs(w) < BORDER) | (np.abs(w - top) < BORDER)
     bad = (looks & (cos < GRAZING)) | (seen & near)
     return bad.reshape(sc["height"] * sc["width"], -1).any(1).reshape(sc["height"], sc["width"])
@@ -78,12 +86,18 @@ def sensitive(name, ref):
 def tolerance(name, ref):
     """2^-23 + G * RAY_ABS * (1 + t_max) * 21 / pitch: an exit ray off by RAY_ABS in origin and direction moves its screen point by at most
     RAY_ABS (1 + t) (1 + 1 / GRAZING) off the grazing cut, i.e. by that many / pitch texels, and a texel step changes the bilinear
-    sample by at most G, the largest difference between neighbouring texels; 2^-23 is the float32 store of a value in [0, 1]."""
-    sc = scene(name)
+    sample by at most G, the largest difference between neighbouring texels; 2^-23 is the float32 store of a value in [0, 1].
+    A scene dict (a random shape) has the exit-ray tolerances of the project's fuzz tests in place of RAY_ABS (1 + t_max): FUZZ_ORI on
+    the origin and FUZZ_DIR on the direction, i.e. FUZZ_ORI + FUZZ_DIR * t_max; and, its texture not being square, the smaller of the two
+    pitches |eu|, |ev| (a displacement of the screen point is that many texels along the finer axis)."""
+    sc = _scene(name)
     tex = sc["texture"].astype(np.float64)
     G = max(np.abs(np.diff(tex, axis=0)).max(), np.abs(np.diff(tex, axis=1)).max())
     t = ref["t"].numpy()[ref["on"].numpy()]
     t_max = float(t.max()) if len(t) else 0.0
+    if isinstance(name, dict):
+        pitch = min(float(np.linalg.norm(sc["screen"].eu)), float(np.linalg.norm(sc["screen"].ev)))
+        return 2.0 ** -23 + G * (FUZZ_ORI + FUZZ_DIR * t_max) * (1.0 + 1.0 / GRAZING) / pitch
     pitch = float(np.linalg.norm(sc["screen"].eu))
     return 2.0 ** -23 + G * RAY_ABS * (1.0 + t_max) * (1.0 + 1.0 / GRAZING) / pitch
 

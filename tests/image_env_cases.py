@@ -47,13 +47,16 @@ def reference(name, law, with_screen, reflection=False):
                                      env.texels, env.rotation, sc["invalid"], reflected(name) if reflection else None)
 
 
-def sensitive(name, law, with_screen, reflection=False):
+def sensitive(name, law, with_screen, reflection=False, ref=None, stage=None):
     """bool [H, W]: with a screen ``image_cases.sensitive``'s pixels (a sample that grazes the screen's plane or lands near a border of it
     may change between screen and environment); pixels with a sample that goes to the environment within POLE of a pole; and, with the
     reflection, pixels with an added reflected ray that goes to the environment within POLE of a pole, sees the screen's plane within
-    BORDER texels of a border, or lands on the screen with |dot(d, n^)| < GRAZING."""
-    sc = image_cases.scene(name)
-    ref = reference(name, law, with_screen, reflection)
+    BORDER texels of a border, or lands on the screen with |dot(d, n^)| < GRAZING.  The tops of u and v are the texture's own width and
+    height, less one.  A scene dict (tests/image_fuzz_cases.py) comes with its own ``ref`` (``image_env_ref.render_from``'s dict) and
+    ``stage`` (``image_ref.render``'s)."""
+    sc = image_cases._scene(name)
+    ref = reference(name, law, with_screen, reflection) if ref is None else ref
+    tex_h, tex_w = np.asarray(sc["texture"]).shape[:2]
     bad = (ref["src"] == image_env_ref.ENV) & (1.0 - ref["ey"].abs() < POLE)
     if reflection:
         rb, added = ref["rb"], ref["added"]
@@ -63,12 +66,12 @@ def sensitive(name, law, with_screen, reflection=False):
             cos = (rb["dn"] / np.linalg.norm(n)).abs()
             seen = (rb["dn"] != 0) & (rb["t"] > 0)
             near = torch.zeros_like(seen)
-            for w, top in ((rb["su"], image_cases.TEX - 1), (rb["sv"], image_cases.TEX - 1)):
+            for w, top in ((rb["su"], tex_w - 1), (rb["sv"], tex_h - 1)):
                 near = near | (w.abs() < image_cases.BORDER) | ((w - top).abs() < image_cases.BORDER)
             bad = bad | (added & ((rb["on"] & (cos < image_cases.GRAZING)) | (seen & near)))
     bad = bad.numpy().reshape(sc["height"] * sc["width"], -1).any(1).reshape(sc["height"], sc["width"])
     if with_screen:
-        bad = bad | image_cases.sensitive(name, image_cases.reference(name, law, True))
+        bad = bad | image_cases.sensitive(name, image_cases.reference(name, law, True) if stage is None else stage)
     return bad
 
 
@@ -116,12 +119,13 @@ def loss_reference(name, law, with_screen, reflection, weighted=False, detach=No
 
 
 def env_step(channels):
-    """G_env: the largest difference between neighbouring texels of the environment, the seam's pair included."""
-    env = environment(channels).texels.astype(np.float64)
+    """G_env: the largest difference between neighbouring texels of the environment, the seam's pair included (``channels``: of the named
+    cases' environment, or a scene dict with its own ``environment``)."""
+    env = (np.asarray(channels["environment"]) if isinstance(channels, dict) else environment(channels).texels).astype(np.float64)
     return max(np.abs(np.diff(env, axis=0)).max(), np.abs(np.diff(np.concatenate([env, env[:, :1]], axis=1), axis=1)).max())
 
 
-def tolerance(name, law, with_screen):
+def tolerance(name, law, with_screen, stage=None):
     """2^-23 + the screen's term (image_cases.tolerance without its own 2^-23; with a screen) + G_env * delta * Ew / (2 pi sin(theta_min)):
     an exit direction off by delta = RAY_ABS + MATH_ABS moves phi by at most delta / sin(theta) off the pole cut, i.e. u by that times
     Ew / (2 pi) texels, and a texel step changes the bilinear sample by at most G_env, the largest difference between neighbouring texels
@@ -131,7 +135,16 @@ def tolerance(name, law, with_screen):
     that covered both coordinates would have the environment term twice (1.1e-8 more on 1.3e-7).  The term is NOT added: the bound stays
     as set, it is the narrower of the two, and a device image that needed the v share would fail here and be looked at.
     With the reflection a colour is T B(exit) + R1 B(ro, wr) with T <= 1 - R1: the two backgrounds' errors are weighted by factors that
-    sum to at most 1, so the same bound holds."""
+    sum to at most 1, so the same bound holds.
+    A scene dict (tests/image_fuzz_cases.py; ``stage``: its ``image_ref.render``) has an environment of its own extents: the texel
+    factor is max(Ew / 2 pi, Eh / pi), the same number for 16 x 32, and delta is image_cases.FUZZ_DIR + MATH_ABS."""
+    if isinstance(name, dict):
+        eh, ew = np.asarray(name["environment"]).shape[:2]
+        sin_min = math.sqrt(1.0 - (1.0 - POLE) ** 2)
+        tol = 2.0 ** -23 + env_step(name) * (image_cases.FUZZ_DIR + MATH_ABS) * max(ew / (2.0 * math.pi), eh / math.pi) / sin_min
+        if with_screen:
+            tol += image_cases.tolerance(name, stage) - 2.0 ** -23
+        return tol
     sc = image_cases.scene(name)
     G = env_step(sc["texture"].shape[2])
     sin_min = math.sqrt(1.0 - (1.0 - POLE) ** 2)

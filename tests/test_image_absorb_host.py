@@ -49,13 +49,18 @@ def _build(stem, headers):
 _HEADERS = ("drt_image_loss.h", "drt_image.h", "drt_paths.h", "drt_path.h", "drt_shade.h", "drt_traverse.h", "drt_common.h")
 
 
-@pytest.fixture(scope="module")
-def hs():
+def load_hs():
+    """The host build of this file, compiled when a source of it is newer, with its signatures."""
     lib = _build("image_absorb", ("drt_image_absorb.h",) + _HEADERS)
     lib.ia_t_backward.argtypes = [_P, _P, _P, _D, _D, _I, _P, _I64] + [_P] * 7
     lib.ia_view.restype = _D
     lib.ia_view.argtypes = [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _D, _D, _I, _I] + [_P] * 16
     return lib
+
+
+@pytest.fixture(scope="module")
+def hs():
+    return load_hs()
 
 
 @pytest.fixture(scope="module")
@@ -73,8 +78,9 @@ class HostView(clear.HostView):
         super().__init__(hs, name, law, fresnel, weighted)
         self.sigma = cases.sigma(name)
 
-    def run(self, V=None, ior_int=IOR, ior_ext=EXT, sigma=None, want_image=False):
+    def run(self, V=None, ior_int=None, ior_ext=None, sigma=None, want_image=False):
         sc, V = self.sc, self.V if V is None else np.ascontiguousarray(V)
+        ior_int, ior_ext = self.ior_int if ior_int is None else ior_int, self.ior_ext if ior_ext is None else ior_ext
         sigma = np.ascontiguousarray(self.sigma if sigma is None else sigma, np.float64)
         C, n = self.tex.shape[2], len(self.cls)
         grad, g_ior, g_sigma, count = np.zeros_like(V), np.zeros(2), np.zeros(C), np.zeros(1, np.int64)

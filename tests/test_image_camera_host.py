@@ -28,8 +28,8 @@ LAWS = ref_mod.LAWS
 CONTROLS = ("detach_direct", "detach_origin", "detach_T")
 
 
-@pytest.fixture(scope="module")
-def hs():
+def load_hs():
+    """The host build of this file, compiled when a source of it is newer, with its signatures."""
     src = os.path.join(ROOT, "tests", "hostsim", "image_camera.cpp")
     out_dir = os.path.join(ROOT, "tests", "hostsim", "_build")
     so = os.path.join(out_dir, "libimage_camera.so")
@@ -45,6 +45,11 @@ def hs():
     return lib
 
 
+@pytest.fixture(scope="module")
+def hs():
+    return load_hs()
+
+
 def _p(a):
     if a is None:
         return None
@@ -57,32 +62,37 @@ def _cam21(camera_M):
 
 
 class HostView:
-    """One case on the host build with the classes and the tape of the restatement's trace at the fixture's camera held fixed."""
+    """One case on the host build with the classes and the tape of the restatement's trace at the fixture's camera held fixed.  ``name``:
+    a scene of image_cases, or a scene dict of tests/image_fuzz_cases.py with its own IORs, fills, target and weight."""
 
     def __init__(self, hs, name, law, fresnel):
-        self.hs, self.sc, self.law, self.fresnel = hs, image_cases.scene(name), law, fresnel
+        own = isinstance(name, dict)
+        self.hs, self.sc, self.law, self.fresnel = hs, image_cases._scene(name), law, fresnel
         sc = self.sc
+        self.ior_int, self.ior_ext = (sc["ior_int"], sc["ior_ext"]) if own else (IOR, EXT)
         self.F = np.ascontiguousarray(sc["mesh"].faces, np.int32)
         self.V = np.ascontiguousarray(sc["mesh"].vertices, np.float64)
         o, d = image_loss_ref.image_ref.sample_rays(sc["camera_M"][3], sc["camera_M"][2], sc["height"], sc["width"], sc["s"])
-        aux = image_loss_ref.snell_ref.trace(sc["mesh"].faces, torch.tensor(self.V), o, d, IOR, EXT, *law)
+        aux = image_loss_ref.snell_ref.trace(sc["mesh"].faces, torch.tensor(self.V), o, d, self.ior_int, self.ior_ext, *law)
         hit, valid = aux["tape"][0] >= 0, aux["valid"]
         self.cls = np.ascontiguousarray(torch.where(hit, torch.where(valid, 1, 2), 0).numpy(), np.int32)
         self.tape = np.ascontiguousarray(aux["tape"].numpy(), np.int32)
         self.hits = np.ascontiguousarray(aux["hits"].numpy(), np.uint8)
         self.cam21 = _cam21(sc["camera_M"])
-        self.target = cases.target(name, law, fresnel)
-        self.tex = np.ascontiguousarray(sc["texture"], np.float32)
+        self.target = np.ascontiguousarray(sc["target"]) if own else cases.target(name, law, fresnel)
+        self.weight = sc["weight"] if own else None
+        tex = np.asarray(sc["texture"], np.float32)
+        self.tex = np.ascontiguousarray(tex[:, :, None] if tex.ndim == 2 else tex)
         C = self.tex.shape[2]
-        self.void, self.invalid = np.full(C, sc["void"]), np.full(C, sc["invalid"])
+        self.void, self.invalid = (np.ascontiguousarray(np.broadcast_to(np.asarray(sc[k], np.float64), (C,))) for k in ("void", "invalid"))
 
     def run(self, cam21=None):
         sc = self.sc
         cam21 = self.cam21 if cam21 is None else np.ascontiguousarray(cam21, np.float64)
         g_cam, count, through = np.zeros(21), np.zeros(1, np.int64), np.zeros(1, np.int64)
         loss = self.hs.ic_view(_p(cam21), sc["height"], sc["width"], sc["s"], _p(sc["screen"].packed()), _p(self.tex), self.tex.shape[0], self.tex.shape[1],
-                               self.tex.shape[2], _p(self.F), _p(self.V), IOR, EXT, int(self.law[2] == "snell"), int(self.fresnel), _p(self.cls), _p(self.tape),
-                               _p(self.hits), _p(self.void), _p(self.invalid), _p(self.target), None, _p(g_cam), _p(count), _p(through))
+                               self.tex.shape[2], _p(self.F), _p(self.V), self.ior_int, self.ior_ext, int(self.law[2] == "snell"), int(self.fresnel), _p(self.cls),
+                               _p(self.tape), _p(self.hits), _p(self.void), _p(self.invalid), _p(self.target), _p(self.weight), _p(g_cam), _p(count), _p(through))
         return dict(loss=loss, g_kinv=g_cam[:9].reshape(3, 3), g_rinv=g_cam[9:].reshape(3, 4), count=int(count[0]), through=int(through[0]))
 
 

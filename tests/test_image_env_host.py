@@ -24,8 +24,8 @@ _P, _I64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 EH, EW = image_env_cases.EH, image_env_cases.EW
 
 
-@pytest.fixture(scope="module")
-def hs():
+def load_hs():
+    """The host build of this file, compiled when a source of it is newer, with its signatures."""
     src = os.path.join(ROOT, "tests", "hostsim", "image_env.cpp")
     out_dir = os.path.join(ROOT, "tests", "hostsim", "_build")
     so = os.path.join(out_dir, "libimage_env.so")
@@ -47,6 +47,11 @@ def hs():
     lib.env_loss_view.restype = ctypes.c_double
     lib.env_loss_view.argtypes = [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I] + [_P] * 11
     return lib
+
+
+@pytest.fixture(scope="module")
+def hs():
+    return load_hs()
 
 
 def _p(a):
@@ -274,30 +279,41 @@ def test_the_reflection_term_against_the_restatement(hs, with_screen):
 
 
 # ---- the photometric loss and its adjoint ------------------------------------------------------------------------------------------------
+def host_loss_of(hs, sc, law, with_screen, reflection, fwd, texels, rotation, target, weight, ii, ie):
+    """The header's loss, gradients, count and image of a scene dict (one of image_cases, or one of tests/image_fuzz_cases.py with its own
+    texture and environment extents), on the classes, tape and occlusion verdicts of ``fwd`` (``image_env_ref.loss_forward``'s dict)."""
+    mesh = sc["mesh"]
+    faces, verts = np.ascontiguousarray(mesh.faces, dtype=np.int32), np.ascontiguousarray(mesh.vertices, dtype=np.float64)
+    cam = np.ascontiguousarray(np.concatenate([np.asarray(sc["camera_M"][3]).reshape(-1), np.asarray(sc["camera_M"][2])[:3, :].reshape(-1)]))
+    tex = np.asarray(sc["texture"], np.float32)
+    tex = np.ascontiguousarray(tex[:, :, None] if tex.ndim == 2 else tex)
+    texels = np.ascontiguousarray(texels, dtype=np.float32)
+    C = tex.shape[2]
+    gV, g_ior, count = np.zeros_like(verts), np.zeros(2), np.zeros(1, np.int64)
+    image = np.zeros((sc["height"], sc["width"], C), np.float32)
+    invalid = np.ascontiguousarray(np.broadcast_to(np.asarray(sc["invalid"], np.float64), (C,)))
+    loss = hs.env_loss_view(_p(cam), sc["height"], sc["width"], sc["s"], _p(sc["screen"].packed()) if with_screen else None, _p(tex) if with_screen else None,
+                            tex.shape[0], tex.shape[1], C, _p(texels), texels.shape[0], texels.shape[1], _p(np.ascontiguousarray(rotation, dtype=np.float64)), _p(faces),
+                            _p(verts), len(faces),
+                            ii, ie, int(law[2] == "snell"), int(reflection), _p(np.ascontiguousarray(fwd["cls"].numpy(), dtype=np.int32)),
+                            _p(np.ascontiguousarray(fwd["tape"].numpy(), dtype=np.int32)), _p(np.ascontiguousarray(fwd["hits"].numpy(), dtype=np.uint8)),
+                            _p(np.ascontiguousarray(fwd["seen"].numpy(), dtype=np.uint8)), _p(invalid), _p(np.ascontiguousarray(target)), _p(weight), _p(gV), _p(g_ior),
+                            _p(count), _p(image))
+    return dict(loss=loss, grad_V=gV, g_int=g_ior[0], g_ext=g_ior[1], count=int(count[0]), image=image)
+
+
 def host_loss(hs, name, law, with_screen, reflection, weighted=False, ior=None):
     """The header's loss, gradients, count and image of a case, on the restatement's classes, tape and occlusion verdicts."""
     import image_loss_cases
     from conftest import IOR
     sc = image_cases.scene(name)
     ref = image_env_cases.loss_reference(name, law, with_screen, reflection, weighted)
-    fwd = ref["fwd"]
     env = image_env_cases.environment(sc["texture"].shape[2])
-    mesh = sc["mesh"]
-    faces, verts = np.ascontiguousarray(mesh.faces, dtype=np.int32), np.ascontiguousarray(mesh.vertices, dtype=np.float64)
-    cam = np.ascontiguousarray(np.concatenate([np.asarray(sc["camera_M"][3]).reshape(-1), np.asarray(sc["camera_M"][2])[:3, :].reshape(-1)]))
-    C = sc["texture"].shape[2]
-    gV, g_ior, count = np.zeros_like(verts), np.zeros(2), np.zeros(1, np.int64)
-    image = np.zeros((sc["height"], sc["width"], C), np.float32)
-    target = image_env_cases.loss_target(name, law, with_screen, reflection)
     weight = image_loss_cases.half_weight(name) if weighted else None
     ii, ie = ior if ior is not None else (IOR, image_cases.EXT)
-    loss = hs.env_loss_view(_p(cam), sc["height"], sc["width"], sc["s"], _p(sc["screen"].packed()) if with_screen else None, _p(sc["texture"]) if with_screen else None,
-                            image_cases.TEX, image_cases.TEX, C, _p(env.texels), EH, EW, _p(np.ascontiguousarray(env.rotation)), _p(faces), _p(verts), len(faces),
-                            ii, ie, int(law[2] == "snell"), int(reflection), _p(np.ascontiguousarray(fwd["cls"].numpy(), dtype=np.int32)),
-                            _p(np.ascontiguousarray(fwd["tape"].numpy(), dtype=np.int32)), _p(np.ascontiguousarray(fwd["hits"].numpy(), dtype=np.uint8)),
-                            _p(np.ascontiguousarray(fwd["seen"].numpy(), dtype=np.uint8)), _p(np.full(C, sc["invalid"])), _p(target), _p(weight), _p(gV), _p(g_ior),
-                            _p(count), _p(image))
-    return dict(loss=loss, grad_V=gV, g_int=g_ior[0], g_ext=g_ior[1], count=int(count[0]), image=image), ref
+    got = host_loss_of(hs, sc, law, with_screen, reflection, ref["fwd"], env.texels, env.rotation, image_env_cases.loss_target(name, law, with_screen, reflection), weight,
+                       ii, ie)
+    return got, ref
 
 
 LOSS_CASES = [("wide", image_cases.LAWS[1], True, True), ("wide", image_cases.LAWS[1], False, True), ("v5", image_cases.LAWS[2], True, True),

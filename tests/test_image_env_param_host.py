@@ -27,8 +27,8 @@ EH, EW = cases.EH, cases.EW
 LAWS = image_cases.LAWS
 
 
-@pytest.fixture(scope="module")
-def hs():
+def load_hs():
+    """The host build of this file, compiled when a source of it is newer, with its signatures."""
     src = os.path.join(ROOT, "tests", "hostsim", "image_env_param.cpp")
     out_dir = os.path.join(ROOT, "tests", "hostsim", "_build")
     so = os.path.join(out_dir, "libimage_env_param.so")
@@ -44,11 +44,40 @@ def hs():
     return lib
 
 
+@pytest.fixture(scope="module")
+def hs():
+    return load_hs()
+
+
 def _p(a):
     if a is None:
         return None
     assert a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(_P)
+
+
+def host_view_of(hs, sc, law, with_screen, reflection, sm, texels, rot, target, weight, ior_int, ior_ext, grads=True):
+    """The header's loss, texel gradient [Eh, Ew, C], rotation partials [3, 3] and read statistics of a scene dict (one of image_cases, or
+    one of tests/image_fuzz_cases.py with its own texture and environment extents) on ``sm``, image_env_param_ref.samples' dict."""
+    mesh = sc["mesh"]
+    faces, verts = np.ascontiguousarray(mesh.faces, dtype=np.int32), np.ascontiguousarray(mesh.vertices, dtype=np.float64)
+    cam = np.ascontiguousarray(np.concatenate([np.asarray(sc["camera_M"][3]).reshape(-1), np.asarray(sc["camera_M"][2])[:3, :].reshape(-1)]))
+    tex = np.asarray(sc["texture"], np.float32)
+    tex = np.ascontiguousarray(tex[:, :, None] if tex.ndim == 2 else tex)
+    C = tex.shape[2]
+    texels, rot = np.ascontiguousarray(texels, dtype=np.float32), np.ascontiguousarray(rot, dtype=np.float64)
+    eh, ew = texels.shape[:2]
+    g_env, g_R, stats = (np.zeros((eh, ew, C)), np.zeros((3, 3)), np.zeros(5)) if grads else (None, None, None)
+    seen = sm["refl"]["seen"] if reflection else torch.zeros(len(sm["cls"]), dtype=torch.bool)
+    invalid = np.ascontiguousarray(np.broadcast_to(np.asarray(sc["invalid"], np.float64), (C,)))
+    loss = hs.env_param_view(_p(cam), sc["height"], sc["width"], sc["s"], _p(sc["screen"].packed()) if with_screen else None, _p(tex) if with_screen else None,
+                             tex.shape[0], tex.shape[1], C, _p(texels), eh, ew, _p(rot), _p(faces), _p(verts), len(faces), ior_int, ior_ext,
+                             int(law[2] == "snell"), int(reflection), _p(np.ascontiguousarray(sm["cls"].numpy(), dtype=np.int32)),
+                             _p(np.ascontiguousarray(sm["out_o"].numpy())), _p(np.ascontiguousarray(sm["out_d"].numpy())), _p(np.ascontiguousarray(sm["T"].numpy())),
+                             _p(np.ascontiguousarray(sm["tape"][0].numpy(), dtype=np.int32)), _p(np.ascontiguousarray(seen.numpy(), dtype=np.uint8)),
+                             _p(invalid), _p(np.ascontiguousarray(target)), _p(weight),
+                             _p(g_env), _p(g_R), _p(stats))
+    return dict(loss=loss, g_env=g_env, g_R=g_R, stats=stats)
 
 
 def host_view(hs, name, law, with_screen, reflection, weighted=False, env=None, R=None, grads=True):
@@ -57,23 +86,9 @@ def host_view(hs, name, law, with_screen, reflection, weighted=False, env=None, 
     sc = image_cases.scene(name)
     sm = cases.samples(name, law, with_screen, reflection)
     _, e = cases.case_args(name, with_screen)
-    C = sc["texture"].shape[2]
-    mesh = sc["mesh"]
-    faces, verts = np.ascontiguousarray(mesh.faces, dtype=np.int32), np.ascontiguousarray(mesh.vertices, dtype=np.float64)
-    cam = np.ascontiguousarray(np.concatenate([np.asarray(sc["camera_M"][3]).reshape(-1), np.asarray(sc["camera_M"][2])[:3, :].reshape(-1)]))
-    texels = np.ascontiguousarray(e.texels if env is None else env, dtype=np.float32)
-    rot = np.ascontiguousarray(e.rotation if R is None else R, dtype=np.float64)
-    g_env, g_R, stats = (np.zeros((EH, EW, C)), np.zeros((3, 3)), np.zeros(5)) if grads else (None, None, None)
-    seen = sm["refl"]["seen"] if reflection else torch.zeros(len(sm["cls"]), dtype=torch.bool)
     weight = image_loss_cases.half_weight(name) if weighted else None
-    loss = hs.env_param_view(_p(cam), sc["height"], sc["width"], sc["s"], _p(sc["screen"].packed()) if with_screen else None, _p(sc["texture"]) if with_screen else None,
-                             image_cases.TEX, image_cases.TEX, C, _p(texels), EH, EW, _p(rot), _p(faces), _p(verts), len(faces), image_cases.IOR, image_cases.EXT,
-                             int(law[2] == "snell"), int(reflection), _p(np.ascontiguousarray(sm["cls"].numpy(), dtype=np.int32)),
-                             _p(np.ascontiguousarray(sm["out_o"].numpy())), _p(np.ascontiguousarray(sm["out_d"].numpy())), _p(np.ascontiguousarray(sm["T"].numpy())),
-                             _p(np.ascontiguousarray(sm["tape"][0].numpy(), dtype=np.int32)), _p(np.ascontiguousarray(seen.numpy(), dtype=np.uint8)),
-                             _p(np.full(C, sc["invalid"], dtype=np.float64)), _p(image_env_cases.loss_target(name, law, with_screen, reflection)), _p(weight),
-                             _p(g_env), _p(g_R), _p(stats))
-    return dict(loss=loss, g_env=g_env, g_R=g_R, stats=stats)
+    return host_view_of(hs, sc, law, with_screen, reflection, sm, e.texels if env is None else env, e.rotation if R is None else R,
+                        image_env_cases.loss_target(name, law, with_screen, reflection), weight, image_cases.IOR, image_cases.EXT, grads)
 
 
 # `v5` and `v41` have three channels, `wide` one

@@ -26,8 +26,8 @@ EXT = cases.EXT
 LOSS_REL = cases.LOSS_REL
 
 
-@pytest.fixture(scope="module")
-def hs():
+def load_hs():
+    """The host build of this file, compiled when a source of it is newer, with its signatures."""
     src = os.path.join(ROOT, "tests", "hostsim", "image_loss.cpp")
     out_dir = os.path.join(ROOT, "tests", "hostsim", "_build")
     so = os.path.join(out_dir, "libimage_loss.so")
@@ -43,6 +43,11 @@ def hs():
     return lib
 
 
+@pytest.fixture(scope="module")
+def hs():
+    return load_hs()
+
+
 def _p(a):
     if a is None:
         return None
@@ -55,27 +60,32 @@ def _cam21(camera_M):
 
 
 class HostView:
-    """One case on the host build with the classes and the tape of the restatement's forward at conftest.IOR held fixed."""
+    """One case on the host build with the classes and the tape of the restatement's forward at conftest.IOR held fixed.  ``name``: a
+    scene of image_cases, or a scene dict of tests/image_fuzz_cases.py with its own IORs, fills, target and weight."""
 
     def __init__(self, hs, name, law, fresnel, weighted=False):
-        self.hs, self.sc, self.law, self.fresnel = hs, image_cases.scene(name), law, fresnel
+        own = isinstance(name, dict)
+        self.hs, self.sc, self.law, self.fresnel = hs, image_cases._scene(name), law, fresnel
         sc = self.sc
+        self.ior_int, self.ior_ext = (sc["ior_int"], sc["ior_ext"]) if own else (IOR, EXT)
         self.F = np.ascontiguousarray(sc["mesh"].faces, np.int32)
         self.V = np.ascontiguousarray(sc["mesh"].vertices, np.float64)
         o, d = image_loss_ref.image_ref.sample_rays(sc["camera_M"][3], sc["camera_M"][2], sc["height"], sc["width"], sc["s"])
-        aux = image_loss_ref.snell_ref.trace(sc["mesh"].faces, torch.tensor(self.V), o, d, IOR, EXT, *law)
+        aux = image_loss_ref.snell_ref.trace(sc["mesh"].faces, torch.tensor(self.V), o, d, self.ior_int, self.ior_ext, *law)
         hit, valid = aux["tape"][0] >= 0, aux["valid"]
         self.cls = np.ascontiguousarray(torch.where(hit, torch.where(valid, 1, 2), 0).numpy(), np.int32)
         self.tape = np.ascontiguousarray(aux["tape"].numpy(), np.int32)
         self.hits = np.ascontiguousarray(aux["hits"].numpy(), np.uint8)
-        self.target = cases.target(name, law, fresnel)
-        self.weight = cases.half_weight(name) if weighted else None
-        self.tex = np.ascontiguousarray(sc["texture"], np.float32)
+        self.target = np.ascontiguousarray(sc["target"]) if own else cases.target(name, law, fresnel)
+        self.weight = sc["weight"] if own else cases.half_weight(name) if weighted else None
+        tex = np.asarray(sc["texture"], np.float32)
+        self.tex = np.ascontiguousarray(tex[:, :, None] if tex.ndim == 2 else tex)
         C = self.tex.shape[2]
-        self.void, self.invalid = np.full(C, sc["void"]), np.full(C, sc["invalid"])
+        self.void, self.invalid = (np.ascontiguousarray(np.broadcast_to(np.asarray(sc[k], np.float64), (C,))) for k in ("void", "invalid"))
 
-    def run(self, V=None, ior_int=IOR, ior_ext=EXT, want_image=False):
+    def run(self, V=None, ior_int=None, ior_ext=None, want_image=False):
         sc, V = self.sc, self.V if V is None else np.ascontiguousarray(V)
+        ior_int, ior_ext = self.ior_int if ior_int is None else ior_int, self.ior_ext if ior_ext is None else ior_ext
         grad, g_ior, count = np.zeros_like(V), np.zeros(2), np.zeros(1, np.int64)
         image = np.empty((sc["height"], sc["width"], self.tex.shape[2]), np.float32) if want_image else None
         loss = self.hs.il_view(_p(_cam21(sc["camera_M"])), sc["height"], sc["width"], sc["s"], _p(sc["screen"].packed()), _p(self.tex), self.tex.shape[0],

@@ -23,8 +23,8 @@ _P, _D, _I = ctypes.c_void_p, ctypes.c_double, ctypes.c_int
 LAWS = ref_mod.LAWS
 
 
-@pytest.fixture(scope="module")
-def hs():
+def load_hs():
+    """The host build of this file, compiled when a source of it is newer, with its signatures."""
     src = os.path.join(ROOT, "tests", "hostsim", "image_screen.cpp")
     out_dir = os.path.join(ROOT, "tests", "hostsim", "_build")
     so = os.path.join(out_dir, "libimage_screen.so")
@@ -40,6 +40,11 @@ def hs():
     return lib
 
 
+@pytest.fixture(scope="module")
+def hs():
+    return load_hs()
+
+
 def _p(a):
     if a is None:
         return None
@@ -48,18 +53,24 @@ def _p(a):
 
 
 class HostView:
-    """One case on the host build with the restatement's constants (classes, rays, throughputs) handed in."""
+    """One case on the host build with the restatement's constants (classes, rays, throughputs) handed in.  ``name``: a scene of
+    image_cases, or a scene dict of tests/image_fuzz_cases.py with its own IORs, fills, target and weight."""
 
     def __init__(self, hs, name, law, fresnel):
-        self.hs, self.sc = hs, image_cases.scene(name)
-        const = ref_mod.constants(name, law, fresnel)
+        own = isinstance(name, dict)
+        self.hs, self.sc = hs, image_cases._scene(name)
+        sc = self.sc
+        const = ref_mod.trace(sc["mesh"].faces, sc["mesh"].vertices, sc["camera_M"], sc["height"], sc["width"], sc["s"], law, fresnel, sc["ior_int"],
+                              sc["ior_ext"]) if own else ref_mod.constants(name, law, fresnel)
         self.cls = np.ascontiguousarray(const["cls"].numpy(), np.int32)
         self.o, self.d, self.T = (np.ascontiguousarray(const[k].numpy(), np.float64) for k in ("o", "d", "T"))
-        self.P = np.ascontiguousarray(ref_mod.pose(name).numpy())
-        self.tex = np.ascontiguousarray(self.sc["texture"], np.float32)
-        self.target = cases.target(name, law, fresnel)
+        self.P = np.ascontiguousarray((ref_mod.rows_of(sc["screen"]) if own else ref_mod.pose(name)).numpy())
+        tex = np.asarray(sc["texture"], np.float32)
+        self.tex = np.ascontiguousarray(tex[:, :, None] if tex.ndim == 2 else tex)
+        self.target = np.ascontiguousarray(sc["target"]) if own else cases.target(name, law, fresnel)
+        self.weight = sc["weight"] if own else None
         C = self.tex.shape[2]
-        self.void, self.invalid = np.full(C, self.sc["void"]), np.full(C, self.sc["invalid"])
+        self.void, self.invalid = (np.ascontiguousarray(np.broadcast_to(np.asarray(sc[k], np.float64), (C,))) for k in ("void", "invalid"))
 
     def run(self, P=None, tex=None):
         sc = self.sc
@@ -67,7 +78,7 @@ class HostView:
         tex = self.tex if tex is None else np.ascontiguousarray(tex, np.float32)
         g_screen, g_tex, count = np.zeros(9), np.zeros(tex.shape, np.float64), np.zeros(1, np.int64)
         loss = self.hs.is_view(sc["height"], sc["width"], sc["s"], _p(P.reshape(-1)), _p(tex), tex.shape[0], tex.shape[1], tex.shape[2], _p(self.cls), _p(self.o),
-                               _p(self.d), _p(self.T), _p(self.void), _p(self.invalid), _p(self.target), None, _p(g_screen), _p(g_tex), _p(count))
+                               _p(self.d), _p(self.T), _p(self.void), _p(self.invalid), _p(self.target), _p(self.weight), _p(g_screen), _p(g_tex), _p(count))
         return dict(loss=loss, g_screen=g_screen.reshape(3, 3), g_texture=g_tex, count=int(count[0]))
 
 

@@ -34,8 +34,8 @@ EH, EW = image_env_cases.EH, image_env_cases.EW
 PAIR = ("v5", "v41")
 
 
-@pytest.fixture(scope="module")
-def hv():
+def load_hv():
+    """The host build of this file, compiled when a source of it is newer, with its signatures."""
     src = os.path.join(ROOT, "tests", "hostsim", "image_views_env.cpp")
     out_dir = os.path.join(ROOT, "tests", "hostsim", "_build")
     so = os.path.join(out_dir, "libimage_views_env.so")
@@ -51,6 +51,11 @@ def hv():
     lib.ive_views_loss.restype = _D
     lib.ive_views_loss.argtypes = [_P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _D, _D, _I, _I] + [_P] * 10
     return lib
+
+
+@pytest.fixture(scope="module")
+def hv():
+    return load_hv()
 
 
 def _p(a):

@@ -22,8 +22,8 @@ _P, _I64, _D, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_in
 EXT = cases.EXT
 
 
-@pytest.fixture(scope="module")
-def hv():
+def load_hv():
+    """The host build of this file, compiled when a source of it is newer, with its signatures."""
     src = os.path.join(ROOT, "tests", "hostsim", "image_views.cpp")
     out_dir = os.path.join(ROOT, "tests", "hostsim", "_build")
     so = os.path.join(out_dir, "libimage_views.so")
@@ -39,6 +39,11 @@ def hv():
     lib.iv_views_loss.restype = _D
     lib.iv_views_loss.argtypes = [_P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _D, _D, _I, _I] + [_P] * 10
     return lib
+
+
+@pytest.fixture(scope="module")
+def hv():
+    return load_hv()
 
 
 def _p(a):
