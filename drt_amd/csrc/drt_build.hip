@@ -747,6 +747,35 @@ int drt_bvh_sorted_faces(drt_scene_t* s, int32_t* d_order, void* stream) {
     return DRT_OK;
 }
 
+int drt_bvh_export(drt_scene_t* s, int what, void* d_out, int64_t bytes, void* stream) {
+    CHECK_BUILT(s);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = s->n_faces, inner = n > 1 ? n - 1 : 1;
+    const void* src = nullptr;
+    int64_t size = 0;
+    switch (what) {
+        case DRT_BVH_KEYS:         src = s->keys[s->sorted_buf]; size = (int64_t)sizeof(uint32_t) * n; break;
+        case DRT_BVH_ORDER:        src = s->idx[s->sorted_buf]; size = (int64_t)sizeof(uint32_t) * n; break;
+        case DRT_BVH_NODES:        src = s->nodes; size = (int64_t)sizeof(Node) * inner; break;
+        case DRT_BVH_PARENT_INNER: src = s->parent_inner; size = (int64_t)sizeof(int32_t) * inner; break;
+        case DRT_BVH_PARENT_LEAF:  src = s->parent_leaf; size = (int64_t)sizeof(int32_t) * n; break;
+        case DRT_BVH_RANGE_LO:     src = s->range_lo; size = (int64_t)sizeof(int32_t) * inner; break;
+        case DRT_BVH_RANGE_HI:     src = s->range_hi; size = (int64_t)sizeof(int32_t) * inner; break;
+        case DRT_BVH_WIDE:         src = s->wide; size = (int64_t)sizeof(Node4Q) * inner; break;
+        case DRT_BVH_TRIS:         src = s->tris; size = (int64_t)sizeof(TriRec) * n; break;
+        case DRT_BVH_TRIS_FLAT:    src = s->tris_flat; size = (int64_t)sizeof(TriRec) * n; break;
+        case DRT_BVH_SLOT_OF_FACE: src = s->slot_of_face; size = (int64_t)sizeof(int32_t) * n; break;
+        case DRT_BVH_PARAMS:       src = s->params; size = (int64_t)sizeof(BuildParams); break;
+        default: return fail(DRT_E_INVALID, "drt_bvh_export: unknown array %d", what);
+    }
+    if (n == 0 && what != DRT_BVH_PARAMS) size = 0;      // an empty mesh has no tree (and its BuildParams are those of the last non-empty build)
+    if (bytes != size) return fail(DRT_E_INVALID, "drt_bvh_export: array %d holds %lld bytes, not %lld", what, (long long)size, (long long)bytes);
+    if (size && !d_out) return fail(DRT_E_INVALID, "d_out is null");
+    { int rc = wait_build(s, st); if (rc) return rc; }
+    if (size) HIP_TRY(hipMemcpyAsync(d_out, src, (size_t)size, hipMemcpyDeviceToDevice, st));
+    return DRT_OK;
+}
+
 int drt_tree_mode(drt_scene_t* s, int mode, int rebuild_every) {
     CHECK_SCENE(s);
     if (mode < 0 || mode > 2 || rebuild_every < 1) return fail(DRT_E_INVALID, "tree mode 0..2, rebuild_every >= 1");

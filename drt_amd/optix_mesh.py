@@ -196,6 +196,43 @@ class optix_mesh:
             _lib.check(_lib.lib().drt_bvh_sorted_faces(self._h, out.data_ptr(), _stream()))
         return out
 
+    # layouts of drt_lbvh.h Node, Node4Q, drt_tri.h TriRec and drt_scene.h BuildParams (with its MortonPlan)
+    NODE_DTYPE = [(k, "<f4") for k in ("c0lox", "c0hix", "c0loy", "c0hiy", "c1lox", "c1hix", "c1loy", "c1hiy", "c0loz", "c0hiz", "c1loz", "c1hiz")] + \
+                 [(k, "<i4") for k in ("child0", "child1", "pad0", "pad1")]
+    NODE4Q_DTYPE = [(k, "<f4") for k in ("ox", "oy", "oz", "sx", "sy", "sz")] + \
+                   [(k, "u1", (4,)) for k in ("qlox", "qloy", "qloz", "qhix", "qhiy", "qhiz")] + [("child", "<i4", (4,))]
+    TRIREC_DTYPE = [("v0", "<f4", (3,)), ("face", "<i4"), ("e1", "<f4", (3,)), ("margin", "<f4"), ("e2", "<f4", (3,)), ("pad1", "<f4")]
+    PARAMS_DTYPE = dict(names=["lo", "inv", "pad", "reserved", "axis", "pos", "bits", "plan_pad"], offsets=[0, 12, 24, 28, 32, 62, 92, 95], itemsize=100,
+                        formats=[("<f4", (3,)), ("<f4", (3,)), "<f4", "<i4", ("u1", (30,)), ("u1", (30,)), ("u1", (3,)), ("u1", (3,))])   # (+ 2 bytes of padding)
+    TREE_ARRAYS = ("keys", "order", "nodes", "parent_inner", "parent_leaf", "range_lo", "range_hi", "wide", "tris", "tris_flat", "slot_of_face", "params")
+
+    def tree_arrays(self, names=None):
+        """{name: numpy array} of the build's arrays (include/drt_hip.h: drt_bvh_export; ``names``: a subset of TREE_ARRAYS);
+        synchronises.  ``nodes``, ``wide``, ``tris`` / ``tris_flat`` and ``params`` are structured (NODE_DTYPE, NODE4Q_DTYPE, TRIREC_DTYPE,
+        PARAMS_DTYPE; byte k of a Node4Q bound word is child k).  With F faces the node arrays have max(F - 1, 1) entries.
+        ``keys`` are the sorted keys of the last FULL build: after a kept-topology update in tree mode 1 they are stale (they belong to
+        the vertices of that build), in tree mode 2 they are undefined."""
+        import numpy as np
+        assert self.builded, "update_mesh must be called first"
+        n = self.n_faces
+        inner = max(n - 1, 1) if n else 0
+        shape = {"keys": (np.uint32, n), "order": (np.uint32, n), "nodes": (np.dtype(self.NODE_DTYPE), inner), "parent_inner": (np.int32, inner),
+                 "parent_leaf": (np.int32, n), "range_lo": (np.int32, inner), "range_hi": (np.int32, inner), "wide": (np.dtype(self.NODE4Q_DTYPE), inner),
+                 "tris": (np.dtype(self.TRIREC_DTYPE), n), "tris_flat": (np.dtype(self.TRIREC_DTYPE), n), "slot_of_face": (np.int32, n),
+                 "params": (np.dtype(self.PARAMS_DTYPE), 1)}
+        out = {}
+        with _on(self.device):
+            for name in (self.TREE_ARRAYS if names is None else names):
+                dtype, count = shape[name]
+                nbytes = np.dtype(dtype).itemsize * count
+                buf = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.device}")
+                _lib.check(_lib.lib().drt_bvh_export(self._h, self.TREE_ARRAYS.index(name), buf.data_ptr(), nbytes, _stream()))
+                out[name] = buf.cpu().numpy().view(dtype)
+        out_params = out.get("params")
+        if out_params is not None:
+            out["params"] = out_params[0]
+        return out
+
     STAGES = ("build", "cull", "trace1", "shade1", "trace2", "shade2", "trace3", "finish", "collect", "backward", "loss_bwd_fused", "raster", "fill", "path")
 
     def profile_enable(self, on=1):

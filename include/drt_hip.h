@@ -113,6 +113,18 @@ int drt_tree_mode(drt_scene_t* s, int mode, int rebuild_every);
 /* Diagnostic: the scene box the last build derived from the vertices -- out7 = lo[3], 1/extent[3], leaf padding (float32; the margin of
  * the hit-point test is half the padding); host-synchronising.  What a replayed capture of an update must reproduce. */
 int drt_build_params(drt_scene_t* s, float* out7, void* stream);
+/* Diagnostic: one array of the last build, copied device -> device into d_out on `stream` (after the build; not host-synchronising).
+ * `bytes` must be exactly the array's size (F faces, I = max(F - 1, 1) inner nodes), else DRT_E_INVALID and nothing is written:
+ * KEYS uint32 [F] and ORDER uint32 [F] (sorted Morton keys, face id per slot), NODES 64 B x I (binary nodes), PARENT_INNER int32 [I],
+ * PARENT_LEAF int32 [F] (2 * parent + child slot), RANGE_LO / RANGE_HI int32 [I], WIDE 64 B x I (quantised 4-wide nodes; entries of
+ * subtrees that fit one leaf are never written, except the root's), TRIS / TRIS_FLAT 48 B x F (records in slot order / in the order the projection pass
+ * reads), SLOT_OF_FACE int32 [F], PARAMS 100 B (scene box, padding, Morton plan).  KEYS are those of the last FULL build: stale after a
+ * kept-topology update in tree mode 1, undefined in mode 2.  An empty mesh has empty arrays. */
+enum {
+    DRT_BVH_KEYS = 0, DRT_BVH_ORDER = 1, DRT_BVH_NODES = 2, DRT_BVH_PARENT_INNER = 3, DRT_BVH_PARENT_LEAF = 4, DRT_BVH_RANGE_LO = 5,
+    DRT_BVH_RANGE_HI = 6, DRT_BVH_WIDE = 7, DRT_BVH_TRIS = 8, DRT_BVH_TRIS_FLAT = 9, DRT_BVH_SLOT_OF_FACE = 10, DRT_BVH_PARAMS = 11
+};
+int drt_bvh_export(drt_scene_t* s, int what, void* d_out, int64_t bytes, void* stream);
 
 /* ---- B2: Scene.render_transparent, DiffRender.py:420-432 (trace2 :537-546, Dintersect
  * :492-501, refract_ray :503-535) -------------------------------------------------------

@@ -28,13 +28,17 @@ struct HsScene {
     std::vector<TriRec> tris;
     std::vector<int32_t> parent_inner, parent_leaf;
     std::vector<uint32_t> keys, idx;
+    std::vector<TriRec> tris_flat;           // the records in face order (what k_tri_flat writes after an update_mesh)
+    std::vector<int32_t> slot_of_face;
+    struct Params { float lo[3], inv[3], pad; int32_t reserved; MortonPlan plan; } params{};   // drt_scene.h BuildParams
     float pad = 0.f;
     int height = 0;
 };
 
 static f3 vert(const HsScene& s, int32_t i) { return f3{s.verts[3 * i], s.verts[3 * i + 1], s.verts[3 * i + 2]}; }
 
-static void build(HsScene& s) {
+// `drop`: low key bits cleared before the sort, as k_morton does for meshes that take the fused sort (rebuild_impl: 6), else 0
+static void build(HsScene& s, int drop = 0) {
     const int n = (int)(s.faces.size() / 3);
     const int64_t nv = (int64_t)s.verts.size() / 3;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -48,8 +52,9 @@ static void build(HsScene& s) {
     s.pad = pad_for_extent(fmaxf(ex, fmaxf(ey, ez)));
     std::vector<uint32_t> key(n);
     const MortonPlan plan = morton_plan(ex, ey, ez);
+    s.params = HsScene::Params{{lo[0], lo[1], lo[2]}, {inv.x, inv.y, inv.z}, s.pad, 0, plan};
     for (int i = 0; i < n; ++i)
-        key[i] = morton_key(vert(s, s.faces[3 * i]), vert(s, s.faces[3 * i + 1]), vert(s, s.faces[3 * i + 2]), f3{lo[0], lo[1], lo[2]}, inv, plan);
+        key[i] = morton_key(vert(s, s.faces[3 * i]), vert(s, s.faces[3 * i + 1]), vert(s, s.faces[3 * i + 2]), f3{lo[0], lo[1], lo[2]}, inv, plan) & ~((1u << drop) - 1u);
     s.idx.resize(n);
     std::iota(s.idx.begin(), s.idx.end(), 0u);
     std::stable_sort(s.idx.begin(), s.idx.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
@@ -63,6 +68,8 @@ static void build(HsScene& s) {
     s.range_hi.assign(inner, n - 1);
     s.wide.assign(inner, Node4Q{});
     s.tris.resize(n);
+    s.tris_flat.resize(n);
+    s.slot_of_face.assign(n, -1);
     if (n == 0) return;
     if (n == 1) {
         node_set_child_box(s.nodes[0], 0, box_empty());
@@ -83,6 +90,8 @@ static void build(HsScene& s) {
         const int32_t face = (int32_t)s.idx[k];
         const f3 a = vert(s, s.faces[3 * face]), b = vert(s, s.faces[3 * face + 1]), c = vert(s, s.faces[3 * face + 2]);
         s.tris[k] = make_tri(a, b, c, face, hit_margin(s.pad));
+        s.tris_flat[face] = s.tris[k];
+        s.slot_of_face[face] = k;
         Box box = box_of_tri(a, b, c, s.pad);
         int32_t link = s.parent_leaf[k];
         while (link >= 0) {
@@ -123,6 +132,42 @@ void* hs_create(const int32_t* faces, int64_t n_faces, const float* verts, int64
     s->verts.assign(verts, verts + 3 * n_verts);
     build(*s);
     return s;
+}
+void* hs_create_ex(const int32_t* faces, int64_t n_faces, const float* verts, int64_t n_verts, int drop) {
+    HsScene* s = new HsScene();
+    s->faces.assign(faces, faces + 3 * n_faces);
+    s->verts.assign(verts, verts + 3 * n_verts);
+    build(*s, drop);
+    return s;
+}
+int hs_leaf_bits() { return kLeafBits; }
+// One array of the build, selected and sized as drt_bvh_export does (include/drt_hip.h DRT_BVH_*): 0 keys, 1 order, 2 nodes, 3 parent_inner,
+// 4 parent_leaf, 5 range_lo, 6 range_hi, 7 wide, 8 tris, 9 tris_flat (face order), 10 slot_of_face, 11 params.  Returns 0, or -1 (and writes
+// nothing) when `bytes` is not the array's size.
+int hs_export(void* h, int what, void* out, int64_t bytes) {
+    HsScene* s = (HsScene*)h;
+    const void* src = nullptr;
+    int64_t size = 0;
+    auto pick = [&](const auto& v) { src = v.data(); size = (int64_t)(v.size() * sizeof(v[0])); };
+    switch (what) {
+        case 0: pick(s->keys); break;
+        case 1: pick(s->idx); break;
+        case 2: pick(s->nodes); break;
+        case 3: pick(s->parent_inner); break;
+        case 4: pick(s->parent_leaf); break;
+        case 5: pick(s->range_lo); break;
+        case 6: pick(s->range_hi); break;
+        case 7: pick(s->wide); break;
+        case 8: pick(s->tris); break;
+        case 9: pick(s->tris_flat); break;
+        case 10: pick(s->slot_of_face); break;
+        case 11: src = &s->params; size = (int64_t)sizeof(s->params); break;
+        default: return -1;
+    }
+    if (s->tris.empty() && what != 11) size = 0;
+    if (bytes != size) return -1;
+    if (size) memcpy(out, src, (size_t)size);
+    return 0;
 }
 void hs_destroy(void* h) { delete (HsScene*)h; }
 int hs_height(void* h) { return ((HsScene*)h)->height; }

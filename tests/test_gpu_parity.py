@@ -105,6 +105,14 @@ def test_b1_edge_cases(hand):
     assert t.intersect(wide[:, ::2])[1].tolist() == [0, -1, -1]
 
 
+def _assert_sorted_and_stable(t):
+    """The exported keys do not decrease along the slots, and faces of equal keys are in face order."""
+    a = t.tree_arrays(("keys", "order"))
+    keys, order = a["keys"].astype(np.int64), a["order"].astype(np.int64)
+    assert np.all(np.diff(keys) >= 0)
+    assert np.all(np.diff(order)[np.diff(keys) == 0] > 0)
+
+
 def test_lbvh_rebuild_is_sound_and_stable_under_load(horse50k):
     """Many rebuilds back to back with traversal launches in flight: the inter-workgroup box
     hand-off of the refit (agent-scope release/acquire) must never leave a stale box."""
@@ -114,6 +122,7 @@ def test_lbvh_rebuild_is_sound_and_stable_under_load(horse50k):
     ref_T, ref_ID = t.intersect(rays)
     order0 = t.sorted_faces().clone()
     assert torch.equal(torch.sort(order0).values, torch.arange(len(horse50k.faces), device="cuda", dtype=torch.int32))
+    _assert_sorted_and_stable(t)
     g = torch.Generator(device="cuda").manual_seed(0)
     for it in range(40):
         # alternate between very different vertex sets: a stale box read from the previous build
@@ -642,6 +651,7 @@ def test_large_mesh_uses_the_unfused_sort_and_stays_exact():
     assert bad == 0 and 3 * t.wide_depth <= 64, (bad, height, t.wide_depth)
     order = t.sorted_faces().cpu().numpy()
     assert np.array_equal(np.sort(order), np.arange(len(sphere.faces)))
+    _assert_sorted_and_stable(t)
     rays = _camera_rays(sphere, 192, 11).cuda()
     T, ID = t.intersect(rays)
     assert 0.1 < (ID >= 0).float().mean().item() < 0.9

@@ -2,7 +2,9 @@
 
 This is how the LBVH build logic, the traversal and the hand-derived adjoint are
 checked in the GPU-less container; the `-m gpu` tests repeat the comparisons on the
-real kernels."""
+real kernels.  (The trees here are sorted by the full 30-bit key, hs_create; the tree the
+device builds for meshes of up to 262 144 faces drops the low 6 key bits -- hs_create_ex,
+held array by array to a restatement in test_bvh_host.py.)"""
 import ctypes
 
 import numpy as np
