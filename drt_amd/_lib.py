@@ -79,6 +79,7 @@ SIGNATURES = {
     "drt_hull_field": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _D, _D, _D, _D, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
     "drt_hull_mark": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _D, _P, _P, _P, _P]),
     "drt_hull_emit": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _D, _D, _D, _D, _D, _P, _P, _P, _I64, _I64, _P, _P, _P]),
+    "drt_decode_patterns": (_c.c_int, [_P, _P, _I64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P, _P, _P, _P, _P]),
     "drt_render_image": (_c.c_int, [_P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _D, _D, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int,
                                     _c.c_int, _P, _P, _P, _P, _P, _P]),
     "drt_render_image_loss": (_c.c_int, [_P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _D, _D, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_int,

@@ -667,6 +667,24 @@ int drt_hull_emit(const float* d_field, int nx, int ny, int nz, double lo_x, dou
                   const uint8_t* d_edge_mask, const int32_t* d_v_inc, const int32_t* d_t_inc, int64_t n_verts, int64_t n_faces,
                   double* d_verts, int32_t* d_faces, void* stream);
 
+/* ---- Gray-code pattern photographs -> screen codes, mask and ray targets (csrc/drt_decode.h states the law) ---
+ * Opt-in; drt_version() stays 13: probe for the symbol.  d_frames uint8 [n_views, F, height, width]: F = 2 (nbx + nby) photographs per
+ * view of a monitor of tex_w x tex_h texels (each in [2, 32768]; nbx = ceil(log2 tex_w), nby = ceil(log2 tex_h)) that shows bit after
+ * bit of the Gray code of the texel column, then of the row, most significant first, every pattern followed by its complement.
+ * Per pixel and bit: bit = a > b, c = |a - b|; contrast = min c; the pixel decodes iff contrast >= min_contrast (1..255) and the code
+ * lies inside the texture.  d_codes int16 [n_views, height, width, 2] = (x, y), or (-1, -1); d_contrast uint8 [n_views, height, width].
+ * d_background (may be NULL): the same patterns photographed without the object, [F, height, width] for all views
+ * (background_view_stride = 0) or one stack per view, background_view_stride bytes apart (>= F height width).  With it, d_mask uint8
+ * (may be NULL) = 255 where the background decodes and the object frames do not, or decode to a texel max(|dx|, |dy|) >= mask_shift away,
+ * else 0; d_covered uint8 (may be NULL) = 1 where the background decodes.  d_positions float64 [n_views, height * width, 3] (may be
+ * NULL; needs d_screens float64 [n_views, 9] = p0, eu, ev per view, a DEVICE pointer) = (p0 + x eu) + y ev, an x component that is
+ * exactly 0 replaced by 1e-12, and (0, 0, 0) where the pixel does not decode or -- zero_outside_mask = 1 (needs d_background) -- lies
+ * outside the mask.  The input pointers may have any alignment and the planes any size; nothing outside the stacks is read.  One
+ * kernel on `stream`, no workspace, no atomics: two runs give the same bits.  A bad argument gives DRT_E_INVALID and touches nothing. */
+int drt_decode_patterns(const uint8_t* d_frames, const uint8_t* d_background, int64_t background_view_stride, int n_views, int height, int width,
+                        int tex_h, int tex_w, int min_contrast, int mask_shift, const double* d_screens, int zero_outside_mask, int16_t* d_codes,
+                        uint8_t* d_contrast, uint8_t* d_mask, uint8_t* d_covered, double* d_positions, void* stream);
+
 /* ---- the refracted image of the mesh in front of a textured screen (csrc/drt_image.h states the law) ---------
  * A forward renderer, opt-in, without a gradient: rows [y0, y1) of the float32 image [height, width, channels] a pinhole camera sees.
  * camera21 (HOST, 21 doubles) = K^-1 [3,3] then the top [3,4] of R^-1, row-major; screen9 (HOST) = p0, eu, ev: the world position of
