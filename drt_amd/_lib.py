@@ -105,6 +105,8 @@ SIGNATURES = {
                                                _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drt_render_image_loss_views_env": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _D, _D, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int,
                                                    _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P]),
+    "drt_render_image_loss_views_absorb": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _D, _D, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int,
+                                                      _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P]),
     "drt_limit_sgd_step": (_c.c_int, [_P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _D, _P]),
     "drt_limit_sgd_step3": (_c.c_int, [_P, _P, _P, _I64, _D, _D, _c.c_int, _c.c_int, _D, _P, _P, _P, _P, _P]),
     "drt_weight_terms3": (_c.c_int, [_P, _P, _I64, _P, _P]),

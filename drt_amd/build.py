@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # gfx950 kernels + the C ABI, one translation unit per concern; drt_remesh.cpp is the host-only part (remeshing)
-UNITS = ["drt_api.hip", "drt_build.hip", "drt_trace.hip", "drt_pipeline.hip", "drt_paths.hip", "drt_raster.hip", "drt_edges.hip", "drt_topology.hip", "drt_remesh_gpu.hip", "drt_hull.hip", "drt_decode.hip", "drt_image.hip", "drt_image_loss.hip", "drt_image_screen.hip", "drt_image_camera.hip", "drt_image_views.hip", "drt_image_absorb.hip", "drt_image_env.hip", "drt_image_env_param.hip", "drt_image_views_env.hip", "drt_remesh.cpp"]
+UNITS = ["drt_api.hip", "drt_build.hip", "drt_trace.hip", "drt_pipeline.hip", "drt_paths.hip", "drt_raster.hip", "drt_edges.hip", "drt_topology.hip", "drt_remesh_gpu.hip", "drt_hull.hip", "drt_decode.hip", "drt_image.hip", "drt_image_loss.hip", "drt_image_screen.hip", "drt_image_camera.hip", "drt_image_views.hip", "drt_image_absorb.hip", "drt_image_env.hip", "drt_image_env_param.hip", "drt_image_views_env.hip", "drt_image_views_absorb.hip", "drt_remesh.cpp"]
 OUT = os.path.join(HERE, "libdrt_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 

@@ -281,11 +281,15 @@ class SyntheticPhotoData(PhotoData):
     ``render.Screen.behind`` the object, the photograph the rendered image, and the silhouette mask the pixels with an interaction (the
     ``hit`` plane > 0) through ``views.process_mask``.  ``view_ids``: keep only these views of the turntable of ``n_total``.
     ``environment`` / ``reflection``: ``render_image``'s -- the photographs are taken in that room, with the light reflected off the outer
-    surface when asked for; ``screen=False`` (needs an environment): no screen behind the object, ``texture`` is then ignored."""
+    surface when asked for; ``screen=False`` (needs an environment): no screen behind the object, ``texture`` is then ignored.
+    ``absorption`` (``render.check_absorption``'s forms): the object is tinted.  With screens only the photographs
+    come from ``render_image(absorption=)``.  With an environment ``render_image`` refuses that pair, so the clear render supplies the
+    silhouettes alone and the photographs are rendered through ``image_loss_views_fused(absorption=, want_images=True)`` against zero
+    targets, up to 16 views a call."""
 
     def __init__(self, scene_gt, center, extent, resx, resy, texture, num_view=8, device="cuda", n_total=None, view_ids=None, seed=0,
                  name="synthetic-photo", path_law=(6, "reflect", "snell"), supersample=2, fresnel=True, span=2.0, void=0.0, invalid=0.0,
-                 environment=None, reflection=False, screen=True):
+                 environment=None, reflection=False, screen=True, absorption=None):
         from . import render
         if not screen and environment is None:
             raise ValueError("screen=False needs an environment: without either there is nothing to photograph")
@@ -295,6 +299,8 @@ class SyntheticPhotoData(PhotoData):
         ids = list(range(n_total)) if view_ids is None else list(view_ids)
         law = tuple(path_law) + ("reference",) * (3 - len(path_law))
         more = {} if environment is None else {"environment": environment, "reflection": reflection}      # (without it: the call of before)
+        if absorption is not None and environment is None:
+            more = {"absorption": absorption}
         cameras, screens, photos, soft = [], [], [], []
         for k in ids:
             at = render.Screen.behind(cams[k], center, extent, tex.shape[1], tex.shape[0], span=span) if screen else None
@@ -304,10 +310,22 @@ class SyntheticPhotoData(PhotoData):
             screens.append(at)
             photos.append(image)
             soft.append(views.process_mask((hit > 0).cpu().numpy()))
+        if absorption is not None and environment is not None:
+            zeros = torch.zeros((len(ids), resy, resx, int(photos[0].shape[-1])), dtype=torch.float32, device=photos[0].device)
+            binding = scene_gt.bind_image_views(cameras, resy, resx, screens if screen else None, zeros, environment=environment)
+            photos = []
+            with torch.no_grad():
+                for b in range(0, len(ids), render.MAX_VIEWS_PER_CALL):
+                    chunk = list(range(b, min(b + render.MAX_VIEWS_PER_CALL, len(ids))))
+                    photos += list(scene_gt.image_loss_views_fused(binding, chunk, tex, vertices=False, supersample=supersample, max_bounces=law[0], tir=law[1],
+                                                                   refraction=law[2], fresnel=fresnel, void=void, invalid=invalid, reflection=reflection,
+                                                                   absorption=absorption, want_images=True)[1])
+            binding.release()
         super().__init__(cameras, screens if screen else None, tex, torch.stack(photos), soft, resx, resy, device=device, seed=seed, name=name,
                          environment=environment)
         self.path_law, self.supersample, self.fresnel, self.void, self.invalid = law, supersample, fresnel, void, invalid
         self.reflection = bool(reflection)
+        self.absorption = None if absorption is None else render.check_absorption(absorption, int(self.photos.shape[-1]))
 
 
 # ---------------------------------------------------------------------------------------------------------------

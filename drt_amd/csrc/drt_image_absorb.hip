@@ -16,9 +16,7 @@
 // Everything runs on the caller's stream, nothing is read back, every list size stays on the device.
 #include "drt_image_loss_bwd.h"
 
-namespace {
-
-// the host array sigma[channels] of an entry point, after image_call_check
+// the host array sigma[channels] of an entry point, after image_call_check (drt_image_views_absorb.hip uses it too)
 int absorb_sigma_check(const double* sigma, int channels, ImageSigma& out) {
     if (!sigma) return fail(DRT_E_INVALID, "null host pointer argument (sigma)");
     out = ImageSigma{{0.0, 0.0, 0.0}};
@@ -29,6 +27,8 @@ int absorb_sigma_check(const double* sigma, int channels, ImageSigma& out) {
     }
     return DRT_OK;
 }
+
+namespace {
 
 // k_image_shade<., ., ., ImageAbsorb> as the shade hook of image_forward_from; `src`: the payload
 void absorb_shade(const ImageShadeArgs& a, const void* src) { image_shade_launch(a, *static_cast<const ImageAbsorb*>(src)); }

@@ -142,21 +142,34 @@ enum : int { kImageBgFill = 0, kImageBgScreen = 1, kImageBgEnv = 2 };
 
 // Colour of one sample in front of a screen (has_screen) and an environment: image_sample_colour with the environment in the place of
 // `void`.  tx.c is the channel count (without a screen tx holds nothing else).  Returns where the colour came from.  acos / atan2 are
-// evaluated for the samples that go to the environment and for no other.
+// evaluated for the samples that go to the environment and for no other.  ABSORB (absorbing glass in a room):
+// (A_ch * T) times the background, A_ch = exp(-(sigma_ch * L)) -- the environment is attenuated exactly like the texture, in
+// image_sample_colour<true>'s association and with its fixed trip count.
+template <bool ABSORB = false>
 DRT_HD int image_env_sample_colour(const ImageScreen& sc, const ImageTex& tx, bool has_screen, const ImageEnv& env, int cls, d3 o, d3 d, double T,
-                                   const double* fill_invalid, double* c) {
+                                   const double* fill_invalid, double* c, double L = 0.0, const double* sigma = nullptr) {
     if (cls == kImageInvalid) {
         for (int ch = 0; ch < tx.c; ++ch) c[ch] = fill_invalid[ch];
         return kImageBgFill;
     }
     double u, v;
     if (has_screen && image_screen_uv(sc, tx.th, tx.tw, o, d, u, v)) {
-        for (int ch = 0; ch < tx.c; ++ch) c[ch] = T * image_bilinear(tx, u, v, ch);
+        if constexpr (ABSORB) {
+            for (int ch = 0; ch < kImageMaxChannels; ++ch)
+                if (ch < tx.c) c[ch] = (image_absorb_factor(sigma[ch], L) * T) * image_bilinear(tx, u, v, ch);
+        } else {
+            for (int ch = 0; ch < tx.c; ++ch) c[ch] = T * image_bilinear(tx, u, v, ch);
+        }
         return kImageBgScreen;
     }
     image_env_uv(env, d, u, v);
     const ImageEnvCell cell = image_env_cell(env, u, v);
-    for (int ch = 0; ch < tx.c; ++ch) c[ch] = T * image_env_bilinear(env, cell, ch);
+    if constexpr (ABSORB) {
+        for (int ch = 0; ch < kImageMaxChannels; ++ch)
+            if (ch < tx.c) c[ch] = (image_absorb_factor(sigma[ch], L) * T) * image_env_bilinear(env, cell, ch);
+    } else {
+        for (int ch = 0; ch < tx.c; ++ch) c[ch] = T * image_env_bilinear(env, cell, ch);
+    }
     return kImageBgEnv;
 }
 
@@ -232,18 +245,40 @@ DRT_HD double image_env_background_backward(const ImageScreen& sc, const ImageTe
 }
 
 // image_sample_backward in front of a screen (has_screen) and an environment: every THROUGH sample carries a gradient, through the screen
-// where it lands on it (image_sample_backward itself: the same bits) and through the environment lookup otherwise.
-template <bool SNELL, bool FRESNEL, typename Add>
+// where it lands on it (image_sample_backward itself: the same bits) and through the environment lookup otherwise.  LENGTH (absorbing
+// glass): on the screen image_sample_backward<.., LENGTH>; to the environment the seeds g_c[ch] A_ch stand in for g_c
+// (so g_T = sum g_c A E, and the (u, v) lookup seeds are scaled by A too), and g_L = sum_ch (g_c[ch] (-sigma_ch)) c[ch] with the forward's
+// c[ch] = (A_ch T) E_ch goes to every interaction with sg < 0 (image_path_backward<.., LENGTH>).
+template <bool SNELL, bool FRESNEL, bool LENGTH = false, typename Add>
 DRT_HD bool image_env_sample_backward(const PathCtx& c, d3 o, d3 d, const int32_t* faces, int64_t face_stride, int n_hits, d3 exit_o, d3 exit_d, double T,
                                       const ImageScreen& sc, const ImageTex& tx, bool has_screen, const ImageEnv& env, const double* g_c, Add add,
-                                      double& g_int, double& g_ext) {
+                                      double& g_int, double& g_ext, double L = 0.0, const double* sigma = nullptr) {
     double u, v;
-    if (has_screen && image_screen_uv(sc, tx.th, tx.tw, exit_o, exit_d, u, v))
-        return image_sample_backward<SNELL, FRESNEL>(c, o, d, faces, face_stride, n_hits, exit_o, exit_d, T, sc, tx, g_c, add, g_int, g_ext);
-    d3 g_o, g_d;
-    const double g_T = image_env_background_backward(sc, tx, false, env, exit_o, exit_d, g_c, T, g_o, g_d);
-    image_path_backward<SNELL, FRESNEL>(c, o, d, faces, face_stride, n_hits, g_o, g_d, g_T, add, g_int, g_ext);
-    return true;
+    if constexpr (LENGTH) {
+        if (has_screen && image_screen_uv(sc, tx.th, tx.tw, exit_o, exit_d, u, v))
+            return image_sample_backward<SNELL, FRESNEL, true>(c, o, d, faces, face_stride, n_hits, exit_o, exit_d, T, sc, tx, g_c, add, g_int, g_ext, nullptr, nullptr,
+                                                               L, sigma);
+        double E[kImageMaxChannels], gA[kImageMaxChannels] = {0.0, 0.0, 0.0}, g_L = 0.0;
+        image_env_background(sc, tx, false, env, exit_o, exit_d, E);
+        for (int ch = 0; ch < tx.c; ++ch) {
+            const double A = image_absorb_factor(sigma[ch], L);
+            gA[ch] = g_c[ch] * A;
+            const double col = (A * T) * E[ch];             // the forward's c[ch]
+            const double gl = (g_c[ch] * (-sigma[ch])) * col;
+            g_L = ch == 0 ? gl : g_L + gl;
+        }
+        d3 g_o, g_d;
+        const double g_T = image_env_background_backward(sc, tx, false, env, exit_o, exit_d, gA, T, g_o, g_d);
+        image_path_backward<SNELL, FRESNEL, true>(c, o, d, faces, face_stride, n_hits, g_o, g_d, g_T, add, g_int, g_ext, nullptr, nullptr, g_L);
+        return true;
+    } else {
+        if (has_screen && image_screen_uv(sc, tx.th, tx.tw, exit_o, exit_d, u, v))
+            return image_sample_backward<SNELL, FRESNEL>(c, o, d, faces, face_stride, n_hits, exit_o, exit_d, T, sc, tx, g_c, add, g_int, g_ext);
+        d3 g_o, g_d;
+        const double g_T = image_env_background_backward(sc, tx, false, env, exit_o, exit_d, g_c, T, g_o, g_d);
+        image_path_backward<SNELL, FRESNEL>(c, o, d, faces, face_stride, n_hits, g_o, g_d, g_T, add, g_int, g_ext);
+        return true;
+    }
 }
 
 // The adjoint of the reflection term R1 * B(ro, wr) of a sample with camera ray (o, d) and first face `face`, under the seeds g_c: one

@@ -106,12 +106,17 @@ void reflection_pass(drt_scene* s, const PathCtx& pc, const ImageCall& c, const 
 // the caller's wavefront, with the face tape kept), reflection pass, loss resolve, and -- on a scene with triangles, when a gradient or the
 // count is wanted -- the list of through samples, the adjoint and the reflection's adjoint.  Afterwards the pixel seeds g_c, the state
 // bytes, the parked rows, the throughputs and the tape are what the resolve read: between it and the return only w.idx[0] and the counter
-// kCntValid are written (the through list).
-template <typename VIEW, typename Forward>
+// kCntValid are written (the through list).  PAYLOAD: ImageClear, or (drt_image_views_absorb.hip) an ImageAbsorb, taken
+// by value and handed to `forward(pay)`, which completes it (the lengths' address), as image_loss_run does; its resolve also adds the
+// sigma partials into out.grad_sigma.  The reflection's pass and adjoint are the same under both payloads: the reflected light never
+// entered the object.
+template <typename VIEW, typename Forward, typename PAYLOAD = ImageClear>
 int env_loss_run(drt_scene* s, const double* d_verts, const ImageCall& c, const VIEW& view, Forward forward, const ImageScreenEnv& bg, bool reflection,
-                 const ImageLossOut& out, hipStream_t st, const char* who) {
+                 const ImageLossOut& out, hipStream_t st, const char* who, PAYLOAD pay = PAYLOAD{}) {
     { int rc = ensure_image_loss_ws(s, c.n_pix * c.tx.c, 0, st, who); if (rc) return rc; }
-    { int rc = forward(); if (rc) return rc; }
+    if constexpr (std::is_invocable_v<Forward, PAYLOAD&>) { int rc = forward(pay); if (rc) return rc; }
+    else { int rc = forward(); if (rc) return rc; }
+    double* const grad_sigma = PAYLOAD::kAbsorb ? out.grad_sigma : nullptr;
     const PathCtx pc = image_path_ctx(s, d_verts, c);
     if (reflection) reflection_pass(s, pc, c, view, st);
     const PathsWs& w = *paths_ws_of(s);
@@ -119,22 +124,22 @@ int env_loss_run(drt_scene* s, const double* d_verts, const ImageCall& c, const 
     const unsigned pix_grid = (unsigned)((c.n_pix + kPathBlock - 1) / kPathBlock);
     if (reflection) {          // (the tape's address is read here, behind the forward that may have grown it)
         const ImageScreenEnvReflect bgr{bg.screen, bg.env, pc, c.snell, w.tape, nullptr};
-        auto resolve = det_mode() ? k_image_loss_resolve<true, VIEW, ImageClear, ImageScreenEnvReflect>
-                                  : k_image_loss_resolve<false, VIEW, ImageClear, ImageScreenEnvReflect>;
-        resolve<<<pix_grid, kPathBlock, 0, st>>>(view, c.band, c.n_pix, c.tx, c.fill, c.fresnel, ImageClear{}, w.park, w.park + 3 * w.fused_cap, w.thr, w.state,
-                                                 w.hits, out.target, out.weight, lw.g_c, out.image, out.loss, nullptr, bgr);
+        auto resolve = det_mode() ? k_image_loss_resolve<true, VIEW, PAYLOAD, ImageScreenEnvReflect>
+                                  : k_image_loss_resolve<false, VIEW, PAYLOAD, ImageScreenEnvReflect>;
+        resolve<<<pix_grid, kPathBlock, 0, st>>>(view, c.band, c.n_pix, c.tx, c.fill, c.fresnel, pay, w.park, w.park + 3 * w.fused_cap, w.thr, w.state,
+                                                 w.hits, out.target, out.weight, lw.g_c, out.image, out.loss, grad_sigma, bgr);
     } else {
-        auto resolve = det_mode() ? k_image_loss_resolve<true, VIEW, ImageClear, ImageScreenEnv>
-                                  : k_image_loss_resolve<false, VIEW, ImageClear, ImageScreenEnv>;
-        resolve<<<pix_grid, kPathBlock, 0, st>>>(view, c.band, c.n_pix, c.tx, c.fill, c.fresnel, ImageClear{}, w.park, w.park + 3 * w.fused_cap, w.thr, w.state,
-                                                 w.hits, out.target, out.weight, lw.g_c, out.image, out.loss, nullptr, bg);
+        auto resolve = det_mode() ? k_image_loss_resolve<true, VIEW, PAYLOAD, ImageScreenEnv>
+                                  : k_image_loss_resolve<false, VIEW, PAYLOAD, ImageScreenEnv>;
+        resolve<<<pix_grid, kPathBlock, 0, st>>>(view, c.band, c.n_pix, c.tx, c.fill, c.fresnel, pay, w.park, w.park + 3 * w.fused_cap, w.thr, w.state,
+                                                 w.hits, out.target, out.weight, lw.g_c, out.image, out.loss, grad_sigma, bg);
     }
     if (s->n_faces > 0 && (out.grad_verts || out.grad_ior || out.count)) {
         int32_t* const done = w.idx[0];          // (the reflection list is no longer needed: its verdicts are in the state bytes)
         launch_paths_collect(grid_for(c.n, kPathBlock, 8 * s->n_cu), st, (unsigned)c.n, w.state, done, w.cnt + kCntValid);
         const int grid = (out.grad_verts ? DRT_BWD_BPC : kImageLossBpc) * s->n_cu;
-        image_loss_bwd_kernel<VIEW, ImageClear, false, ImageScreenEnv>(det_mode(), c.snell, c.fresnel, out.grad_verts != nullptr)<<<grid, 256, 0, st>>>(
-            pc, view, c.band, c.tx, ImageClear{}, c.max_bounces, w.park, w.park + 3 * w.fused_cap, w.thr, w.tape, w.hits, done, w.cnt + kCntValid, lw.g_c,
+        image_loss_bwd_kernel<VIEW, PAYLOAD, false, ImageScreenEnv>(det_mode(), c.snell, c.fresnel, out.grad_verts != nullptr)<<<grid, 256, 0, st>>>(
+            pc, view, c.band, c.tx, pay, c.max_bounces, w.park, w.park + 3 * w.fused_cap, w.thr, w.tape, w.hits, done, w.cnt + kCntValid, lw.g_c,
             out.grad_verts, out.grad_ior, reinterpret_cast<unsigned long long*>(out.count), nullptr, bg);
         if (reflection && (out.grad_verts || out.grad_ior))
             reflect_bwd_kernel<VIEW>((det_mode() ? 4 : 0) | (c.snell ? 2 : 0) | (out.grad_verts ? 1 : 0), std::make_integer_sequence<int, 8>{})<<<grid, 256, 0, st>>>(

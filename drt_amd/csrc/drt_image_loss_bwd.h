@@ -6,7 +6,8 @@
 // drt_image_views.hip <ImageViewTable, ImageClear> (10.6) and drt_image_absorb.hip <ImageOneView, ImageAbsorb> (10.7).
 // Four units because a kernel's register allocation depends on the other kernels of its unit.  For the same reason the
 // forms under an environment have units of their own: drt_image_env.hip <ImageOneView, ImageClear, ., ImageScreenEnv[Reflect]> (10.8) and
-// drt_image_views_env.hip <ImageViewTable, ImageClear, ., ImageScreenEnv[Reflect]> (10.10), through env_loss_run (drt_image_env_loss.h).
+// drt_image_views_env.hip <ImageViewTable, ImageClear, ., ImageScreenEnv[Reflect]> (10.10), through env_loss_run (drt_image_env_loss.h);
+// and drt_image_views_absorb.hip <ImageViewTable, ImageAbsorb> under all three backgrounds (10.13).
 #pragma once
 #include "drt_image_wave.h"
 #include "drt_image_loss.h"
@@ -25,6 +26,7 @@ __global__ void __launch_bounds__(kPathBlock) k_image_loss_resolve(VIEW view, Im
                                                                     const float* __restrict__ weight, double* __restrict__ g_c,
                                                                     float* __restrict__ image, double* loss, double* grad_sigma,
                                                                     BACKGROUND bg = BACKGROUND{}) {
+    static_assert(!(PAYLOAD::kAbsorb && BACKGROUND::kEnv) || std::is_same_v<VIEW, ImageViewTable>, "absorbing glass in a room: under the view table only");
     const int64_t pix = (int64_t)blockIdx.x * kPathBlock + threadIdx.x;
     LossAcc<DET> acc;
     [[maybe_unused]] LossAcc<DET> sig[kImageMaxChannels];
@@ -76,11 +78,14 @@ __global__ void __launch_bounds__(kPathBlock) k_image_loss_resolve(VIEW view, Im
 // in kPathsBwdBatch-sized fills, the IOR partials through two LossAcc; VERTS = false: no table in LDS.  grad_verts (VERTS), grad_ior and
 // count may each be null.  CAMERA: seeds [2, band.n, 3] receives (g_o; g_d) of every listed sample that lands on the screen, under its
 // sample index; the other rows are left as they are.  The absorbing forms with the table ask for two blocks per CU: without that bound
-// they drop to one wave (profiles/image_absorb_resources.txt).  BACKGROUND with an environment (ImageClear, no CAMERA): every listed
+// they drop to one wave (profiles/image_absorb_resources.txt); in front of an environment they do not ask for it: under that bound the
+// forms with the table spill 35 to 157 VGPRs, without it they run one wave and spill at most 4 (profiles/image_views_absorb_resources.txt).
+// BACKGROUND with an environment (no CAMERA; ImageAbsorb under the view
+// table only, drt_image_views_absorb.hip): every listed
 // sample carries a gradient, through the screen where its exit ray lands on it and through the environment lookup otherwise
 // (image_env_sample_backward); the reflection's adjoint is a kernel of its own (drt_image_env.hip).
 template <bool DET, bool SNELL, bool FRESNEL, bool VERTS, typename VIEW, typename PAYLOAD, bool CAMERA, typename BACKGROUND = ImageScreenOnly>
-__global__ void __launch_bounds__(256, PAYLOAD::kAbsorb && VERTS ? 2 : 1)
+__global__ void __launch_bounds__(256, PAYLOAD::kAbsorb && VERTS && !BACKGROUND::kEnv ? 2 : 1)
     k_image_loss_bwd(PathCtx c, VIEW view, ImageBand band, ImageTex tx, PAYLOAD pay, int max_bounces, const double* __restrict__ park_ori,
                      const double* __restrict__ park_dir, const double* __restrict__ thr, const int32_t* __restrict__ tape,
                      const uint8_t* __restrict__ hits, const int32_t* __restrict__ list, const unsigned* __restrict__ n_list,
@@ -108,9 +113,11 @@ __global__ void __launch_bounds__(256, PAYLOAD::kAbsorb && VERTS ? 2 : 1)
         double gi, ge;
         bool carried;
         if constexpr (BACKGROUND::kEnv) {
-            static_assert(!PAYLOAD::kAbsorb && !CAMERA, "an environment goes with clear glass and without camera seeds");
-            carried = image_env_sample_backward<SNELL, FRESNEL>(c, o, d, tape + i, (int64_t)band.n, min((int)hits[i], max_bounces), load_d3(park_ori, i),
-                                                                load_d3(park_dir, i), FRESNEL ? thr[i] : 1.0, v.sc, tx, bg.screen, bg.env, g, add, gi, ge);
+            static_assert(!CAMERA, "an environment goes without camera seeds");
+            static_assert(!PAYLOAD::kAbsorb || std::is_same_v<VIEW, ImageViewTable>, "absorbing glass in a room: under the view table only");
+            carried = image_env_sample_backward<SNELL, FRESNEL, PAYLOAD::kAbsorb>(c, o, d, tape + i, (int64_t)band.n, min((int)hits[i], max_bounces),
+                                                                                  load_d3(park_ori, i), load_d3(park_dir, i), FRESNEL ? thr[i] : 1.0, v.sc, tx,
+                                                                                  bg.screen, bg.env, g, add, gi, ge, L, sigma);
         } else {
             carried = image_sample_backward<SNELL, FRESNEL, PAYLOAD::kAbsorb>(c, o, d, tape + i, (int64_t)band.n, min((int)hits[i], max_bounces), load_d3(park_ori, i),
                                                                               load_d3(park_dir, i), FRESNEL ? thr[i] : 1.0, v.sc, tx, g, add, gi, ge,

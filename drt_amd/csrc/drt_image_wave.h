@@ -11,6 +11,7 @@
 // A unit instantiates the forms it launches and no others, so a kernel stays in the unit that held it before there was a template
 // (a kernel's register allocation depends on the other kernels of its unit: DESIGN.md section 4).
 #pragma once
+#include <type_traits>
 #include <utility>
 #include "drt_device.h"
 #include "drt_pathws.h"
@@ -70,13 +71,14 @@ struct ImageAbsorb {
     double* __restrict__ len;      // the interior length of every sample of the band (PathsWs::len)
     ImageSigma sigma;
     struct Sums {
-        double lc[kImageMaxChannels] = {0.0, 0.0, 0.0};          // that of L_j c_j[ch] over the through samples on the screen (the sigma partials)
+        double lc[kImageMaxChannels] = {0.0, 0.0, 0.0};          // that of L_j c_j[ch] over the lit through samples, transmitted part only (the sigma partials)
         double l_sum;                                            // that of L over the through samples
     };
 };
 
 // ---- the background policy: where the colour of a direct or through sample comes from.  A form without an environment holds no trace of
-// it (`if constexpr (BACKGROUND::kEnv)`, as kAbsorb); it goes with ImageClear only.
+// it (`if constexpr (BACKGROUND::kEnv)`, as kAbsorb).  With ImageAbsorb it goes under ImageViewTable only (drt_image_views_absorb.hip,
+// DESIGN.md 10.13): the single-view pair is never instantiated.
 struct ImageScreenOnly { static constexpr bool kEnv = false; };
 struct ImageScreenEnv {
     static constexpr bool kEnv = true, kReflect = false;
@@ -161,6 +163,9 @@ void image_start_call(const ImageStartArgs& a, const void* src);
 
 // One buffer of a workspace grown to n doubles (defined in drt_image.hip): never inside a stream capture (`what`, for the message).
 int grow_doubles(double*& buf, int64_t& cap, int64_t n, hipStream_t st, const char* who, const char* what);
+
+// The host array sigma[channels] of an absorbing entry point, after image_call_check (defined in drt_image_absorb.hip).
+int absorb_sigma_check(const double* sigma, int channels, ImageSigma& out);
 
 // The workspace of the loss calls behind drt_scene::image_loss_ws (drt_image_loss.hip; drt_image_views.hip shares the pixel seeds), and its
 // growth to n_seed doubles of pixel seeds and n_cam doubles of camera-ray seeds (0: none wanted) -- never inside a stream capture.
@@ -363,7 +368,6 @@ __device__ __forceinline__ void image_pixel_walk(const ImageCam& cam, const Imag
                                                  const uint8_t* __restrict__ state, const uint8_t* __restrict__ hits, double* sum,
                                                  typename PAYLOAD::Sums& more, int& n_hit, int& n_through, const BACKGROUND& bg = BACKGROUND{},
                                                  int* n_reflect = nullptr) {
-    static_assert(!(PAYLOAD::kAbsorb && BACKGROUND::kEnv), "an environment goes with clear glass only");
     const int s2 = band.s * band.s;
     n_hit = 0; n_through = 0;
     if constexpr (PAYLOAD::kAbsorb) more.l_sum = 0.0;
@@ -389,12 +393,41 @@ __device__ __forceinline__ void image_pixel_walk(const ImageCam& cam, const Imag
         }
         double c[kImageMaxChannels];
         if constexpr (PAYLOAD::kAbsorb) {
-            const bool lit = image_sample_colour<true>(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c, L, pay.sigma.v);
+            if constexpr (BACKGROUND::kEnv) {
+                // Absorbing glass in a room: the environment is attenuated like the texture.  lc takes the transmitted
+                // colour BEFORE the reflection is added into c: that light never entered the object and carries no sigma partial.
+                const bool lit = image_env_sample_colour<true>(sc, tx, bg.screen, bg.env, cls, o, d, T, fill.c_invalid, c, L, pay.sigma.v) != kImageBgFill;
 #pragma unroll
-            for (int ch = 0; ch < kImageMaxChannels; ++ch) {
-                if (ch >= tx.c) continue;
-                sum[ch] = j == 0 ? c[ch] : sum[ch] + c[ch];
-                if (lit && cls == kImageThrough) more.lc[ch] = more.lc[ch] + L * c[ch];
+                for (int ch = 0; ch < kImageMaxChannels; ++ch) {
+                    if (ch >= tx.c) continue;
+                    if (lit && cls == kImageThrough) more.lc[ch] = more.lc[ch] + L * c[ch];
+                }
+                if constexpr (BACKGROUND::kReflect) {
+                    if (cls == kImageThrough && (state[i] & kImageReflectSeen)) {
+                        d3 co, cd, ro, wr;
+                        double R1;
+                        image_sample_ray(cam, band.s, x, y, j, co, cd);
+                        const bool seen = bg.snell ? image_reflect_first<true>(bg.pc, bg.first_face[i], co, cd, ro, wr, R1)
+                                                   : image_reflect_first<false>(bg.pc, bg.first_face[i], co, cd, ro, wr, R1);
+                        if (seen) {
+                            image_env_add_reflection(sc, tx, bg.screen, bg.env, ro, wr, R1, c);
+                            if (n_reflect) ++*n_reflect;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int ch = 0; ch < kImageMaxChannels; ++ch) {
+                    if (ch >= tx.c) continue;
+                    sum[ch] = j == 0 ? c[ch] : sum[ch] + c[ch];
+                }
+            } else {
+                const bool lit = image_sample_colour<true>(sc, tx, cls, o, d, T, fill.c_void, fill.c_invalid, c, L, pay.sigma.v);
+#pragma unroll
+                for (int ch = 0; ch < kImageMaxChannels; ++ch) {
+                    if (ch >= tx.c) continue;
+                    sum[ch] = j == 0 ? c[ch] : sum[ch] + c[ch];
+                    if (lit && cls == kImageThrough) more.lc[ch] = more.lc[ch] + L * c[ch];
+                }
             }
         } else {
             if constexpr (BACKGROUND::kEnv) {
@@ -426,6 +459,7 @@ __global__ void __launch_bounds__(kPathBlock) k_image_resolve(ImageCam cam, Imag
                                                                const double* __restrict__ thr, const uint8_t* __restrict__ state,
                                                                const uint8_t* __restrict__ hits, float* __restrict__ image, float* __restrict__ hit,
                                                                float* __restrict__ through, float* __restrict__ length, BACKGROUND bg = BACKGROUND{}) {
+    static_assert(!(PAYLOAD::kAbsorb && BACKGROUND::kEnv), "one view: an environment goes with clear glass only");
     const int64_t pix = (int64_t)blockIdx.x * kPathBlock + threadIdx.x;
     if (pix >= n_pix) return;
     const int s2 = band.s * band.s;

@@ -887,7 +887,7 @@ def enqueue_image_env_term(scene, vertices, a, ior, texture, env, target, weight
 
 
 def enqueue_image_views_term(scene, vertices, binding, view_ids, texture, law, supersample, fresnel, void, invalid, ior, loss_ptr, grad_ptr,
-                             grad_ior_ptr=None, count_ptr=None, bands=None, reflection=False):
+                             grad_ior_ptr=None, count_ptr=None, bands=None, reflection=False, absorption=None, grad_sigma_ptr=None, images_ptr=None):
     """Enqueues the photometric image term of the listed views of ``binding`` (a ``render.ImageViews``) -- the SUM over ``view_ids`` of one
     view's loss and d loss / d vertices (unit seed), as one forward wavefront and one adjoint pass per band -- on the current stream; the
     one place that packs the arguments of drt_render_image_loss_views and drt_render_image_loss_views_env.  The entry point follows the
@@ -897,12 +897,21 @@ def enqueue_image_views_term(scene, vertices, binding, view_ids, texture, law, s
     ``invalid``: float64 numpy arrays of C values; ``ior``: (interior, exterior) floats; ``bands``: rows [r0, r1) of the tall image of
     ``len(view_ids) * H`` rows (``render.plan_bands``), the whole of it without.  ``loss_ptr`` / ``grad_ptr`` / ``grad_ior_ptr`` /
     ``count_ptr`` are raw device addresses the kernels ADD into (float64, or fixed-point cells in deterministic mode; int64 count); all
-    but the first may be None.  Nothing is checked here but what the library checks.  The caller is inside ``_on(device)``.  Returns
-    what the enqueued kernels read, for the caller to keep alive."""
+    but the first may be None.  ``absorption``: C float64 coefficients on the host (``render.check_absorption``), or
+    None; with them the call goes to drt_render_image_loss_views_absorb whether or not the binding has an environment, with
+    ``grad_sigma_ptr`` (C more accumulators for d loss / d sigma, addressed like ``grad_ior_ptr``) and ``images_ptr`` (a float32 stack
+    [n_views, H, W, C] that receives the rendered pixels of the listed views), both nullable; with None the entry point and the packed
+    arguments are exactly those of before.  Nothing is checked here but what the library checks.  The caller is inside
+    ``_on(device)``.  Returns what the enqueued kernels read, for the caller to keep alive."""
     ids = (ctypes.c_int * len(view_ids))(*view_ids)
     flags = _law_flags(law[1], law[2] if len(law) > 2 else "reference")
     env = getattr(binding, "env", None)
-    if env is None:
+    if absorption is not None:
+        fn = _lib.lib().drt_render_image_loss_views_absorb
+        more = (absorption.ctypes.data, grad_sigma_ptr) + ((None, 0, 0, None, 0) if env is None else
+                                                          (env.data_ptr(), env.shape[0], env.shape[1], binding.env_rot.ctypes.data, int(reflection))) + (images_ptr,)
+        tex_args = (None, 0, 0, env.shape[2]) if texture is None else (texture.data_ptr(), texture.shape[0], texture.shape[1], texture.shape[2])
+    elif env is None:
         fn, more = _lib.lib().drt_render_image_loss_views, ()
         tex_args = (texture.data_ptr(), texture.shape[0], texture.shape[1], texture.shape[2])
     else:
@@ -1091,6 +1100,27 @@ def _image_views_term(scene, binding, a, ior, tex, law):
             enqueue_image_views_term(scene, v, binding, a["ids"], tex, law, a["supersample"], a["fresnel"], a["void"], a["invalid"], ior, loss.data_ptr(),
                                      _lib.ptr(cells.get(_VERTS)), cells["ior"].data_ptr(), count.data_ptr(), a["bands"], a.get("reflection", False))
     return _Term(v.device, _verts_ior_accs(v, a["vertices"]), enqueue, ((_VERTS, None),) + _IOR_FEEDS, count)
+
+
+def _image_views_absorb_term(scene, binding, a, ior, tex, law):
+    """The term of image_loss_views_fused under an absorption (``enqueue_image_views_term``) for the inputs (vertices,
+    ior_int, ior_ext, absorption): as ``_image_views_term``, with the C sigma accumulators only when the absorption is a tensor that
+    needs a gradient, and -- with ``a["want_images"]`` -- ``image``: a stack [n_views, H, W, C] of the capture's
+    layout in which the listed views' pixels are written (the others stay zero)."""
+    v = _f64c(scene.vertices.detach(), "vertices")
+    dev = v.device
+    accs = _verts_ior_accs(v, a["vertices"])
+    accs["sigma"] = (torch.empty(a["channels"], dtype=torch.float64, device=dev), (3,))
+    count = torch.zeros((), dtype=torch.int64, device=dev)
+    # (the library writes a listed view's pixels at that view's place in a stack of the capture's layout)
+    stack = torch.zeros((binding.n, binding.height, binding.width, a["channels"]), dtype=torch.float32, device=dev) if a["want_images"] else None
+
+    def enqueue(loss, cells):
+        with _on(dev):
+            enqueue_image_views_term(scene, v, binding, a["ids"], tex, law, a["supersample"], a["fresnel"], a["void"], a["invalid"], ior, loss.data_ptr(),
+                                     _lib.ptr(cells.get(_VERTS)), cells["ior"].data_ptr(), count.data_ptr(), a["bands"], a.get("reflection", False),
+                                     a["absorption"], _lib.ptr(cells.get("sigma")), _lib.ptr(stack))
+    return _Term(dev, accs, enqueue, ((_VERTS, None),) + _IOR_FEEDS + (("sigma", None),), count, stack)
 
 
 def ray_loss(out_ori, out_dir, mask, screen_pixel, valid):
@@ -1451,7 +1481,7 @@ class Scene(StepwiseMixin):
 
     def image_loss_views_fused(self, binding, view_ids, texture, *, ior_int=None, ior_ext=None, vertices=True, supersample=1, max_bounces=2,
                                tir="drop", refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, environment=None,
-                               reflection=False):
+                               reflection=False, absorption=None, want_images=False):
         """The SUM over ``view_ids`` (1..16 views of ``binding``, repeats allowed) of ``image_loss_fused`` of each view against its target
         (and weight plane) of the binding -- loss, vertex gradient, IOR partials, ``last_image_count`` -- evaluated as ONE forward
         wavefront and ONE adjoint pass instead of one chain of launches per view (drt_render_image_loss_views).  The views
@@ -1463,7 +1493,15 @@ class Scene(StepwiseMixin):
         ``texture`` is None exactly when that binding has no screens, and ``reflection=True`` (needs such a binding and ``fresnel``) adds
         the outer-surface reflection.  The environment belongs to the capture: ``environment=`` given HERE raises ``ValueError``, and so
         does ``reflection=True`` on a binding without an environment.  The environment's texels and rotation receive no gradient in this
-        call; ``image_loss_fused`` keeps those."""
+        call; ``image_loss_fused`` keeps those.
+        ``absorption``: ``image_loss_fused``'s -- None, one number, C numbers or a float64 tensor ``[C]`` (read to the
+        host once per call).  Every view is then rendered with absorbing glass, on a binding with an environment too: the environment
+        is attenuated along the interior length exactly like the texture, the reflection is not (that light never entered the object).
+        The vertex and IOR gradients are the derivative of the whole law, the interior lengths included; a tensor that requires grad
+        receives d loss / d absorption, from the transmitted light alone (drt_render_image_loss_views_absorb).  With None the call is
+        what it was.  ``want_images=True`` (needs ``absorption``; 0.0 renders clear glass) returns ``(loss, images)`` with the float32
+        images ``[k, H, W, C]`` of the listed views: the way to render a tinted object in a room -- a binding with one view serves for a
+        single one, since ``render_image`` refuses that pair."""
         from . import render as _render
         if environment is not None:
             raise ValueError("environment: the multi-view call takes its environment from the binding; give it to bind_image_views(..., environment=)")
@@ -1471,14 +1509,26 @@ class Scene(StepwiseMixin):
             raise ValueError("reflection: the multi-view call reflects the binding's environment and this binding has none; "
                              "give one to bind_image_views(..., environment=)")
         a = _render.check_image_views_law(binding, view_ids, texture, ior_int, ior_ext, vertices, supersample, max_bounces, tir, refraction, fresnel,
-                                          void, invalid, max_samples, reflection)
+                                          void, invalid, max_samples, reflection, absorption, want_images)
         if binding.scene is not self:
             raise ValueError("binding was made by another scene's bind_image_views")
         ior, tracked = _ior_args(intIOR if ior_int is None else ior_int, extIOR if ior_ext is None else ior_ext)
         with _on(self._dev):
             tex = None if a["texture"] is None else torch.as_tensor(a["texture"], device=self._dev).to(torch.float32).contiguous()
+        inputs = (self.vertices if a["vertices"] else self.vertices.detach(),) + tracked
+        if a["absorption"] is not None:
+            term = _image_views_absorb_term(self, binding, a, ior, tex, (a["max_bounces"], tir, refraction))
+            # (inputs is (vertices, ior_int, ior_ext) -- _ior_args always gives two -- so the absorption sits at position 3, the ``users`` of
+            # the term's sigma accumulators)
+            assert len(inputs) == 3
+            loss = _UnitSeedTerm.apply(term, *inputs, absorption if isinstance(absorption, torch.Tensor) else None)
+            self.last_image_count = term.count
+            if not a["want_images"]:
+                return loss
+            with _on(self._dev):
+                return loss, term.image[torch.as_tensor(a["ids"], dtype=torch.int64, device=self._dev)]
         term = _image_views_term(self, binding, a, ior, tex, (a["max_bounces"], tir, refraction))
-        loss = _UnitSeedTerm.apply(term, self.vertices if a["vertices"] else self.vertices.detach(), *tracked)
+        loss = _UnitSeedTerm.apply(term, *inputs)
         self.last_image_count = term.count
         return loss
 

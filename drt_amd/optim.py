@@ -496,6 +496,41 @@ class ShardedIteration(FusedIteration):
         self._init(scene, data, HyperParams, lr, views_per_step, concurrent, path_law, schedule)
 
 
+class AbsorptionState:
+    """The absorption coefficients of a photometric fit and, when they are fitted, the moments of their optimiser:
+    ``sigma`` float64 numpy [C] on the host -- what the next step's call takes --, and ``calibrate.fit_absorption``'s update: Adam
+    steps of ``lr`` (in units of sigma) on the C numbers, each followed by the projection onto ``sigma >= 0``.  ``lr == 0``: sigma is
+    fixed and ``update`` is never called.  ``optimize_photometric`` makes one and hands it to every pass's stepper, so the fit and its
+    moments carry across passes."""
+
+    def __init__(self, absorption, channels, lr=0.0):
+        from . import render
+        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not (float(lr) >= 0.0) or not np.isfinite(float(lr)):
+            raise ValueError(f"absorption_lr must be a finite number >= 0, got {lr!r}")
+        self.lr = float(lr)
+        start = render.check_absorption(0.0 if absorption is None else absorption, channels)
+        self.sigma = np.ascontiguousarray(start, dtype=np.float64).copy()
+        self.steps = 0
+        self._param = self._opt = None
+        if self.lr > 0.0:
+            self._param = torch.tensor(self.sigma, dtype=torch.float64, requires_grad=True)
+            self._opt = torch.optim.Adam([self._param], lr=self.lr)
+
+    @property
+    def fitted(self):
+        return self.lr > 0.0
+
+    def update(self, grad):
+        """One Adam step on ``grad`` (C float64 numbers on the host: d weighted loss / d sigma), then the projection; returns sigma."""
+        self._param.grad = torch.as_tensor(np.asarray(grad, dtype=np.float64).reshape(self.sigma.shape)).clone()
+        self._opt.step()
+        with torch.no_grad():
+            self._param.clamp_(min=0.0)
+        self.sigma[:] = self._param.detach().numpy()          # (in place: the array the next call's pointer is taken from)
+        self.steps += 1
+        return self.sigma
+
+
 class PhotoIteration(FusedIteration):
     """FusedIteration for a capture of plain photographs (captured_data.PhotoData): slot 0 of the accumulator block, where the
     refraction term goes, holds the photometric image term of ``views_per_step`` drawn views, evaluated as ONE forward wavefront and ONE
@@ -504,10 +539,16 @@ class PhotoIteration(FusedIteration):
     ``path_law`` = (max_bounces, tir[, refraction]), ``fresnel`` and ``supersample`` are the image's law (``Scene.render_image``);
     ``HyperParams["IOR"]`` is the object's index of refraction.  A capture with an ``environment`` is rendered in
     front of it (its binding carries it), without a screen when the capture has none; ``reflection=True`` (needs such a capture and
-    ``fresnel``) adds the outer-surface reflection.  One process only."""
+    ``fresnel``) adds the outer-surface reflection.  ``absorption``: None (clear glass: the call of before),
+    ``render.check_absorption``'s forms, or an ``AbsorptionState``; every view is then rendered with absorbing glass
+    (drt_render_image_loss_views_absorb), in a room too.  With ``absorption_lr == 0`` sigma is fixed and the step stays free of
+    read-backs.  ``absorption_lr > 0`` fits sigma jointly with the mesh (from ``absorption``, or from 0 without one): after each step the
+    C accumulated partials are copied to the host -- ONE small device-to-host copy and synchronisation per step, which is why it is
+    opt-in --, weighted like the image term, and ``AbsorptionState.update`` makes the Adam step and the projection onto sigma >= 0 that
+    the next step's call takes.  ``self.absorption`` is the state (None for clear glass).  One process only."""
 
     def __init__(self, scene, data, HyperParams, lr, views_per_step=8, path_law=(6, "reflect", "snell"), fresnel=True, supersample=1, concurrent=True,
-                 schedule=None, max_samples=1 << 22, reflection=False):
+                 schedule=None, max_samples=1 << 22, reflection=False, absorption=None, absorption_lr=0.0):
         import torch.distributed as tdist
         if tdist.is_available() and tdist.is_initialized():
             raise NotImplementedError("PhotoIteration runs in one process: under an initialised torch.distributed group the photometric term "
@@ -541,6 +582,21 @@ class PhotoIteration(FusedIteration):
         self.fills = (render._fill(getattr(data, "void", 0.0), c, "void"), render._fill(getattr(data, "invalid", 0.0), c, "invalid"))
         self.ior = (Render._ior_host(hp["IOR"], "HyperParams['IOR']"), Render._ior_host(Render.extIOR, "extIOR"))
         self.last_views = []
+        if isinstance(absorption, AbsorptionState):
+            if absorption.sigma.shape != (c,):
+                raise ValueError(f"absorption: the state holds {absorption.sigma.size} coefficients, the capture has {c} channels")
+            self.absorption = absorption
+        elif absorption is None and not isinstance(absorption_lr, bool) and absorption_lr == 0:
+            self.absorption = None
+        else:
+            self.absorption = AbsorptionState(absorption, c, absorption_lr)
+        self._sigma_acc = self._sigma_like = None
+        if self.absorption is not None and self.absorption.fitted:
+            from . import det
+            with torch.cuda.device(dev):
+                self._sigma_like = torch.empty(c, dtype=Float, device=dev)
+                self._sigma_acc = det.acc(self._sigma_like)
+            self._fills.append(self._sigma_acc)
 
     def draw(self):
         """(image view ids, silhouette view ids) of this iteration, from the capture's two generators."""
@@ -555,7 +611,19 @@ class PhotoIteration(FusedIteration):
             return []
         return Render.enqueue_image_views_term(self.scene, vertices, self.binding, image_ids, self.texture, self.image_law, self.supersample, self.fresnel,
                                                *self.fills, self.ior, self._l_ptr[0], self._g_ptr[0], bands=self.bands_of(len(image_ids)),
-                                               reflection=self.reflection)
+                                               reflection=self.reflection, absorption=None if self.absorption is None else self.absorption.sigma,
+                                               grad_sigma_ptr=None if self._sigma_acc is None else self._sigma_acc.data_ptr())
+
+    def step(self):
+        """FusedIteration's step; with ``absorption_lr > 0`` followed by the read-back of the C sigma partials of this step and the
+        host-side update of the coefficients (``AbsorptionState.update``)."""
+        out = super().step()
+        if self._sigma_acc is not None and self.last_views:
+            from . import det
+            with torch.no_grad(), torch.cuda.device(self._sigma_acc.device):
+                partial = det.value(self._sigma_acc, self._sigma_like).cpu().numpy()          # (the step's one synchronisation)
+            self.absorption.update(self._weights()[0] * partial)
+        return out
 
     def _weights(self):
         hp, data = self.hp, self.data
@@ -564,10 +632,12 @@ class PhotoIteration(FusedIteration):
 
 
 def optimize_photometric(scene, data, HyperParams, views_per_step=8, remesh="isotropic", output=True, path_law=(6, "reflect", "snell"), fresnel=True,
-                         supersample=1, reflection=False):
+                         supersample=1, reflection=False, absorption=None, absorption_lr=0.0):
     """The pass / iteration loop of ``optimize_sharded`` on one rank with PhotoIteration steps: fits ``scene``'s mesh to the photographs of
     ``data`` (captured_data.PhotoData) under ``HyperParams`` (``image_w`` in the place of ``ray_w``; the other keys as in ``optimize``).
-    ``remesh`` as in ``optimize``; ``reflection`` as in PhotoIteration.  Returns (scene, history, stats): history = the weighted loss every 100 iterations, stats the passes,
+    ``remesh`` as in ``optimize``; ``reflection``, ``absorption`` and ``absorption_lr`` as in PhotoIteration: ONE ``AbsorptionState`` is made here and
+    handed to every pass's stepper, so a fit of the coefficients carries across passes; it is returned in ``stats["absorption"]`` (None for clear glass; its
+    ``sigma`` holds the final values).  Returns (scene, history, stats): history = the weighted loss every 100 iterations, stats the passes,
     iterations and ``step_seconds`` (the iterations without the remesh, device-synchronised at the end of each pass)."""
     remesh = resolve_remesh(remesh)
     hp = dict(HyperParams)
@@ -578,13 +648,19 @@ def optimize_photometric(scene, data, HyperParams, views_per_step=8, remesh="iso
     schedule = (data.ray_view_generator(), data.silh_view_generator())      # one view schedule across passes
     stats = {"views_per_step": int(views_per_step), "passes": 0, "iterations": 0, "step_seconds": 0.0}
     history = []
+    state = absorption
+    if not isinstance(state, AbsorptionState) and (absorption is not None or absorption_lr != 0):
+        from . import render
+        state = AbsorptionState(absorption, int(render.check_texture(data.texture).shape[2]) if data.screens is not None else int(data.environment.texels.shape[2]),
+                                absorption_lr)
+    stats["absorption"] = state
     for i_pass, remesh_len, lr in pass_schedule(hp):
         if output:
             print(f"remesh_len {remesh_len:g} lr {lr:g}")
         if remesh is not None:
             remesh(scene, remesh_len)
         stepper = PhotoIteration(scene, data, hp, lr, views_per_step, path_law=path_law, fresnel=fresnel, supersample=supersample, schedule=schedule,
-                                 reflection=reflection)
+                                 reflection=reflection, absorption=state)
         torch.cuda.synchronize(scene.vertices.device)
         t0 = time.perf_counter()
         run_steps(stepper, hp["Iters"], history, output)

@@ -736,11 +736,14 @@ def check_view_ids(view_ids, n_views):
 
 
 def check_image_views_law(binding, view_ids, texture, ior_int=None, ior_ext=None, vertices=True, supersample=1, max_bounces=2, tir="drop",
-                          refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, reflection=False):
+                          refraction="reference", fresnel=True, void=0.0, invalid=0.0, max_samples=1 << 22, reflection=False, absorption=None,
+                          want_images=False):
     """Every argument check of ``Scene.image_loss_views_fused`` behind the binding: ``check_render_args``' dict for the tall image of
     ``len(view_ids) * H`` rows (camera and screen are the first listed view's and stand for nothing), plus ids, ior and vertices.  The
     environment is the binding's (``a["environment"]``, or None); ``texture`` is None exactly when the binding has no screens;
-    ``reflection`` needs the binding's environment and ``fresnel``."""
+    ``reflection`` needs the binding's environment and ``fresnel``.  ``absorption``: ``check_absorption``'s forms,
+    C float64 coefficients or None in the dict -- here, unlike in the single-view calls, it goes with the binding's environment;
+    ``want_images``: True or False."""
     if not isinstance(binding, ImageViews):
         raise ValueError(f"binding must be a drt_amd.render.ImageViews (Scene.bind_image_views), got {type(binding).__name__}")
     ids = check_view_ids(view_ids, binding.n)
@@ -765,6 +768,12 @@ def check_image_views_law(binding, view_ids, texture, ior_int=None, ior_ext=None
     if not isinstance(vertices, (bool, np.bool_)):
         raise ValueError(f"vertices must be True or False, got {vertices!r}")
     a["vertices"] = bool(vertices)
+    a["absorption"] = check_absorption(absorption, a["channels"])
+    if not isinstance(want_images, (bool, np.bool_)):
+        raise ValueError(f"want_images must be True or False, got {want_images!r}")
+    if want_images and a["absorption"] is None:
+        raise ValueError("want_images=True needs absorption (0.0 renders clear glass): the clear multi-view calls write no image")
+    a["want_images"] = bool(want_images)
     return a
 
 

@@ -920,6 +920,31 @@ int drt_render_image_loss_views_env(drt_scene_t* s, const double* d_verts, const
                                     const float* d_weights, double* d_loss, double* d_grad_verts, double* d_grad_ior, int64_t* d_count, const float* d_env,
                                     int env_h, int env_w, const double* env_rot9, int reflection, void* stream);
 
+/* ---- ... of absorbing glass, in front of the screens, of one environment, or of both --------------------------------
+ * The SUM over the listed views of one view's loss under drt_render_image_loss_absorb's law, as ONE forward wavefront, at most ONE
+ * reflection pass and ONE adjoint pass: drt_render_image_loss_views' arguments up to d_count, then sigma and d_grad_sigma as in
+ * drt_render_image_loss_absorb (sigma: HOST array of `channels` values, finite and >= 0; d_grad_sigma: nullable, `channels` accumulators,
+ * wide in deterministic mode like d_grad_ior), then drt_render_image_loss_env's five, then d_images, before `stream`.  A through sample's
+ * transmitted colour is (A_ch T) B_ch, A_ch = exp(-(sigma_ch L)); B is the texture where the exit ray lands on its view's screen and
+ * otherwise, with an environment, the environment lookup -- attenuated exactly like the texture.  With reflection = 1 the sample also
+ * receives R1 B(ro, wr), NOT attenuated: that light never entered the object.  d loss / d sigma_ch = -g_c[ch] sum_j L_j c_j[ch] over the
+ * transmitted part of the through samples alone.  d_env == NULL: screens only -- d_texture is required and reflection must be 0.
+ * d_env != NULL: drt_render_image_loss_views_env's rules; d_texture == NULL then means no screen for any view.  d_images: nullable; a
+ * float32 stack [n_views, height, width, channels] in the capture's layout, of which the rendered pixels of the listed views' rows inside
+ * [r0, r1) are written (a view listed twice is written twice with the same values).  With every sigma_ch = 0 the loss, both gradients and
+ * the count have the bits of drt_render_image_loss_views / drt_render_image_loss_views_env in deterministic mode; the sigma partial is not
+ * zero there.  No environment texel or rotation gradient.  Workspace: drt_render_image_loss_views' and the interior lengths of
+ * drt_render_image_loss_absorb; growth inside a stream capture is refused with this function's name.  Both accumulation modes.
+ * DRT_E_INVALID (nothing enqueued, no output touched), in this order: what drt_render_image_loss_views refuses (with an environment a NULL
+ * d_texture is allowed), a NULL sigma or a coefficient that is negative or not finite, then what drt_render_image_loss_views_env refuses
+ * about the environment, or reflection != 0 without one -- the message names the argument.  drt_version() stays 13: probe for the symbol. */
+int drt_render_image_loss_views_absorb(drt_scene_t* s, const double* d_verts, const drt_image_views_t* views, const int* view_ids, int k, int r0, int r1,
+                                       int supersample, double ior_int, double ior_ext, int max_bounces, int law_flags, int fresnel, const float* d_texture,
+                                       int tex_h, int tex_w, int channels, const double* fill_void, const double* fill_invalid, const float* d_targets,
+                                       const float* d_weights, double* d_loss, double* d_grad_verts, double* d_grad_ior, int64_t* d_count, const double* sigma,
+                                       double* d_grad_sigma, const float* d_env, int env_h, int env_w, const double* env_rot9, int reflection, float* d_images,
+                                       void* stream);
+
 /* ---- measurement (bench.py's live per-kernel timing) --------------------------------------------
  * When enabled (on = 1; on = 2 additionally collects the traversal statistics below, which perturbs
  * timing; on = 3 runs the sub-batches of a call one after the other on ONE internal stream instead of two, so that
